@@ -5,8 +5,8 @@ Workload (N=1): configs[1] of BASELINE.json = c2: 1920x1080, 8 spheres + checker
 1 reflection bounce (SURVEY.md Appendix B scene, canonical framing pitch = 500/W).  One step = one full
 frame traced by rt_render_kernel (one launch) writing the RGBA32F framebuffer (unclamped HDR, the
 parity image) and the RGBA8 display image, all buffers resident in HBM.  Rays are the reference's
-actually-traced count (primary + reflected + shadow), taken from the kernel's own
-per-pixel ray counters before the timed region and checked against the reference's pinned total.
+actually-traced count (primary + reflected + shadow): the reference's pinned total, which
+`--full` checks against the kernel's own per-pixel ray counters before the timed region.
 
 N>1 (torch.distributed.run, one rank per GPU): `--scaling weak` (default) — frames are independent units,
 so every rank renders whole frames of its own (one per step) with no data-path collective; the job's rays
@@ -15,7 +15,13 @@ and gathered to rank 0 over RCCL by the C ABI's group (rt_group_create_rank + rt
 ncclRecv, double-buffered slabs), north_star's row-partitioned c4 design.  `--scaling streams` — N frames
 per step, each banded over all ranks, one RCCL all-to-all hands frame f to rank f (Python/torch exchange).
 
-Extra legs in the same JSON line (outside the timed region of `value`):
+A plain run sets up, warms up, times `--steps` steps and prints the line: `value` from the reference's pinned ray
+count, `ms_per_step` = the timed region / `--steps`, the rooflines from the timed interval.  `--dump-outputs DIR`
+writes the last timed step's RGBA32F and RGBA8 buffers as DIR/rgba32f.npy and DIR/rgba8.npy (float32; the scene and
+view are fixed, so the same arguments give the same inputs in every run and build).
+
+`--full` adds the parity and ray-count check of the timed frame against tests/golden, the one-stream launch
+duration the rooflines divide by, and the extra legs in the same JSON line (outside the timed region of `value`):
   * "c4" (every N, unless --no-c4): c3's 3840x2160 frame split over the N ranks + RCCL gather to rank 0
     through rt_render_multi (N = 1: a one-rank group, ncclSend/ncclRecv to self), frames/s and Mray/s, with
     the gathered frame checked byte for byte against a one-launch render;
@@ -44,6 +50,39 @@ FP64_PEAK_TFLOPS = 78.6        # MI355X FP64 vector spec (an FMA 
 # Algorithmic FP64 operations per frame (add, mul, div, sqrt = 1 each; SURVEY.md §8d counting restatement)
 FP64_FLOPS_PER_FRAME = {"c1": 71.4e6, "c2": 1.038e9, "c3": 5.417e9, "c4": 5.417e9, "c5": 122.6e9}
 BYTES_PER_PIXEL = 16 + 4       # RGBA32F framebuffer + RGBA8 display image written per pixel
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: bytes of .npy payload in all (the contract's limit is 64 MB)
+DUMP_SEED = 20240607            # --dump-outputs: seed of the pixel sample of a frame above the budget
+
+
+def dump_pixel_sample(n_pixels, bytes_per_pixel, budget=DUMP_BUDGET_BYTES):
+    """Which pixels of an n_pixels frame --dump-outputs writes, when every pixel costs bytes_per_pixel over all the
+    dumped arrays: None (all of them) within the budget, else a sorted sample without replacement that depends on
+    the frame size, the budget and DUMP_SEED only, so two builds dump the same pixels."""
+    import numpy as np
+    keep = budget // bytes_per_pixel
+    if n_pixels <= keep:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, size=keep, replace=False))
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write {name: (rows, W, C) device tensor} as dirname/<name>.npy in float32 (every value of an RGBA32F or RGBA8
+    buffer is exact in float32), (rows, W, C) whole or (pixels, C) sampled by dump_pixel_sample.  -> what was written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    n_pixels = {a.shape[0] * a.shape[1] for a in arrays.values()}
+    assert len(n_pixels) == 1, "the dumped buffers cover the same pixels"
+    n_pixels = n_pixels.pop()
+    idx = dump_pixel_sample(n_pixels, sum(4 * a.shape[2] for a in arrays.values()), budget)
+    info = {"dir": dirname, "dtype": "float32", "pixels": n_pixels if idx is None else int(idx.size),
+            "of_pixels": n_pixels, "sample_seed": None if idx is None else DUMP_SEED, "files": []}
+    for name, a in arrays.items():
+        h = a.detach().cpu().numpy().astype(np.float32)
+        if idx is not None:
+            h = h.reshape(n_pixels, h.shape[2])[idx]
+        np.save(os.path.join(dirname, name + ".npy"), h)
+        info["files"].append(name + ".npy")
+    return info
 
 
 def parse(argv=None):
@@ -51,6 +90,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the parity and ray-count check of the timed "
+                         "frame, the one-stream kernel time of the rooflines, the c4, c3/c5 and drop-in legs and the CPU "
+                         "baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step rendered (the frame buffers a caller "
+                         "of rt_render_dev receives) as DIR/<name>.npy in float32: every pixel, or, above "
+                         f"{DUMP_BUDGET_BYTES // 1_000_000} MB in all, the same fixed seeded sample of pixels of each")
     ap.add_argument("--config", default="c2", choices=["c1", "c2", "c3", "c5"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "streams", "strong"])
     ap.add_argument("--band-height", type=int, default=0, help="0: auto (equal rows per rank)")
@@ -92,6 +139,8 @@ def launch_plan(args, env, argv, device_count=None):
     ws = env.get("WORLD_SIZE")
     if args.gpus < 1:
         return "error", f"--gpus must be >= 1 (got {args.gpus})"
+    if args.steps < 1:
+        return "error", f"--steps must be >= 1 (got {args.steps}): the timed region holds that many steps"
     if ws is not None:
         try:
             w = int(ws)
@@ -857,6 +906,10 @@ def main() -> int:
     strong = world > 1 and args.scaling == "strong"         # one banded frame + RCCL gather (C ABI group)
     if strong and rehearsal:
         raise SystemExit("--scaling strong needs one GPU per rank (RCCL refuses two ranks on one device)")
+    if args.dump_outputs and (strong or streams):
+        raise SystemExit("--dump-outputs writes the frame buffers of whole-frame steps (one GPU, or --scaling weak)")
+    # A plain run does what `value` needs and no more; everything beside it waits for --full.
+    extras = args.full and not args.profile_kernel_only
     parity = "skipped"
     res_extra = {}
 
@@ -900,8 +953,8 @@ def main() -> int:
         fl = plan.frame_local[prank]           # ... per frame
 
         # ---- parity + ray count (outside the timed region) ----------------------------------------------
-        rays_frame = scenes.PINNED_RAYS.get(args.config)
-        if not args.profile_kernel_only:
+        rays_frame = scenes.PINNED_RAYS.get(args.config)   # (the reference's count; --full counts the frame's own)
+        if extras:
             chk = tr.render(cam, W, H, B, rgba32f=False, rgb64f=True, raycount=True)
             torch.cuda.synchronize()
             rc = chk["raycount"].cpu().numpy().view(np.uint32)
@@ -943,9 +996,12 @@ def main() -> int:
             barrier()
             elapsed, avg_kern_ms = pipelined_frames(torch, L, abi, trs, sts, launch_args, args.steps, args.settle)
             barrier()
-            # (skipped in --profile-kernel-only runs, whose trace must end with the timed dispatches)
-            kern_serial_ms = (None if args.profile_kernel_only else
-                              serial_kernel_ms(torch, L, abi, launch_args[0], stream))
+            if args.dump_outputs and rank == 0:              # the last timed step's buffers, before anything reuses them
+                last = (args.steps - 1) % nfly
+                res_extra["dump_outputs"] = dump_outputs(args.dump_outputs, {"rgba32f": outs[last][0],
+                                                                             "rgba8": outs[last][1]})
+            # (--full only; a --profile-kernel-only trace must end with the timed dispatches)
+            kern_serial_ms = serial_kernel_ms(torch, L, abi, launch_args[0], stream) if extras else None
             elapsed = max_over_ranks(elapsed)
             for t in trs[1:]:
                 t.close()
@@ -1015,8 +1071,10 @@ def main() -> int:
     roof["kernel_ms_serial"] = round(kern_serial_ms, 5) if kern_serial_ms is not None else None
     roof["interval_ms_in_flight"] = round(avg_kern_ms, 5)
     roof["frames_in_flight"] = nfly
-    roof["kernel_ms_note"] = ("kernel_ms = kernel_ms_serial: average duration of rt_render_kernel launched back to "
-                              "back on one stream (HIP events on that stream); interval_ms_in_flight: per-frame "
+    roof["kernel_ms_note"] = (("kernel_ms = kernel_ms_serial: average duration of rt_render_kernel launched back to "
+                               "back on one stream (HIP events on that stream); " if kern_serial_ms is not None else
+                               "kernel_ms = interval_ms_in_flight (the one-stream launch duration is timed with "
+                               "--full); ") + "interval_ms_in_flight: per-frame "
                               f"interval over the timed region with {nfly} launch stream(s), HIP events bracketing "
                               "them (a frame's launch overlaps the previous frame's tail when > 1)")
     prof = rocprof_reference(args.config, nl == H and world == 1)
@@ -1029,7 +1087,7 @@ def main() -> int:
         roof["traffic"] = None                               # the PMC figures are whole-frame, one GPU
 
     # ---- extra legs (outside the timed region of `value`) --------------------------------------------------
-    extra_ok = not args.profile_kernel_only
+    extra_ok = extras
 
     def result():
         """The JSON line (rank 0): the timed metric above plus the extra legs gathered so far."""
@@ -1040,6 +1098,7 @@ def main() -> int:
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(extras),
             "ms_per_step": round(ms_step, 4),
             "ms_per_frame": round(ms_step / job_frames, 4),
             "higher_is_better": True,
@@ -1243,7 +1302,7 @@ def main() -> int:
 
     if rank == 0:
         res = result()
-        if world == 1 and not args.no_cpu_baseline and not args.profile_kernel_only:
+        if world == 1 and extras and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args, cfg, scene, cam, W, H, B, rays_frame)
         print(json.dumps(res), file=out, flush=True)
     tr.close()

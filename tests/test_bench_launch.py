@@ -152,3 +152,45 @@ def test_c4_projection_keys():
     slow = bench.c4_projection_keys(8, 0.112, [0.001], 0.0005, 10_000_000)      # gather-bound
     assert slow["n8_limiting_stage"] == "gather (nominal xGMI)"
     assert slow["n8_projected_frame_ms"] == slow["n8_gather_ms_nominal"]
+
+
+def test_full_is_off_by_default_and_steps_are_checked():
+    """A plain run is the lean one; everything beside the headline figure waits for --full."""
+    a = _args("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    assert _args("--full").full is True
+    assert _args("--dump-outputs", "d").dump_outputs == "d"
+    kind, msg = bench.launch_plan(_args("--steps", "0"), {}, [])
+    assert kind == "error" and "--steps" in msg
+
+
+def test_dump_pixel_sample_is_fixed_and_within_budget():
+    """--dump-outputs: every pixel within the budget, else the same sorted sample in every run and build."""
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000
+    assert bench.dump_pixel_sample(160 * 120, 32) is None
+    assert bench.dump_pixel_sample(1000, 32, budget=32_000) is None                  # exactly the budget
+    n = 1920 * 1080
+    idx = bench.dump_pixel_sample(n, 32)
+    assert idx.size == bench.DUMP_BUDGET_BYTES // 32 and idx.size * 32 <= bench.DUMP_BUDGET_BYTES
+    assert idx[0] >= 0 and idx[-1] < n and (idx[1:] > idx[:-1]).all()               # sorted, no pixel twice
+    assert (idx == bench.dump_pixel_sample(n, 32)).all()
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    f = torch.arange(6 * 5 * 4, dtype=torch.float32).reshape(6, 5, 4) / 7
+    b = (torch.arange(6 * 5 * 4) % 256).to(torch.uint8).reshape(6, 5, 4)
+    info = bench.dump_outputs(str(tmp_path / "whole"), {"rgba32f": f, "rgba8": b})
+    assert info["pixels"] == info["of_pixels"] == 30 and info["sample_seed"] is None
+    got_f, got_b = (np.load(tmp_path / "whole" / n) for n in ("rgba32f.npy", "rgba8.npy"))
+    assert got_f.dtype == got_b.dtype == np.float32
+    assert np.array_equal(got_f, f.numpy()) and np.array_equal(got_b, b.numpy().astype(np.float32))
+    # above the budget: the same pixels of both buffers, chosen by dump_pixel_sample
+    info = bench.dump_outputs(str(tmp_path / "part"), {"rgba32f": f, "rgba8": b}, budget=7 * 32)
+    idx = bench.dump_pixel_sample(30, 32, budget=7 * 32)
+    assert info["pixels"] == 7 == idx.size and info["of_pixels"] == 30 and info["sample_seed"] == bench.DUMP_SEED
+    got_f, got_b = (np.load(tmp_path / "part" / n) for n in ("rgba32f.npy", "rgba8.npy"))
+    assert got_f.shape == got_b.shape == (7, 4) and got_f.dtype == got_b.dtype == np.float32
+    assert np.array_equal(got_f, f.numpy().reshape(30, 4)[idx])
+    assert np.array_equal(got_b, b.numpy().reshape(30, 4).astype(np.float32)[idx])

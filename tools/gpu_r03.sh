@@ -15,7 +15,7 @@ if [ "${TESTS:-1}" = "1" ]; then
   [ $rc -eq 0 ] || { echo "pytest rc=$rc"; exit $rc; }
 fi
 if [ "${BENCH:-1}" = "1" ]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 3; }
   cat "$OUT/bench.json"
 fi

@@ -37,7 +37,7 @@ if want diag; then
   rc=$?; cat "$OUT/diag.log"; [ $rc -eq 0 ] || { echo "diag rc=$rc"; exit 14; }
 fi
 if want bench; then
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 3; }
   cat "$OUT/bench.json"
 fi

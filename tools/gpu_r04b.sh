@@ -21,7 +21,7 @@ if want ab; then
   cat "$OUT/ab.jsonl"
 fi
 if want bench; then
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 3; }
   python3 -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms_serial'], d['roofline']['interval_ms_in_flight'], {k: v.get('kernel_ms_serial') for k, v in d.get('configs', {}).items()}, d.get('drop_in', {}).get('moving_camera', {}).get('ms_per_frame'))"
 fi

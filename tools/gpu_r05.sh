@@ -92,12 +92,12 @@ if want ab; then
   cat "$OUT/ab.jsonl"
 fi
 if want bench; then
-  timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
+  timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err" \
       || { echo "bench failed"; tail -30 "$OUT/bench.err"; exit 3; }
   python3 -c "import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']; print(d['value'], d['ms_per_step'], r['kernel_ms_serial'], r['interval_ms_in_flight'], {k: v.get('kernel_ms_serial') for k, v in d.get('configs', {}).items()}, json.dumps(d.get('c4', {}))[:1200], json.dumps(d.get('drop_in', {}))[:900])"
 fi
 if want rehearse; then
-  timeout -k 10 600 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline \
+  timeout -k 10 600 python bench.py --full --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline \
       > "$OUT/rehearse.json" 2> "$OUT/rehearse.err" || { echo "rehearsal failed"; tail -30 "$OUT/rehearse.err"; exit 4; }
   python3 -c "import json; d=json.load(open('$OUT/rehearse.json')); print(d['n_gpus'], d['value'], d['config']['parallelism']); print(json.dumps(d.get('c4'))[:1500])"
 fi
