@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 7
+#define RT_ABI_VERSION 8
 
 #define RT_OK            0
 #define RT_EINVAL       -1   /* bad argument (null pointer, size, unsupported material, ...) */
@@ -211,6 +211,40 @@ int rt_set_scene(rt_ctx* ctx, const rt_scene* scene);
 int rt_render_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth,
                   const rt_rows* rows, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                   uint32_t* raycount, void* stream);
+
+/* ---- supersampled rendering (ABI 8) -------------------------------------------------------------- */
+/* S x S samples per pixel (S = `samples` in {1, 2, 4, 8}) on a regular grid, summed in the render kernel, so only
+ * the width x height output pixels are written.  This is NOT the app's jittered, adaptive rayTraceScreen
+ * (rt_render_screen is): the samples are fixed, and every one of them is a pixel of the existing contract.
+ *  1. Sample-grid camera cam_s (rt_camera_supersample): eye, look_at and up of `cam`; pitch_s = cam.pitch / S
+ *     (exact: S is a power of two); bottom_x_s = S * cam.bottom_x, bottom_y_s = S * cam.bottom_y (RT_EINVAL when
+ *     a product overflows int32).  For odd W this is not the camera rt_camera_init_reference(S * W, ...) makes:
+ *     -S * (W / 2) differs from -(S * W) / 2.
+ *  2. Sample (a, b) of pixel (i, j), 0 <= a, b < S, has the colour rt_render_dev gives pixel (S i + a, S j + b) of
+ *     the S W x S H frame of cam_s: rayTraceRay on the primary ray of the camera comment above.  The samples of a
+ *     pixel cover its cell [i, i + 1) x [j, j + 1) in pitch units, starting at the one-sample render's point.
+ *  3. Per channel, in FP64, the samples are summed as a fixed pairwise tree: first along a, v[a] <- v[2a] + v[2a+1]
+ *     repeated log2 S times, then the same along b, then one multiplication by 1.0 / (S * S) (exact).  The order is
+ *     part of the contract: another order differs in the last bits.
+ *  4. rgb64f is that value; rgba32f its (float) with alpha 1; rgba8 floor(clamp(c, 0, 1) * 255 + 0.5) of it.
+ *     raycount2 holds two uint32 per pixel: primary + reflected segments, then shadow rays, each summed over the
+ *     pixel's samples (the packed 16 + 16-bit word of rt_render_dev would overflow).
+ *  5. The reference yields NaN colours in some ray-tree scenes.  A channel with a NaN sample is NaN; which NaN
+ *     (sign, payload) is unspecified.  rgba8 of a NaN is 0, as in rt_render_dev.
+ *  6. samples = 1 writes the images rt_render_dev writes (the counters still as two words).
+ * Host only: *out = cam_s (out may be cam).  RT_EINVAL for samples outside {1, 2, 4, 8} or int32 overflow. */
+int rt_camera_supersample(const rt_camera* cam, int samples, rt_camera* out);
+/* The supersampled render of this rank's rows.  Device pointers, each nullable, local_rows * width pixels;
+ * asynchronous on `stream`, no allocation: the rules of rt_render_dev (view calibration and hipGraph capture
+ * included, applied to the sample grid).  `rows` with frames <= 1 is honoured (bands are cut in output rows);
+ * frames > 1 with samples > 1 fails with RT_EINVAL, as does samples outside {1, 2, 4, 8}. */
+int rt_render_ss_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples,
+                     const rt_rows* rows, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                     void* stream);
+/* Synchronous host-buffer convenience, as rt_render (full frame).  *stats: primary_rays = width * height * S * S,
+ * reflect_rays and shadow_rays from the summed counters. */
+int rt_render_ss(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int width, int height, int depth,
+                 int samples, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

@@ -17,6 +17,9 @@
 //                                                  one frame's rows split over 8 GPUs (rt_group, RCCL gather to
 //                                                  GPU 0); with fewer GPUs than --gpus the
 //                                                  contexts share devices and the gather is a device copy
+//   rt_render --config c2 --samples 4 --out c2_ss.ppm
+//                                                  S x S regular-grid samples per pixel summed in the kernel
+//                                                  (rt_render_ss; S in 1, 2, 4, 8 — not the app's jittered mode)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -44,6 +47,7 @@ struct Options {
     int gpus = 0;                            // > 0: rt_group over this many ranks (rt_render_multi)
     int band = 0;                            // band height (0: auto)
     int repeat = 1;                          // frames rendered (the last one is written)
+    int samples = 0;                         // > 0: rt_render_ss with this many samples per axis (plain frames only)
 };
 
 [[noreturn]] void die(const std::string& what, int code) {
@@ -170,9 +174,15 @@ int main(int argc, char** argv) {
         else if (a == "--gpus") o.gpus = std::atoi(next().c_str());
         else if (a == "--band") o.band = std::atoi(next().c_str());
         else if (a == "--repeat") o.repeat = std::max(1, std::atoi(next().c_str()));
+        else if (a == "--samples") o.samples = std::atoi(next().c_str());
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
-                                    "[--gpus N [--band H]] [--repeat K] [--out file.ppm]\n"); return 2; }
+                                    "[--gpus N [--band H]] [--samples 1|2|4|8] [--repeat K] [--out file.ppm]\n");
+               return 2; }
+    }
+    if (o.samples != 0 && (o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --samples applies to plain frames (not --faithful or --gpus)\n");
+        return 2;
     }
 
     rt_scene scene;
@@ -279,8 +289,13 @@ int main(int argc, char** argv) {
     }
     rt_stats st;
     const auto t0 = std::chrono::steady_clock::now();
-    for (int k = 0; k < o.repeat; ++k)
-        check(rt_render(ctx, &scene, &cam, W, H, depth, nullptr, nullptr, rgba8.data(), nullptr, &st), "rt_render");
+    for (int k = 0; k < o.repeat; ++k) {
+        if (o.samples != 0)
+            check(rt_render_ss(ctx, &scene, &cam, W, H, depth, o.samples, nullptr, rgba8.data(), nullptr, &st),
+                  "rt_render_ss");
+        else
+            check(rt_render(ctx, &scene, &cam, W, H, depth, nullptr, nullptr, rgba8.data(), nullptr, &st), "rt_render");
+    }
     const double per_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() /
                                o.repeat;
     check(rt_write_ppm(o.out.c_str(), rgba8.data(), W, H, 4), "rt_write_ppm");
@@ -290,6 +305,7 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
+    if (o.samples != 0) std::printf("rt_render: %d x %d samples per pixel, summed in the kernel\n", o.samples, o.samples);
     if (o.repeat > 1) std::printf("rt_render: %d calls, %.3f ms per call (host to host)\n", o.repeat, per_call_ms);
     rt_ctx_destroy(ctx);
     return 0;

@@ -189,6 +189,23 @@ extern "C" int rt_camera_init_reference(rt_camera* cam, int width, int height, d
     return RT_OK;
 }
 
+// The sample-grid camera of a supersampled render (rt_api.h): pixel (S i + a, S j + b) of this camera's frame is
+// sample (a, b) of pixel (i, j) of `cam`'s.
+extern "C" int rt_camera_supersample(const rt_camera* cam, int samples, rt_camera* out) {
+    if (!cam || !out) return rt_fail(RT_EINVAL, "rt_camera_supersample: null pointer");
+    if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
+        return rt_fail(RT_EINVAL, "rt_camera_supersample: samples must be 1, 2, 4 or 8");
+    const long long bx = (long long)cam->bottom_x * samples, by = (long long)cam->bottom_y * samples;
+    if (bx < INT32_MIN || bx > INT32_MAX || by < INT32_MIN || by > INT32_MAX)
+        return rt_fail(RT_EINVAL, "rt_camera_supersample: samples * bottom_x / bottom_y overflows int32");
+    rt_camera c = *cam;                                                         // (out may alias cam)
+    c.pitch = cam->pitch / (double)samples;                                     // exact: a power of two
+    c.bottom_x = (int32_t)bx;
+    c.bottom_y = (int32_t)by;
+    *out = c;
+    return RT_OK;
+}
+
 namespace {
 
 int frames_of(const rt_rows* r) { return (r && r->frames > 1) ? r->frames : 1; }

@@ -11,7 +11,7 @@
 //                             longest first from a calibration render's per-tile wave times
 //   rt_intersect_kernel       g_scene.intersection on an arbitrary ray list (primitive KATs)
 //   rt_unpack_kernel          multi-GPU: gathered row bands -> image order, packed pixels -> RGBA
-//   rt_raysum_kernel          rt_render's ray statistics
+//   rt_raysum_kernel          rt_render's ray statistics (rt_raysum2_kernel: rt_render_ss's two-word counters)
 //
 // Reference: /root/reference/Hw4/MySdlApplication.cpp (rayTraceScreen :1251-1324, rayTraceRay
 // :1184-1249, intersection code :611-823, :1084-1113).
@@ -395,6 +395,26 @@ __global__ __launch_bounds__(kThreads) void rt_raysum_kernel(const uint32_t* __r
         const uint32_t v = rc[k];
         seg += v & 0xffffu;
         sh += v >> 16;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        seg += __shfl_down(seg, o);
+        sh += __shfl_down(sh, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(sums, seg);
+        atomicAdd(sums + 1, sh);
+    }
+}
+
+// ... of a supersampled render's two-word counters (rt_render_ss_dev: rc2[2 k] segments, rc2[2 k + 1] shadow rays).
+__global__ __launch_bounds__(kThreads) void rt_raysum2_kernel(const uint32_t* __restrict__ rc2, size_t n,
+                                                              unsigned long long* __restrict__ sums) {
+    unsigned long long seg = 0, sh = 0;
+    const uint2* v2 = reinterpret_cast<const uint2*>(rc2);
+    for (size_t k = (size_t)blockIdx.x * kThreads + threadIdx.x; k < n; k += (size_t)gridDim.x * kThreads) {
+        const uint2 v = v2[k];
+        seg += v.x;
+        sh += v.y;
     }
     for (int o = 32; o > 0; o >>= 1) {
         seg += __shfl_down(seg, o);
@@ -871,12 +891,21 @@ static bool byte_format(int f) { return f == RT_PIXEL_RGBA8 || f == RT_PIXEL_RGB
 
 // The device render behind rt_render_dev / rt_render_dev_packed: the float image (fmt_f) and the byte image
 // (fmt_8) in their formats, the FP64 colour and the ray counters, each nullable.
+// ss_log2 >= 0 (rt_render_ss_dev): cam, W, H and rows describe the SAMPLE grid of a supersampled render with
+// S = 1 << ss_log2 samples per axis; the outputs hold (W / S) x (local rows / S) pixels, RGBA formats, and the ray
+// counters are two words per pixel.  Everything per view (order, calibration, cached masks, capture rules) is the
+// sample grid's, unchanged; the kernels are the supersampled instances, which differ in their epilogue only.
 static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
                            int fmt_f, void* pf, int fmt_8, void* p8, double* rgb64f, uint32_t* raycount,
-                           void* stream) {
+                           void* stream, int ss_log2 = -1) {
     RenderParams P;
     int rc = render_params(c, cam, W, H, depth, rows, &P);
     if (rc) return rc;
+    const bool ss = ss_log2 >= 0;
+    if (ss) {
+        P.ss_log2 = ss_log2;
+        P.wg_staging = 0;                           // one-wave direct-store instances only
+    }
     if ((pf && !float_format(fmt_f)) || (p8 && !byte_format(fmt_8)))
         return rt_fail(RT_EINVAL, "render: bad pixel format for the float / byte image");
     if (((pf && fmt_f == RT_PIXEL_GRAY32F) || (p8 && fmt_8 == RT_PIXEL_GRAY8)) && !c->achromatic)
@@ -891,7 +920,7 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
     // tiles) at every config (c2 -1%, c3 -3%, c5 -12%: a finished wave's slot is refilled without
     // waiting for three siblings).  The A/B variants that share a workgroup-wide LDS copy (scene in LDS,
     // staged row stores) keep 256 threads.
-    const bool big = !packed && (c->use_lds || c->wg_staging);    // packed formats: one-wave variants only
+    const bool big = !packed && !ss && (c->use_lds || c->wg_staging);    // packed formats, supersampling: one-wave variants only
     const int tw = big ? kTileW : RT_WG_FAST / 8;
     const int tiles_x = (W + tw - 1) / tw;
     const int tiles_y = (P.local_rows + kTileH - 1) / kTileH;
@@ -921,8 +950,10 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
         memcpy(kp, cam, sizeof(rt_camera)); kp += sizeof(rt_camera);
         // which outputs are written (and in which format) changes the rows' relative cost (an RGB64F parity
         // render writes 24 B per pixel): each output set gets its own calibration
+        // (and a supersampled render its own: it shares the camera and size of a plain render of its sample grid,
+        // not its stores)
         const int outs = (pf ? 1 : 0) | (p8 ? 2 : 0) | (rgb64f ? 4 : 0) | (raycount ? 8 : 0) | (P.fmt_f << 4) |
-                         (P.fmt_8 << 6);
+                         (P.fmt_8 << 6) | ((ss ? ss_log2 + 1 : 0) << 8);
         const int ints[6] = {W, H, depth, tiles_x, tiles_y, outs};
         memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
         if (rows) memcpy(kp, rows, sizeof(rt_rows));
@@ -1025,7 +1056,7 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
     }
     RenderLaunch L;
     // achromatic opaque scenes: the one-channel instances (rt_device.hpp shade ACHRO; RT_ACHRO_OFF=1 for A/B)
-    L.achro = c->achromatic && !c->transparent && !c->tree && !c->achro_off;
+    L.achro = c->achromatic && !c->transparent && !c->tree && !c->achro_off && !ss;
     L.grid = grid;
     L.stream = st;
     L.scene = c->d_scene;
@@ -1056,6 +1087,12 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
         if (c->tree) L.variant = kVarTreePacked;
         else if (c->transparent) L.variant = kVarTranspPacked;
         else L.variant = cull ? kVarCullPacked : kVarFastPacked;
+        if (!c->tree && !c->transparent) L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
+    }
+    if (ss) {                                           // the supersampled instances, one per scene kind
+        if (c->tree) L.variant = kVarTreeSS;
+        else if (c->transparent) L.variant = kVarTranspSS;
+        else L.variant = cull ? kVarCullSS : kVarFastSS;
         if (!c->tree && !c->transparent) L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
     }
     switch (depth) {
@@ -1144,6 +1181,46 @@ extern "C" int rt_render_dev_packed(rt_ctx* c, const rt_camera* cam, int W, int 
                                     void* stream) {
     return render_dev_impl(c, cam, W, H, depth, rows, float_format, float_pixels, byte_format, byte_pixels, nullptr,
                            nullptr, stream);
+}
+
+// log2 of a supersampling factor in {1, 2, 4, 8}, or -1.
+static int ss_log2_of(int samples) {
+    return samples == 1 ? 0 : samples == 2 ? 1 : samples == 4 ? 2 : samples == 8 ? 3 : -1;
+}
+
+// rt_render_ss_dev: the render of the sample grid (camera rt_camera_supersample, S W x S H, row bands S times as
+// high, so every S-row block of samples stays inside one band) through the supersampled kernel instances.
+extern "C" int rt_render_ss_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                const rt_rows* rows, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                uint32_t* raycount2, void* stream) {
+    const int s = ss_log2_of(samples);
+    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_ss_dev: samples must be 1, 2, 4 or 8");
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (long long)W * samples > INT32_MAX || (long long)H * samples > INT32_MAX)
+        return rt_fail(RT_EINVAL, "render: bad image size");
+    int nl = 0;
+    int rc = rt_local_rows(H, rows, &nl);               // the caller's row plan, checked as given
+    if (rc) return rc;
+    if (rows && rows->frames > 1 && samples > 1)
+        return rt_fail(RT_EINVAL, "rt_render_ss_dev: frames > 1 is not supported with samples > 1");
+    // S = 1 without counters is rt_render_dev itself (the two-word counters need the supersampled instances)
+    if (s == 0 && !raycount2)
+        return render_dev_impl(c, cam, W, H, depth, rows, RT_PIXEL_RGBA32F, rgba32f, RT_PIXEL_RGBA8, rgba8, rgb64f,
+                               nullptr, stream);
+    rt_camera cam_s;
+    rc = rt_camera_supersample(cam, samples, &cam_s);
+    if (rc) return rc;
+    rt_rows rows_s{};
+    if (rows) {
+        rows_s = *rows;
+        if (rows->n_ranks > 1) {
+            if ((long long)rows->band_height * samples > INT32_MAX) return rt_fail(RT_EINVAL, "render: bad band height");
+            rows_s.band_height = rows->band_height * samples;
+        }
+    }
+    return render_dev_impl(c, &cam_s, W * samples, H * samples, depth, rows ? &rows_s : nullptr, RT_PIXEL_RGBA32F,
+                           rgba32f, RT_PIXEL_RGBA8, rgba8, rgb64f, raycount2, stream, s);
 }
 
 // Grow-only device buffer k of the context (rt_render's outputs).
@@ -1259,6 +1336,47 @@ extern "C" int rt_render(rt_ctx* c, const rt_scene* scene, const rt_camera* cam,
         if (host[k] && npx && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
     RT_HIP(hipStreamSynchronize(c->rs));
     if (stats) return read_stats(c, npx, (const unsigned long long*)d[4], stats);
+    return RT_OK;
+}
+
+// rt_render for a supersampled frame (rt_render_ss_dev into the context's device buffers, then the copies back).
+extern "C" int rt_render_ss(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                            int samples, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
+    if (!c) return rt_fail(RT_EINVAL, "rt_render_ss: null context");
+    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_ss: samples must be 1, 2, 4 or 8");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31)) return rt_fail(RT_EINVAL, "rt_render_ss: bad image size");
+    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
+    if (rc) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    const size_t npx = (size_t)W * H;
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
+    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
+    for (int k = 0; k < 5; ++k)
+        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->ev0, c->rs));
+    rc = rt_render_ss_dev(c, cam, W, H, depth, samples, nullptr, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                          (uint32_t*)d[3], c->rs);
+    if (rc) return rc;
+    RT_HIP(hipEventRecord(c->ev1, c->rs));
+    if (stats) {
+        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
+        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
+                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
+        RT_HIP(hipGetLastError());
+    }
+    void* host[3] = {rgba32f, rgba8, rgb64f};
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->rs));
+    if (stats) {
+        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
+        if (rc) return rc;
+        // every sample is a primary ray: the summed segment counters hold S * S of them per pixel
+        const uint64_t prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples;
+        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+        stats->primary_rays = prim;
+    }
     return RT_OK;
 }
 

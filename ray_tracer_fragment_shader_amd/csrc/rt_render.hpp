@@ -10,6 +10,9 @@
 //                             scalar cache; the A/B variants with 256-thread workgroups (32 x 8 tiles) copy it
 //                             into LDS once per workgroup (LDS = 1) or stage the output tile in LDS for 32-pixel
 //                             row stores.  Per-level colours wait in LDS slots; stores go out per wave.
+//                             SS = true (the last template parameter; rt_render_ss_dev): the same trace on the
+//                             sample grid of a supersampled frame, and an epilogue that sums each pixel's S x S
+//                             samples across the wave before the one store per pixel.
 //   rt_trace_rays_kernel<B>   rayTraceRay on an arbitrary ray list (parity / fuzz / faithful-screen entry).
 //
 // Output pixel formats (RenderParams::fmt_f / fmt_8, wave-uniform): the float image is RGBA32F (16 B/px) or
@@ -174,6 +177,10 @@ struct RenderParams {
     uint64_t* lmask_out;
     const uint64_t* lmask_in;
     int32_t lmask_stride;
+    // Supersampled instances (render_body SS): log2 of the samples per axis S.  The other fields then describe the
+    // sample grid (width = S x the output's, local_rows = S x its rows); the epilogue sums each pixel's S x S
+    // samples in the wave and stores the output pixel.  (In the struct's tail padding: no other field moves.)
+    int32_t ss_log2;
 };
 
 // The dispatch table's geometry, scalar arguments right after the table, so that gfx950's kernarg preload
@@ -310,7 +317,7 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 
 }
 
 template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG = kThreads, bool TREE = false,
-          bool PACKED = false, bool FIX64 = false, bool ACHRO = false>
+          bool PACKED = false, bool FIX64 = false, bool ACHRO = false, bool SS = false>
 __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene, RenderParams P,
                                             const DispRec* __restrict__ disp, DispGeom geom) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -458,6 +465,43 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
 #endif
         const int lane_e = tid_e & 63;
         const int i_e = tx * TW + (tid_e >> 6) * bw + (lane_e & 7), lr_e = ty_st * kTileH + (lane_e >> 3);
+        if constexpr (SS) {
+            // Supersampled instance: lane (x, y) of the 8 x 8 tile holds sample (x mod S, y mod S) of output pixel
+            // (tile_x * 8 / S + x / S, tile_row * 8 / S + y / S).  The S x S samples of a pixel are summed per channel
+            // in FP64 as the fixed pairwise tree of include/rt_api.h (rt_render_ss_dev): an xor butterfly over lane
+            // bits 0..2 (x: partners 1, 2, .. S/2), then bits 3..5 (y: 8, 16, .. 8 S/2), every lane active.  IEEE
+            // addition is commutative bit for bit for non-NaN operands, so all lanes of a pixel's block end with the
+            // same bits (a NaN's sign and payload may differ by lane: unspecified); 1 / S^2 is a power of two.
+            static_assert(WG == 64 && !PACKED && !LDS, "supersampling: one-wave RGBA direct-store instances only");
+            const int s = P.ss_log2, S1 = (1 << s) - 1;
+            for (int m = 1; m <= S1; m <<= 1) {
+                col.x += __shfl_xor(col.x, m);
+                col.y += __shfl_xor(col.y, m);
+                col.z += __shfl_xor(col.z, m);
+                seg += __shfl_xor(seg, m);
+                sh += __shfl_xor(sh, m);
+            }
+            for (int m = 8; m <= 8 * S1; m <<= 1) {
+                col.x += __shfl_xor(col.x, m);
+                col.y += __shfl_xor(col.y, m);
+                col.z += __shfl_xor(col.z, m);
+                seg += __shfl_xor(seg, m);
+                sh += __shfl_xor(sh, m);
+            }
+            col = scl(ldexp(1.0, -2 * s), col);                // 1.0 / (S * S), exact
+            // P.width and P.local_rows are the sample frame's: S x the output's width and local rows, and S divides
+            // 8, so an S x S block lies either wholly inside the sample frame or wholly outside it: the block of an
+            // in-frame pixel never holds a clamped out-of-frame sample, and the test on the block's first lane is
+            // the test on W and the output's local rows.  (Padding dispatch positions: lr_e is past every row.)
+            if (((lane_e & 7) & S1) == 0 && ((lane_e >> 3) & S1) == 0 && i_e < P.width && lr_e < P.local_rows) {
+                const RenderOuts O = late_outputs();
+                const size_t k = (size_t)(lr_e >> s) * (size_t)(P.width >> s) + (size_t)(i_e >> s);
+                store_pixel<false>(P, k, col, O.o32, O.o8);
+                if (O.o64) { O.o64[3 * k] = col.x; O.o64[3 * k + 1] = col.y; O.o64[3 * k + 2] = col.z; }
+                // two words per pixel (summed over S^2 ray trees the packed 16 + 16-bit word would overflow)
+                if (O.orc) { O.orc[2 * k] = seg; O.orc[2 * k + 1] = sh; }
+            }
+        } else
         if (i_e < P.width && lr_e < P.local_rows) {
             const RenderOuts O = late_outputs();
             const size_t k = (size_t)lr_e * P.width + i_e;
@@ -517,11 +561,11 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
 // (out32 .. outrc are read by late_outputs() from the argument segment, not through the parameters.)
 // The parameter list must match RenderArgs field for field: kernarg_offsets_match below checks it at compile time.
 template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG = kThreads, bool TREE = false,
-          bool PACKED = false, bool FIX64 = false, bool ACHRO = false>
+          bool PACKED = false, bool FIX64 = false, bool ACHRO = false, bool SS = false>
 __global__ __launch_bounds__(WG, MINW) void rt_render_kernel(const DispRec* __restrict__ disp, int32_t tiles_x, int32_t n_disp,
                                                              const DevScene* __restrict__ gscene, RenderParams P,
                                                              void* out32, void* out8, double* out64, uint32_t* outrc) {
-    render_body<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO>(gscene, P, disp, DispGeom{tiles_x, n_disp});
+    render_body<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS>(gscene, P, disp, DispGeom{tiles_x, n_disp});
 }
 
 // The same kernel with its SGPRs capped at RT_FAST_SGPRS (amdgpu_num_sgpr: a constant, hence a kernel of its
@@ -692,6 +736,12 @@ enum RenderVariant {
     kVarCullPacked,
     kVarTranspPacked,
     kVarTreePacked,
+    // supersampled renders (rt_render_ss_dev: render_body SS), one per scene kind: three channels, RGBA formats,
+    // one-wave workgroups, no SGPR cap (an achromatic scene's bits are the same in the three-channel kernel)
+    kVarFastSS,
+    kVarCullSS,
+    kVarTranspSS,
+    kVarTreeSS,
     kVarCount
 };
 
@@ -733,9 +783,9 @@ RT_DECLARE_DEPTH(4) RT_DECLARE_DEPTH(5) RT_DECLARE_DEPTH(6) RT_DECLARE_DEPTH(7)
 
 // Body of the per-depth instance files.
 template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG, bool TREE, bool PACKED = false, bool FIX64 = false,
-          bool ACHRO = false>
+          bool ACHRO = false, bool SS = false>
 hipError_t launch_render_one(const RenderLaunch& L) {
-    auto kern = rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO>;
+    auto kern = rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS>;
     if (L.lds > 65536) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
         if (e != hipSuccess) return e;
@@ -766,6 +816,10 @@ hipError_t launch_render_sg(const RenderLaunch& L) {
 #endif
 #ifndef RT_ACHRO_MAX_B
 #define RT_ACHRO_MAX_B 3
+#endif
+// The supersampled instances (kVar*SS; one-wave tiles).  0: not built (experiment builds; rt_render_ss_dev then fails).
+#ifndef RT_SS
+#define RT_SS (RT_WG_FAST == 64)
 #endif
 
 template <int B>
@@ -828,6 +882,19 @@ hipError_t launch_render_impl(const RenderLaunch& L) {
                 return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, true>(L);
             case kVarTranspPacked: return launch_render_one<B, 0, 1, true, false, 64, false, true>(L);
             case kVarTreePacked: return launch_render_one<B, 0, 1, true, false, 64, true, true>(L);
+#if RT_SS
+            case kVarFastSS:
+                return launch_render_one<B, 0, (B <= 3 ? MW : 1), false, false, RT_WG_FAST, false, false, false, false,
+                                         true>(L);
+            case kVarCullSS:
+                if (RT_CULL_FIX64 && L.P.ns == kCullStride)
+                    return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, false,
+                                             true, false, true>(L);
+                return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, false,
+                                         false, false, true>(L);
+            case kVarTranspSS: return launch_render_one<B, 0, 1, true, false, 64, false, false, false, false, true>(L);
+            case kVarTreeSS: return launch_render_one<B, 0, 1, true, false, 64, true, false, false, false, true>(L);
+#endif
             default: return hipErrorInvalidValue;
         }
     }

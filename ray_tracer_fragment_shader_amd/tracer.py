@@ -75,6 +75,34 @@ class Tracer:
         bufs = self.alloc(width, height, rows, rgba32f, rgba8, rgb64f, raycount)
         return self.render_into(cam, width, height, depth, bufs, rows, stream)
 
+    # ------------------------------------------------------------------------------- supersampled render
+    def alloc_ss(self, width: int, height: int, rows: Optional[abi.rt_rows] = None, rgba32f=True, rgba8=False,
+                 rgb64f=False, raycount=False):
+        """Buffers of a supersampled render: as alloc(), but `raycount` holds two words per pixel, shape
+        (rows, W, 2): primary + reflected segments and shadow rays, summed over the pixel's samples."""
+        bufs = self.alloc(width, height, rows, rgba32f, rgba8, rgb64f, False)
+        if raycount:
+            nl = scenes.local_rows(height, rows)
+            bufs["raycount"] = torch.empty((nl, width, 2), dtype=torch.int32, device=torch.device("cuda", self.device))
+        return bufs
+
+    def render_ss_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int, bufs: dict,
+                       rows: Optional[abi.rt_rows] = None, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_ss_dev: samples x samples regular-grid samples per pixel summed in the kernel (samples in
+        1, 2, 4, 8); asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_ss_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
+                                             ctypes.byref(rows) if rows is not None else None,
+                                             _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
+                                             _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
+                                             ctypes.c_void_p(st.cuda_stream)), "rt_render_ss_dev")
+        return bufs
+
+    def render_ss(self, cam, width, height, depth, samples, rows=None, rgba32f=True, rgba8=False, rgb64f=False,
+                  raycount=False, stream=None):
+        bufs = self.alloc_ss(width, height, rows, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_ss_into(cam, width, height, depth, samples, bufs, rows, stream)
+
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):
         """rt_render_dev_packed: the float image in float_format (RT_PIXEL_RGBA32F / GRAY32F) and the byte
