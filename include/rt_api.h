@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define RT_ABI_VERSION 8
+#define RT_ABI_VERSION 9
 
 #define RT_OK            0
 #define RT_EINVAL       -1   /* bad argument (null pointer, size, unsupported material, ...) */
@@ -245,6 +245,51 @@ int rt_render_ss_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, i
  * reflect_rays and shadow_rays from the summed counters. */
 int rt_render_ss(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int width, int height, int depth,
                  int samples, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
+
+/* ---- adaptive supersampling (ABI 9) -------------------------------------------------------------- */
+/* The S x S samples of rt_render_ss_dev only where the one-sample image has contrast; one sample elsewhere.
+ * Deterministic (not the app's rand()-driven rayTraceScreen chain: rt_render_screen is), and defined entirely by
+ * outputs of the calls above.  For a full width x height frame, S = `samples` in {1, 2, 4, 8} and T = `threshold`
+ * in {-1, .., 255}:
+ *  1. Base frame.  B is the frame rt_render_dev(cam, width, height, depth) writes; q its RGBA8 image,
+ *     floor(clamp(c, 0, 1) * 255 + 0.5) with NaN -> 0.  B(i, j) is sample (0, 0) of pixel (i, j) of the
+ *     supersampled render, bit for bit.
+ *  2. Criterion.  Pixel (i, j) is REFINED iff some in-frame 4-neighbour n in {(i +- 1, j), (i, j +- 1)} and some
+ *     channel c in {r, g, b} has |q_c(i, j) - q_c(n)| > T, in integer arithmetic.  It always reads the base bytes,
+ *     never a refined value.  T = 255 refines nothing; T = -1 refines every pixel that has an in-frame neighbour
+ *     (every pixel of any frame larger than 1 x 1); a 1 x 1 frame refines nothing.
+ *  3. Value.  A refined pixel has exactly the value rt_render_ss_dev(cam, width, height, depth, S) gives it (the
+ *     fixed pairwise tree along a, then along b, times 1 / (S S)); an unrefined pixel has exactly B(i, j).
+ *     rgb64f, rgba32f and rgba8 derive from that value as in rt_render_ss_dev.  raycount2 holds two uint32 per
+ *     pixel: the base sample's counters for an unrefined pixel, the sums over the S x S samples for a refined one.
+ *     NaN rules as in rt_render_ss_dev.
+ *  4. `refined`: a nullable uint8 image, width x height, 1 for a refined pixel and 0 otherwise.
+ *  5. Pins that follow: T = 255 writes the images rt_render_dev writes; T = -1 (frames larger than 1 x 1) writes
+ *     the images rt_render_ss_dev writes.  There is NO shortcut for either: both run the same passes as any other
+ *     T.  S = 1 writes the base images, and `refined` still reports the criterion.
+ * Full frames only: a row band's criterion would need rows its rank does not render, so there is no rt_rows.
+ * rt_render_multi, the packed and asynchronous host paths and the drop-in draw() render one sample per pixel. */
+/* Host only: the bytes of device workspace rt_render_adaptive_dev needs for a width x height frame (the work list
+ * and its counter, and room for the base RGBA8 image).  RT_EINVAL for samples outside {1, 2, 4, 8} or a bad size. */
+int rt_adaptive_workspace_bytes(int width, int height, int samples, size_t* bytes);
+/* Device pointers, each output nullable, width * height pixels; `workspace`: workspace_bytes >=
+ * rt_adaptive_workspace_bytes(...) of device memory, 16-byte aligned, owned by the caller and used by one call at a
+ * time (its first uint32 holds the number of refined pixels once the call's work is done).  Asynchronous on
+ * `stream`, no allocation and no host synchronisation, so it may be captured in a hipGraph like rt_render_dev; the
+ * base pass follows rt_render_dev's view-calibration and capture rules.  Three passes: the base render into the
+ * caller's outputs; a classification pass that writes `refined` and compacts the refined pixels into a work list
+ * (whose order is unspecified and influences no output); a refine pass over the list, S x S lanes per pixel reduced
+ * in the wave, which overwrites the refined pixels in every requested output.
+ * RT_EINVAL (rt_last_error names the argument) for `samples` outside {1, 2, 4, 8}, `threshold` outside -1 .. 255, a
+ * null, misaligned or too small `workspace`, and when the sample-grid camera overflows int32. */
+int rt_render_adaptive_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples,
+                           int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                           uint8_t* refined, void* workspace, size_t workspace_bytes, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_ss (the workspace is the context's).  *n_refined (nullable): the
+ * number of refined pixels n.  *stats from the summed raycount2: primary_rays = (width * height - n) + n * S * S. */
+int rt_render_adaptive(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int width, int height, int depth,
+                       int samples, int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint8_t* refined,
+                       rt_stats* stats, uint64_t* n_refined);
 
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

@@ -20,6 +20,10 @@
 //   rt_render --config c2 --samples 4 --out c2_ss.ppm
 //                                                  S x S regular-grid samples per pixel summed in the kernel
 //                                                  (rt_render_ss; S in 1, 2, 4, 8 — not the app's jittered mode)
+//   rt_render --config c2 --samples 4 --adaptive 8 --out c2_ad.ppm
+//                                                  ... only for the pixels whose one-sample RGBA8 differs from a
+//                                                  4-neighbour by more than 8 in some channel (rt_render_adaptive;
+//                                                  threshold in -1 .. 255), one sample elsewhere
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -48,6 +52,8 @@ struct Options {
     int band = 0;                            // band height (0: auto)
     int repeat = 1;                          // frames rendered (the last one is written)
     int samples = 0;                         // > 0: rt_render_ss with this many samples per axis (plain frames only)
+    bool adaptive = false;                   // --adaptive T: rt_render_adaptive with threshold T (needs --samples)
+    int threshold = 0;
 };
 
 [[noreturn]] void die(const std::string& what, int code) {
@@ -175,10 +181,16 @@ int main(int argc, char** argv) {
         else if (a == "--band") o.band = std::atoi(next().c_str());
         else if (a == "--repeat") o.repeat = std::max(1, std::atoi(next().c_str()));
         else if (a == "--samples") o.samples = std::atoi(next().c_str());
+        else if (a == "--adaptive") { o.adaptive = true; o.threshold = std::atoi(next().c_str()); }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
-                                    "[--gpus N [--band H]] [--samples 1|2|4|8] [--repeat K] [--out file.ppm]\n");
+                                    "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T]] [--repeat K] [--out file.ppm]\n");
                return 2; }
+    }
+    if (o.adaptive && (o.samples == 0 || o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --adaptive needs --samples and applies to plain frames (not --faithful or "
+                             "--gpus)\n");
+        return 2;
     }
     if (o.samples != 0 && (o.faithful >= 0 || o.gpus > 0)) {
         std::fprintf(stderr, "rt_render: --samples applies to plain frames (not --faithful or --gpus)\n");
@@ -288,9 +300,13 @@ int main(int argc, char** argv) {
         return render_multi(o, scene, cam, W, H, depth);
     }
     rt_stats st;
+    uint64_t n_refined = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < o.repeat; ++k) {
-        if (o.samples != 0)
+        if (o.adaptive)
+            check(rt_render_adaptive(ctx, &scene, &cam, W, H, depth, o.samples, o.threshold, nullptr, rgba8.data(),
+                                     nullptr, nullptr, &st, &n_refined), "rt_render_adaptive");
+        else if (o.samples != 0)
             check(rt_render_ss(ctx, &scene, &cam, W, H, depth, o.samples, nullptr, rgba8.data(), nullptr, &st),
                   "rt_render_ss");
         else
@@ -305,7 +321,11 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.samples != 0) std::printf("rt_render: %d x %d samples per pixel, summed in the kernel\n", o.samples, o.samples);
+    if (o.adaptive)
+        std::printf("rt_render: adaptive, threshold %d: %llu of %llu pixels refined with %d x %d samples\n", o.threshold,
+                    (unsigned long long)n_refined, (unsigned long long)W * H, o.samples, o.samples);
+    else if (o.samples != 0)
+        std::printf("rt_render: %d x %d samples per pixel, summed in the kernel\n", o.samples, o.samples);
     if (o.repeat > 1) std::printf("rt_render: %d calls, %.3f ms per call (host to host)\n", o.repeat, per_call_ms);
     rt_ctx_destroy(ctx);
     return 0;

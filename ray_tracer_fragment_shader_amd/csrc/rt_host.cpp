@@ -206,6 +206,17 @@ extern "C" int rt_camera_supersample(const rt_camera* cam, int samples, rt_camer
     return RT_OK;
 }
 
+extern "C" int rt_adaptive_workspace_bytes(int width, int height, int samples, size_t* bytes) {
+    if (!bytes) return rt_fail(RT_EINVAL, "rt_adaptive_workspace_bytes: null pointer");
+    *bytes = 0;
+    if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
+        return rt_fail(RT_EINVAL, "rt_adaptive_workspace_bytes: samples must be 1, 2, 4 or 8");
+    if (width <= 0 || height <= 0 || (long long)width * height > (1LL << 31))
+        return rt_fail(RT_EINVAL, "rt_adaptive_workspace_bytes: bad image size");
+    *bytes = rt_adaptive_layout((size_t)width * (size_t)height).bytes;
+    return RT_OK;
+}
+
 namespace {
 
 int frames_of(const rt_rows* r) { return (r && r->frames > 1) ? r->frames : 1; }

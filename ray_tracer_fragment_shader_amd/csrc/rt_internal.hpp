@@ -23,6 +23,18 @@ int rt_build_dev_scene(const rt_scene* scene, std::vector<unsigned char>* blob);
 // up' = normalize(right x LD), LD = look_at - eye.
 void rt_camera_basis(const rt_camera* cam, double right[3], double upp[3]);
 
+// The workspace of rt_render_adaptive_dev for a W x H frame (rt_adaptive_workspace_bytes): the work-list counter
+// (its own 256 bytes), the base RGBA8 image (used when the caller passes no rgba8) and the list of pixel indices,
+// each 256-byte aligned from a 256-byte aligned base.
+constexpr size_t kAdaptiveAlign = 256;
+struct AdaptiveLayout {
+    size_t base8, list, bytes;                 // offsets of the base image and the list (the counter is at 0); total
+};
+inline AdaptiveLayout rt_adaptive_layout(size_t npx) {
+    const size_t img = (npx * 4 + kAdaptiveAlign - 1) / kAdaptiveAlign * kAdaptiveAlign;
+    return AdaptiveLayout{kAdaptiveAlign, kAdaptiveAlign + img, kAdaptiveAlign + 2 * img};
+}
+
 // Device ordinal of a context (rt_group.cpp).
 int rt_ctx_device(const rt_ctx* ctx);
 

@@ -12,6 +12,8 @@
 //   rt_intersect_kernel       g_scene.intersection on an arbitrary ray list (primitive KATs)
 //   rt_unpack_kernel          multi-GPU: gathered row bands -> image order, packed pixels -> RGBA
 //   rt_raysum_kernel          rt_render's ray statistics (rt_raysum2_kernel: rt_render_ss's two-word counters)
+//   rt_classify_kernel        adaptive supersampling: contrast criterion on the base frame's bytes and compaction of
+//                             the flagged pixels into a work list (the refine kernel: rt_adaptive.hpp)
 //
 // Reference: /root/reference/Hw4/MySdlApplication.cpp (rayTraceScreen :1251-1324, rayTraceRay
 // :1184-1249, intersection code :611-823, :1084-1113).
@@ -35,6 +37,7 @@
 #include "../../include/rt_diag.h"
 #include "rt_internal.hpp"
 #include "rt_render.hpp"
+#include "rt_adaptive.hpp"
 
 using namespace rt;
 
@@ -426,6 +429,87 @@ __global__ __launch_bounds__(kThreads) void rt_raysum2_kernel(const uint32_t* __
     }
 }
 
+// Adaptive supersampling, pass 2 (rt_render_adaptive_dev): the criterion on the W x H base frame and the work list.
+// Pixel k = j W + i is refined iff some in-frame 4-neighbour differs from it by more than T in some colour byte of
+// the base RGBA8 image (T = -1: any in-frame neighbour).  Sets refined[k] (when given) and appends the flagged
+// pixels to `list` behind *count (zeroed on the stream by the caller).  A workgroup of kClassifyThreads work-items
+// takes kClassifyPer runs of kClassifyThreads consecutive pixels; every wave ballots each of its runs and counts the
+// bits, the waves' counts meet in LDS, and ONE atomic add per workgroup reserves its stretch of the list: returning
+// atomics on one word complete at about 88 per us on this chip, and one per wave of 64 pixels (7500 of them in a
+// 1920 x 1080 c2 frame) made this pass 86 us long.  Each flagged lane stores at the workgroup's base + the flagged
+// pixels of earlier waves and runs + the flagged lanes below it.  The list's order depends on the workgroups'
+// arrival; no output does.
+constexpr int kClassifyThreads = 1024, kClassifyPer = 8;
+__global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uint32_t* __restrict__ base8, int W, int H,
+                                                                       int T, uint8_t* __restrict__ refined,
+                                                                       uint32_t* __restrict__ count,
+                                                                       uint32_t* __restrict__ list) {
+    __shared__ uint32_t wave_first[kClassifyThreads / 64];
+    __shared__ uint32_t block_first;
+    const size_t n = (size_t)W * (size_t)H;
+    const size_t k0 = (size_t)blockIdx.x * (kClassifyThreads * kClassifyPer) + threadIdx.x;
+    uint32_t flags = 0;                                     // bit r: this lane's pixel of run r is refined
+    // The loads of all runs first, without branches (a neighbour outside the frame, and a pixel past the frame's end,
+    // is replaced by an in-frame address and masked below): the 5 kClassifyPer loads of a lane are in flight together,
+    // where one dependent round trip per run made the pass latency-bound.
+    uint32_t px[kClassifyPer][5], edge[kClassifyPer];
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        const size_t k = k0 + (size_t)r * kClassifyThreads, kc = k < n ? k : n - 1;   // (n <= 2^31: kc fits 32 bits)
+        const uint32_t j = (uint32_t)kc / (uint32_t)W, i = (uint32_t)kc - j * (uint32_t)W;
+        const uint32_t l = i > 0, rr = i + 1 < (uint32_t)W, d = j > 0, u = j + 1 < (uint32_t)H;
+        edge[r] = k < n ? (l | (rr << 1) | (d << 2) | (u << 3)) : 0u;
+        px[r][0] = base8[kc];
+        px[r][1] = base8[kc - l];
+        px[r][2] = base8[kc + rr];
+        px[r][3] = base8[kc - (d ? (size_t)W : 0)];
+        px[r][4] = base8[kc + (u ? (size_t)W : 0)];
+    }
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        const size_t k = k0 + (size_t)r * kClassifyThreads;
+        bool flag = false;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            int worst = -1;
+            for (int c = 0; c < 24; c += 8) {
+                const int df = (int)((px[r][0] >> c) & 0xffu) - (int)((px[r][nb + 1] >> c) & 0xffu);
+                worst = max(worst, df < 0 ? -df : df);
+            }
+            flag |= ((edge[r] >> nb) & 1u) && worst > T;
+        }
+        if (k < n && refined) refined[k] = flag ? 1 : 0;
+        flags |= (flag ? 1u : 0u) << r;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t ballot[kClassifyPer];                          // every lane of the workgroup is here
+    uint32_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        ballot[r] = __ballot((flags >> r) & 1u);
+        mine += (uint32_t)__popcll(ballot[r]);
+    }
+    if (lane == 0) wave_first[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kClassifyThreads / 64; ++w) {
+            const uint32_t c = wave_first[w];
+            wave_first[w] = sum;
+            sum += c;
+        }
+        block_first = sum ? atomicAdd(count, sum) : 0u;
+    }
+    __syncthreads();
+    uint32_t at = block_first + wave_first[wave];
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        if ((flags >> r) & 1u)
+            list[at + (uint32_t)__popcll(ballot[r] & ((1ull << lane) - 1ull))] = (uint32_t)(k0 + (size_t)r * kClassifyThreads);
+        at += (uint32_t)__popcll(ballot[r]);
+    }
+}
+
 // Diagnostics (include/rt_diag.h): the exact-arithmetic fast paths of rt_device.hpp beside the compiler's
 // IEEE sequences, on caller-supplied operands.  op 0: per vector v (3 doubles) -> 9 doubles
 // [divs(v, len(v)), len(v), unit(v), |v| from unit(), len_fast(v)]; op 1: per pair (a, b) -> 2 doubles
@@ -603,8 +687,9 @@ struct rt_ctx {
     int last_copy_mode = -1;                            // the mode the last packed frame took (rt_diag_copy_path)
     uint64_t ticket = 0;                       // rt_render_packed_async frames queued so far
     // rt_render's device buffers (grow-only, reused across calls): rgba32f, rgba8, rgb64f, raycount, sums,
-    // packed slot 0, packed slot 1
-    static constexpr int kBufs = 5 + kSlots;
+    // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace
+    static constexpr int kBufRefined = 5 + kSlots, kBufAdaptive = 6 + kSlots;
+    static constexpr int kBufs = 7 + kSlots;
     void* d_out[kBufs] = {};
     size_t out_cap[kBufs] = {};
 };
@@ -1374,6 +1459,137 @@ extern "C" int rt_render_ss(rt_ctx* c, const rt_scene* scene, const rt_camera* c
         if (rc) return rc;
         // every sample is a primary ray: the summed segment counters hold S * S of them per pixel
         const uint64_t prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples;
+        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+        stats->primary_rays = prim;
+    }
+    return RT_OK;
+}
+
+// ---- adaptive supersampling (include/rt_api.h, ABI 9) -------------------------------------------------------------
+// Workgroups of the refine launch: a fixed grid of one-wave workgroups (the list's length is only known on the
+// device) that covers the device's wave slots a few times over; the grid-stride loop takes the rest.
+constexpr unsigned kRefineGrid = 8192;
+
+// Three passes on `stream`: the one-sample base render (rt_render_ss_dev with S = 1: rt_render_dev's instances, or
+// the two-word-counter ones when counters are asked for) straight into the caller's outputs, rt_classify_kernel on
+// its RGBA8 bytes, rt_refine_kernel over the work list.  No shortcut for any threshold.
+extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                      int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                      uint32_t* raycount2, uint8_t* refined, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    const int s = ss_log2_of(samples);
+    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: samples must be 1, 2, 4 or 8");
+    if (threshold < -1 || threshold > 255)
+        return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: threshold must lie in -1 .. 255");
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) || (long long)W * samples > INT32_MAX ||
+        (long long)H * samples > INT32_MAX)
+        return rt_fail(RT_EINVAL, "render: bad image size");
+    const size_t npx = (size_t)W * (size_t)H;
+    const AdaptiveLayout lay = rt_adaptive_layout(npx);
+    if (!workspace || workspace_bytes < lay.bytes || (uintptr_t)workspace % 16 != 0)
+        return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: null, misaligned or too small workspace "
+                                  "(rt_adaptive_workspace_bytes)");
+    rt_camera cam_s;
+    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
+    if (rc) return rc;
+    RenderParams P;                                         // the sample grid's: the refine kernel's ray set-up
+    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, &P);
+    if (rc) return rc;
+    P.ss_log2 = s;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+    uint32_t* count = reinterpret_cast<uint32_t*>(ws);
+    uint32_t* list = reinterpret_cast<uint32_t*>(ws + lay.list);
+    uint8_t* base8 = rgba8 ? rgba8 : ws + lay.base8;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+    rc = rt_render_ss_dev(c, cam, W, H, depth, 1, nullptr, rgba32f, base8, rgb64f, raycount2, st);
+    if (rc) return rc;
+    constexpr size_t kClassifyBlock = (size_t)kClassifyThreads * kClassifyPer;
+    hipLaunchKernelGGL(rt_classify_kernel, dim3((unsigned)((npx + kClassifyBlock - 1) / kClassifyBlock)),
+                       dim3(kClassifyThreads), 0, st,
+                       reinterpret_cast<const uint32_t*>(base8), W, H, threshold, refined, count, list);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_classify_kernel: ") + hipGetErrorString(e));
+    // S = 1: a refined pixel's only sample is the base sample itself, already in place
+    if (s == 0 || (!rgba32f && !rgba8 && !rgb64f && !raycount2)) return RT_OK;
+    RefineLaunch L;
+    L.variant = c->tree ? 2 : c->transparent ? 1 : 0;
+    const size_t per_wave = (size_t)64 >> (2 * s);
+    L.grid = (unsigned)std::min<size_t>((npx + per_wave - 1) / per_wave, kRefineGrid);
+    L.stream = st;
+    L.scene = c->d_scene;
+    L.P = P;
+    L.out_w = W;
+    L.count = count;
+    L.list = list;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    switch (depth) {
+        case 0: e = launch_refine<0>(L); break;
+        case 1: e = launch_refine<1>(L); break;
+        case 2: e = launch_refine<2>(L); break;
+        case 3: e = launch_refine<3>(L); break;
+        case 4: e = launch_refine<4>(L); break;
+        case 5: e = launch_refine<5>(L); break;
+        case 6: e = launch_refine<6>(L); break;
+        default: e = launch_refine<7>(L); break;
+    }
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_refine_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// rt_render for an adaptively supersampled frame: rt_render_adaptive_dev into the context's device buffers (its
+// workspace among them), then the copies back.
+extern "C" int rt_render_adaptive(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                                  int samples, int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                  uint8_t* refined, rt_stats* stats, uint64_t* n_refined) {
+    if (!c) return rt_fail(RT_EINVAL, "rt_render_adaptive: null context");
+    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_adaptive: samples must be 1, 2, 4 or 8");
+    if (threshold < -1 || threshold > 255)
+        return rt_fail(RT_EINVAL, "rt_render_adaptive: threshold must lie in -1 .. 255");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31)) return rt_fail(RT_EINVAL, "rt_render_adaptive: bad image size");
+    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
+    if (rc) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    const size_t npx = (size_t)W * H;
+    const AdaptiveLayout lay = rt_adaptive_layout(npx);
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
+    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
+    for (int k = 0; k < 5; ++k)
+        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
+    void *d_ref = nullptr, *d_ws = nullptr;
+    if (refined && (rc = ctx_buffer(c, rt_ctx::kBufRefined, npx, &d_ref)) != RT_OK) return rc;
+    if ((rc = ctx_buffer(c, rt_ctx::kBufAdaptive, lay.bytes, &d_ws)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->ev0, c->rs));
+    rc = rt_render_adaptive_dev(c, cam, W, H, depth, samples, threshold, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                                (uint32_t*)d[3], (uint8_t*)d_ref, d_ws, lay.bytes, c->rs);
+    if (rc) return rc;
+    RT_HIP(hipEventRecord(c->ev1, c->rs));
+    if (stats) {
+        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
+        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
+                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
+        RT_HIP(hipGetLastError());
+    }
+    void* host[3] = {rgba32f, rgba8, rgb64f};
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
+    if (refined && (rc = copy_to_host(c, refined, d_ref, npx, c->rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->rs));
+    uint32_t n = 0;                                         // the work list's length: the refined pixels
+    RT_HIP(hipMemcpy(&n, d_ws, sizeof(n), hipMemcpyDeviceToHost));
+    if (n_refined) *n_refined = n;
+    if (stats) {
+        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
+        if (rc) return rc;
+        // every sample is a primary ray: one per unrefined pixel, S * S per refined one
+        const uint64_t prim = (uint64_t)(npx - n) + (uint64_t)n * (uint64_t)samples * (uint64_t)samples;
         stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
         stats->primary_rays = prim;
     }
