@@ -27,7 +27,7 @@ RT_MAX_DEPTH = 7
 RT_RAND_GLIBC, RT_RAND_MSVC = 0, 1
 RT_MESH_TETRAHEDRON = 1
 RT_MESH_CUBE = 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 RT_TRANSPORT_AUTO, RT_TRANSPORT_RCCL, RT_TRANSPORT_COPY = -1, 0, 1
 RT_OUT_RGBA32F, RT_OUT_RGBA8 = 1, 2
 RT_PIXEL_RGBA32F, RT_PIXEL_GRAY32F, RT_PIXEL_RGBA8, RT_PIXEL_RGB8, RT_PIXEL_GRAY8 = 0, 1, 2, 3, 4
@@ -181,6 +181,11 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "rt_render_adaptive": (c_int, [c_void_p, _P(rt_scene), _P(rt_camera), c_int, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, _P(rt_stats), _P(c_uint64)]),
+    "rt_camera_focus": (c_int, [_P(rt_camera), c_double, _P(rt_camera)]),
+    "rt_render_dof_dev": (c_int, [c_void_p, _P(rt_camera), c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
+    "rt_render_dof": (c_int, [c_void_p, _P(rt_scene), _P(rt_camera), c_int, c_int, c_int, c_int, c_double, c_void_p,
+                              c_void_p, c_void_p, _P(rt_stats)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

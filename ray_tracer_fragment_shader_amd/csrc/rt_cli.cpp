@@ -24,6 +24,10 @@
 //                                                  ... only for the pixels whose one-sample RGBA8 differs from a
 //                                                  4-neighbour by more than 8 in some channel (rt_render_adaptive;
 //                                                  threshold in -1 .. 255), one sample elsewhere
+//   rt_render --config c2 --samples 4 --aperture 8 [--focus 0.8] --out c2_dof.ppm
+//                                                  depth of field: the S x S samples start on a square lens of
+//                                                  half-width 8 around the eye (rt_render_dof); --focus moves the
+//                                                  focal plane to RATIO times the look-at distance (rt_camera_focus)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -54,7 +58,22 @@ struct Options {
     int samples = 0;                         // > 0: rt_render_ss with this many samples per axis (plain frames only)
     bool adaptive = false;                   // --adaptive T: rt_render_adaptive with threshold T (needs --samples)
     int threshold = 0;
+    bool dof = false;                        // --aperture A: rt_render_dof with lens half-width A (needs --samples)
+    double aperture = 0.0;
+    bool focus = false;                      // --focus RATIO: rt_camera_focus before a --aperture render
+    double focus_ratio = 1.0;
 };
+
+// A finite number that fills the whole argument, or a usage error.
+double number_arg(const std::string& flag, const std::string& v) {
+    char* end = nullptr;
+    const double x = std::strtod(v.c_str(), &end);
+    if (v.empty() || *end != 0 || !std::isfinite(x)) {
+        std::fprintf(stderr, "rt_render: %s needs a number, got '%s'\n", flag.c_str(), v.c_str());
+        std::exit(2);
+    }
+    return x;
+}
 
 [[noreturn]] void die(const std::string& what, int code) {
     std::fprintf(stderr, "rt_render: %s failed (%d): %s\n", what.c_str(), code, rt_last_error());
@@ -182,14 +201,30 @@ int main(int argc, char** argv) {
         else if (a == "--repeat") o.repeat = std::max(1, std::atoi(next().c_str()));
         else if (a == "--samples") o.samples = std::atoi(next().c_str());
         else if (a == "--adaptive") { o.adaptive = true; o.threshold = std::atoi(next().c_str()); }
+        else if (a == "--aperture") { o.dof = true; o.aperture = number_arg(a, next()); }
+        else if (a == "--focus") { o.focus = true; o.focus_ratio = number_arg(a, next()); }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
-                                    "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T]] [--repeat K] [--out file.ppm]\n");
+                                    "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | --aperture A [--focus RATIO]]] "
+                                    "[--repeat K] [--out file.ppm]\n");
                return 2; }
     }
     if (o.adaptive && (o.samples == 0 || o.faithful >= 0 || o.gpus > 0)) {
         std::fprintf(stderr, "rt_render: --adaptive needs --samples and applies to plain frames (not --faithful or "
                              "--gpus)\n");
+        return 2;
+    }
+    if (o.dof && (o.samples == 0 || o.adaptive || o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --aperture needs --samples, excludes --adaptive and applies to plain frames "
+                             "(not --faithful or --gpus)\n");
+        return 2;
+    }
+    if (o.dof && o.aperture < 0.0) {
+        std::fprintf(stderr, "rt_render: --aperture must be >= 0\n");
+        return 2;
+    }
+    if (o.focus && (!o.dof || !(o.focus_ratio > 0.0))) {
+        std::fprintf(stderr, "rt_render: --focus needs --aperture and a ratio > 0\n");
         return 2;
     }
     if (o.samples != 0 && (o.faithful >= 0 || o.gpus > 0)) {
@@ -278,6 +313,7 @@ int main(int argc, char** argv) {
 
     rt_camera cam;
     check(rt_camera_init_reference(&cam, W, H, pitch), "rt_camera_init_reference");
+    if (o.focus) check(rt_camera_focus(&cam, o.focus_ratio, &cam), "rt_camera_focus");
     rt_ctx* ctx = nullptr;
     check(rt_ctx_create(o.device, &ctx), "rt_ctx_create");
     std::vector<uint8_t> rgba8((size_t)W * H * 4);
@@ -303,7 +339,10 @@ int main(int argc, char** argv) {
     uint64_t n_refined = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < o.repeat; ++k) {
-        if (o.adaptive)
+        if (o.dof)
+            check(rt_render_dof(ctx, &scene, &cam, W, H, depth, o.samples, o.aperture, nullptr, rgba8.data(), nullptr,
+                                &st), "rt_render_dof");
+        else if (o.adaptive)
             check(rt_render_adaptive(ctx, &scene, &cam, W, H, depth, o.samples, o.threshold, nullptr, rgba8.data(),
                                      nullptr, nullptr, &st, &n_refined), "rt_render_adaptive");
         else if (o.samples != 0)
@@ -321,7 +360,10 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.adaptive)
+    if (o.dof)
+        std::printf("rt_render: depth of field, lens half-width %g, focus ratio %g: %d x %d lens samples per pixel\n",
+                    o.aperture, o.focus_ratio, o.samples, o.samples);
+    else if (o.adaptive)
         std::printf("rt_render: adaptive, threshold %d: %llu of %llu pixels refined with %d x %d samples\n", o.threshold,
                     (unsigned long long)n_refined, (unsigned long long)W * H, o.samples, o.samples);
     else if (o.samples != 0)

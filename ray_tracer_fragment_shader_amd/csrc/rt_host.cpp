@@ -206,6 +206,22 @@ extern "C" int rt_camera_supersample(const rt_camera* cam, int samples, rt_camer
     return RT_OK;
 }
 
+// The camera of rt_render_dof_dev with its focal plane (the plane through look_at spanned by right and up') moved to
+// `ratio` times its distance from the eye: the pitch scales with it, so every pixel's primary ray keeps its
+// direction (up to rounding) and the pinhole view is the same.
+extern "C" int rt_camera_focus(const rt_camera* cam, double ratio, rt_camera* out) {
+    if (!cam || !out) return rt_fail(RT_EINVAL, "rt_camera_focus: null pointer");
+    if (!(ratio > 0.0) || !std::isfinite(ratio))
+        return rt_fail(RT_EINVAL, "rt_camera_focus: ratio must be finite and > 0");
+    rt_camera c = *cam;                                                         // (out may alias cam)
+    if (ratio != 1.0) {                                                         // 1.0: unchanged bit for bit
+        for (int q = 0; q < 3; ++q) c.look_at[q] = cam->eye[q] + ratio * (cam->look_at[q] - cam->eye[q]);
+        c.pitch = ratio * cam->pitch;
+    }
+    *out = c;
+    return RT_OK;
+}
+
 extern "C" int rt_adaptive_workspace_bytes(int width, int height, int samples, size_t* bytes) {
     if (!bytes) return rt_fail(RT_EINVAL, "rt_adaptive_workspace_bytes: null pointer");
     *bytes = 0;

@@ -38,6 +38,7 @@
 #include "rt_internal.hpp"
 #include "rt_render.hpp"
 #include "rt_adaptive.hpp"
+#include "rt_dof.hpp"
 
 using namespace rt;
 
@@ -1590,6 +1591,100 @@ extern "C" int rt_render_adaptive(rt_ctx* c, const rt_scene* scene, const rt_cam
         if (rc) return rc;
         // every sample is a primary ray: one per unrefined pixel, S * S per refined one
         const uint64_t prim = (uint64_t)(npx - n) + (uint64_t)n * (uint64_t)samples * (uint64_t)samples;
+        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+        stats->primary_rays = prim;
+    }
+    return RT_OK;
+}
+
+// ---- depth of field (include/rt_api.h, ABI 10) --------------------------------------------------------------------
+// One launch of rt_dof_kernel (rt_dof.hpp) on `stream`: S x S lens samples per pixel through the generic trace path.
+// Nothing per view: no rt_prepare_kernel, no calibration, no dispatch table, and no field of the context is written,
+// so the context's cone and level masks and its tile order stay what the last rt_render_dev left.  No shortcut for
+// aperture 0 or samples 1.
+extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                 double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                 uint32_t* raycount2, void* stream) {
+    const int s = ss_log2_of(samples);
+    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_dof_dev: samples must be 1, 2, 4 or 8");
+    if (!(aperture >= 0.0) || !std::isfinite(aperture))
+        return rt_fail(RT_EINVAL, "rt_render_dof_dev: aperture must be finite and >= 0");
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) || (long long)W * samples > INT32_MAX ||
+        (long long)H * samples > INT32_MAX)
+        return rt_fail(RT_EINVAL, "rt_render_dof_dev: bad image size (width, height)");
+    rt_camera cam_s;
+    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
+    if (rc) return rc;
+    DofLaunch L;                                            // P: the sample grid's, the kernel's ray set-up
+    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, &L.P);   // (at most 2^31 samples)
+    if (rc) return rc;
+    L.P.ss_log2 = s;
+    L.variant = c->tree ? 2 : c->transparent ? 1 : 0;
+    L.stream = (hipStream_t)stream;
+    L.scene = c->d_scene;
+    L.aperture = aperture;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    hipError_t e;
+    switch (depth) {
+        case 0: e = launch_dof<0>(L); break;
+        case 1: e = launch_dof<1>(L); break;
+        case 2: e = launch_dof<2>(L); break;
+        case 3: e = launch_dof<3>(L); break;
+        case 4: e = launch_dof<4>(L); break;
+        case 5: e = launch_dof<5>(L); break;
+        case 6: e = launch_dof<6>(L); break;
+        default: e = launch_dof<7>(L); break;
+    }
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_dof_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// rt_render for a depth-of-field frame (rt_render_dof_dev into the context's device buffers, then the copies back).
+extern "C" int rt_render_dof(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                             int samples, double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                             rt_stats* stats) {
+    if (!c) return rt_fail(RT_EINVAL, "rt_render_dof: null context");
+    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_dof: samples must be 1, 2, 4 or 8");
+    if (!(aperture >= 0.0) || !std::isfinite(aperture))
+        return rt_fail(RT_EINVAL, "rt_render_dof: aperture must be finite and >= 0");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31))
+        return rt_fail(RT_EINVAL, "rt_render_dof: bad image size (width, height)");
+    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
+    if (rc) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    const size_t npx = (size_t)W * H;
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
+    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
+    for (int k = 0; k < 5; ++k)
+        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->ev0, c->rs));
+    rc = rt_render_dof_dev(c, cam, W, H, depth, samples, aperture, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                           (uint32_t*)d[3], c->rs);
+    if (rc) return rc;
+    RT_HIP(hipEventRecord(c->ev1, c->rs));
+    if (stats) {
+        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
+        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
+                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
+        RT_HIP(hipGetLastError());
+    }
+    void* host[3] = {rgba32f, rgba8, rgb64f};
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->rs));
+    if (stats) {
+        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
+        if (rc) return rc;
+        // every lens sample is a primary ray: the summed segment counters hold S * S of them per pixel
+        const uint64_t prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples;
         stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
         stats->primary_rays = prim;
     }

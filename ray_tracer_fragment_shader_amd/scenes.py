@@ -237,6 +237,14 @@ def make_camera(width: int, height: int, pitch: float) -> abi.rt_camera:
     return cam
 
 
+def focus_camera(cam: abi.rt_camera, ratio: float) -> abi.rt_camera:
+    """rt_camera_focus: `cam` with its focal plane (the plane through look_at, for Tracer.render_dof) at `ratio`
+    times its distance from the eye and the pitch scaled with it, so the view is the same."""
+    out = abi.rt_camera()
+    abi.check(abi.lib().rt_camera_focus(ctypes.byref(cam), float(ratio), ctypes.byref(out)), "rt_camera_focus")
+    return out
+
+
 # BASELINE.json configs (SURVEY.md §8 shorthand)
 CONFIGS = {
     "c1": Config("c1", 640, 480, 3, 1, 0),

@@ -138,6 +138,25 @@ class Tracer:
         bufs = self.alloc_adaptive(width, height, samples, rgba32f, rgba8, rgb64f, raycount)
         return self.render_adaptive_into(cam, width, height, depth, samples, threshold, bufs, stream)
 
+    # ------------------------------------------------------------------------------------- depth of field
+    def render_dof_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int,
+                        aperture: float, bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_dof_dev into alloc_ss() buffers (full frames): samples x samples rays per pixel from a square
+        lens of half-width `aperture` around the eye, focused on the plane through cam.look_at
+        (scenes.focus_camera moves it); asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_dof_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
+                                              float(aperture), _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
+                                              _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
+                                              ctypes.c_void_p(st.cuda_stream)), "rt_render_dof_dev")
+        return bufs
+
+    def render_dof(self, cam, width, height, depth, samples, aperture, rgba32f=True, rgba8=False, rgb64f=False,
+                   raycount=False, stream=None):
+        """-> the buffers of alloc_ss() (the keys of render_ss())."""
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_dof_into(cam, width, height, depth, samples, aperture, bufs, stream)
+
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):
         """rt_render_dev_packed: the float image in float_format (RT_PIXEL_RGBA32F / GRAY32F) and the byte
