@@ -13,7 +13,7 @@
 //   rt_unpack_kernel          multi-GPU: gathered row bands -> image order, packed pixels -> RGBA
 //   rt_raysum_kernel          rt_render's ray statistics (rt_raysum2_kernel: rt_render_ss's two-word counters)
 //   rt_classify_kernel        adaptive supersampling: contrast criterion on the base frame's bytes and compaction of
-//                             the flagged pixels into a work list (the refine kernel: rt_adaptive.hpp)
+//                             the flagged pixels into a work list (the refine kernel: rt_sampled.hpp)
 //
 // Reference: /root/reference/Hw4/MySdlApplication.cpp (rayTraceScreen :1251-1324, rayTraceRay
 // :1184-1249, intersection code :611-823, :1084-1113).
@@ -37,8 +37,7 @@
 #include "../../include/rt_diag.h"
 #include "rt_internal.hpp"
 #include "rt_render.hpp"
-#include "rt_adaptive.hpp"
-#include "rt_dof.hpp"
+#include "rt_sampled.hpp"
 
 using namespace rt;
 
@@ -1181,16 +1180,7 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
         else L.variant = cull ? kVarCullSS : kVarFastSS;
         if (!c->tree && !c->transparent) L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
     }
-    switch (depth) {
-        case 0: e = launch_render<0>(L); break;
-        case 1: e = launch_render<1>(L); break;
-        case 2: e = launch_render<2>(L); break;
-        case 3: e = launch_render<3>(L); break;
-        case 4: e = launch_render<4>(L); break;
-        case 5: e = launch_render<5>(L); break;
-        case 6: e = launch_render<6>(L); break;
-        default: e = launch_render<7>(L); break;
-    }
+    e = with_depth(depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
     if (lm_calib && !cull_kernel) {
         // a fast kernel's scene: the level masks of the view from a culling kernel that stores nothing else (identity
@@ -1208,16 +1198,7 @@ static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int de
         M.orc = nullptr;
         M.variant = mw5 ? kVarCull : kVarCullAnyW;
         M.lds = slot_bytes(depth, false, RT_WG_FAST, true);
-        switch (depth) {
-            case 0: e = launch_render<0>(M); break;
-            case 1: e = launch_render<1>(M); break;
-            case 2: e = launch_render<2>(M); break;
-            case 3: e = launch_render<3>(M); break;
-            case 4: e = launch_render<4>(M); break;
-            case 5: e = launch_render<5>(M); break;
-            case 6: e = launch_render<6>(M); break;
-            default: e = launch_render<7>(M); break;
-        }
+        e = with_depth(depth, [&](auto B) { return launch_render<decltype(B)::value>(M); });
         if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("level-mask launch: ") + hipGetErrorString(e));
     }
     if (calibrate) {
@@ -1274,19 +1255,37 @@ static int ss_log2_of(int samples) {
     return samples == 1 ? 0 : samples == 2 ? 1 : samples == 4 ? 2 : samples == 8 ? 3 : -1;
 }
 
+// The front of the sampled _dev entry points: the checks on samples (*s: its log2), context, camera and frame size;
+// then, with P given (the list-free kernels of rt_sampled.hpp, which index a whole frame of at most 2^31 pixels), the
+// sample-grid camera and the sample grid's RenderParams with ss_log2 set.
+static int sample_grid_front(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int* s,
+                             RenderParams* P) {
+    *s = ss_log2_of(samples);
+    if (*s < 0) return rt_fail(RT_EINVAL, "render: samples must be 1, 2, 4 or 8");
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (P && (long long)W * H > (1LL << 31)) || (long long)W * samples > INT32_MAX ||
+        (long long)H * samples > INT32_MAX)
+        return rt_fail(RT_EINVAL, "render: bad image size (width, height)");
+    if (!P) return RT_OK;
+    rt_camera cam_s;
+    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
+    if (rc) return rc;
+    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, P);   // (at most 2^31 samples)
+    if (rc) return rc;
+    P->ss_log2 = *s;
+    return RT_OK;
+}
+
 // rt_render_ss_dev: the render of the sample grid (camera rt_camera_supersample, S W x S H, row bands S times as
 // high, so every S-row block of samples stays inside one band) through the supersampled kernel instances.
 extern "C" int rt_render_ss_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
                                 const rt_rows* rows, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                                 uint32_t* raycount2, void* stream) {
-    const int s = ss_log2_of(samples);
-    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_ss_dev: samples must be 1, 2, 4 or 8");
-    if (!c) return rt_fail(RT_EINVAL, "render: null context");
-    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
-    if (W <= 0 || H <= 0 || (long long)W * samples > INT32_MAX || (long long)H * samples > INT32_MAX)
-        return rt_fail(RT_EINVAL, "render: bad image size");
+    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, nullptr);
+    if (rc) return rc;
     int nl = 0;
-    int rc = rt_local_rows(H, rows, &nl);               // the caller's row plan, checked as given
+    rc = rt_local_rows(H, rows, &nl);                   // the caller's row plan, checked as given
     if (rc) return rc;
     if (rows && rows->frames > 1 && samples > 1)
         return rt_fail(RT_EINVAL, "rt_render_ss_dev: frames > 1 is not supported with samples > 1");
@@ -1387,11 +1386,59 @@ static int copy_to_host(rt_ctx* c, void* host, const void* dev, size_t bytes, hi
     return RT_OK;
 }
 
-static int queue_raysum(rt_ctx* c, size_t npx, uint32_t* d_rc, unsigned long long* d_sums) {
+// Sum a render's per-pixel ray counters into d_sums[0..1]: `words` = 1 for the packed 16 + 16-bit word of the plain
+// renders, 2 for the two words per pixel of the sampled ones.
+static int queue_raysum(rt_ctx* c, size_t npx, int words, uint32_t* d_rc, unsigned long long* d_sums) {
     RT_HIP(hipMemsetAsync(d_sums, 0, 2 * sizeof(unsigned long long), c->rs));
-    hipLaunchKernelGGL(rt_raysum_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
-                       dim3(kThreads), 0, c->rs, (const uint32_t*)d_rc, npx, d_sums);
+    hipLaunchKernelGGL(words == 2 ? rt_raysum2_kernel : rt_raysum_kernel,
+                       dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)), dim3(kThreads), 0, c->rs,
+                       (const uint32_t*)d_rc, npx, d_sums);
     RT_HIP(hipGetLastError());
+    return RT_OK;
+}
+
+// One more context buffer of a host render (rt_render_adaptive's two): `bytes` of buffer k (0: not wanted), copied back
+// to `host` when that is given.  dev: filled in by host_render.
+struct ExtraBuf {
+    int k;
+    size_t bytes;
+    void* host;
+    void* dev;
+};
+
+// The host side of rt_render and its sampled siblings, after their argument checks: the context's device buffers for
+// the outputs asked for (npx pixels, rc_words counter words each) and for `extra`; the render queued by render(d)
+// (d[0..3]: RGBA32F, RGBA8, RGB64F, counters) between the timing events; the ray sums; asynchronous copies back on the
+// render stream (rt_host_alloc memory: a copy kernel; other memory: hipMemcpyAsync) and one synchronisation of that
+// stream (not of the device: other streams' work is not waited for).  Then primary(&n) gives the primary rays traced
+// (every sample is one: the summed segment counters hold them all), from which the statistics are written.
+template <class Render, class Primary>
+static int host_render(rt_ctx* c, size_t npx, int rc_words, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                       rt_stats* stats, ExtraBuf* extra, int n_extra, Render&& render, Primary&& primary) {
+    RT_HIP(hipSetDevice(c->device));
+    int rc;
+    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 4 * rc_words, 2 * sizeof(unsigned long long)};
+    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
+    for (int k = 0; k < 5; ++k)
+        if (want[k] && npx > 0 && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
+    for (int k = 0; k < n_extra; ++k)
+        if (extra[k].bytes && (rc = ctx_buffer(c, extra[k].k, extra[k].bytes, &extra[k].dev)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->ev0, c->rs));
+    if ((rc = render(d)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->ev1, c->rs));
+    if (stats && npx > 0 && (rc = queue_raysum(c, npx, rc_words, (uint32_t*)d[3], (unsigned long long*)d[4]))) return rc;
+    void* host[3] = {rgba32f, rgba8, rgb64f};
+    for (int k = 0; k < 3; ++k)
+        if (host[k] && npx && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
+    for (int k = 0; k < n_extra; ++k)
+        if (extra[k].host && (rc = copy_to_host(c, extra[k].host, extra[k].dev, extra[k].bytes, c->rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->rs));
+    uint64_t prim = 0;
+    if ((rc = primary(&prim)) != RT_OK || !stats) return rc;
+    if ((rc = read_stats(c, npx, (const unsigned long long*)d[4], stats)) != RT_OK) return rc;
+    stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+    stats->primary_rays = prim;
     return RT_OK;
 }
 
@@ -1403,67 +1450,38 @@ extern "C" int rt_render(rt_ctx* c, const rt_scene* scene, const rt_camera* cam,
     RenderParams P;
     rc = render_params(c, cam, W, H, depth, rows, &P);
     if (rc) return rc;
-    RT_HIP(hipSetDevice(c->device));
     const size_t npx = (size_t)P.local_rows * W;
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 4, 2 * sizeof(unsigned long long)};
-    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
-    for (int k = 0; k < 5; ++k)
-        if (want[k] && npx > 0 && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
-    RT_HIP(hipEventRecord(c->ev0, c->rs));
-    rc = rt_render_dev(c, cam, W, H, depth, rows, (float*)d[0], (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3], c->rs);
-    if (rc) return rc;
-    RT_HIP(hipEventRecord(c->ev1, c->rs));
-    if (stats && npx > 0 && (rc = queue_raysum(c, npx, (uint32_t*)d[3], (unsigned long long*)d[4]))) return rc;
-    // asynchronous copies on the render stream (rt_host_alloc memory: a copy kernel; other memory: hipMemcpyAsync),
-    // one synchronisation of that stream (not of the device: other streams' work is not waited for)
-    void* host[3] = {rgba32f, rgba8, rgb64f};
-    for (int k = 0; k < 3; ++k)
-        if (host[k] && npx && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
-    RT_HIP(hipStreamSynchronize(c->rs));
-    if (stats) return read_stats(c, npx, (const unsigned long long*)d[4], stats);
+    return host_render(
+        c, npx, 1, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return rt_render_dev(c, cam, W, H, depth, rows, (float*)d[0], (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3],
+                                 c->rs);
+        },
+        [&](uint64_t* prim) { *prim = npx; return RT_OK; });
+}
+
+// The checks the host entry points of the sampled renders share (the _dev calls check the rest).
+static int sampled_host_checks(const char* who, const rt_ctx* c, int W, int H, int samples) {
+    if (!c) return rt_fail(RT_EINVAL, std::string(who) + ": null context");
+    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, std::string(who) + ": samples must be 1, 2, 4 or 8");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": bad image size (width, height)");
     return RT_OK;
 }
 
 // rt_render for a supersampled frame (rt_render_ss_dev into the context's device buffers, then the copies back).
 extern "C" int rt_render_ss(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
                             int samples, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
-    if (!c) return rt_fail(RT_EINVAL, "rt_render_ss: null context");
-    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_ss: samples must be 1, 2, 4 or 8");
-    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31)) return rt_fail(RT_EINVAL, "rt_render_ss: bad image size");
-    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
-    if (rc) return rc;
-    RT_HIP(hipSetDevice(c->device));
+    int rc = sampled_host_checks("rt_render_ss", c, W, H, samples);
+    if (rc || (rc = rt_set_scene(c, scene))) return rc;     // no device work when the scene is unchanged
     const size_t npx = (size_t)W * H;
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
-    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
-    for (int k = 0; k < 5; ++k)
-        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
-    RT_HIP(hipEventRecord(c->ev0, c->rs));
-    rc = rt_render_ss_dev(c, cam, W, H, depth, samples, nullptr, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
-                          (uint32_t*)d[3], c->rs);
-    if (rc) return rc;
-    RT_HIP(hipEventRecord(c->ev1, c->rs));
-    if (stats) {
-        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
-        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
-                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
-        RT_HIP(hipGetLastError());
-    }
-    void* host[3] = {rgba32f, rgba8, rgb64f};
-    for (int k = 0; k < 3; ++k)
-        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
-    RT_HIP(hipStreamSynchronize(c->rs));
-    if (stats) {
-        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
-        if (rc) return rc;
-        // every sample is a primary ray: the summed segment counters hold S * S of them per pixel
-        const uint64_t prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples;
-        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
-        stats->primary_rays = prim;
-    }
-    return RT_OK;
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return rt_render_ss_dev(c, cam, W, H, depth, samples, nullptr, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                                    (uint32_t*)d[3], c->rs);
+        },
+        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }
 
 // ---- adaptive supersampling (include/rt_api.h, ABI 9) -------------------------------------------------------------
@@ -1478,27 +1496,16 @@ extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, in
                                       int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                                       uint32_t* raycount2, uint8_t* refined, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-    const int s = ss_log2_of(samples);
-    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: samples must be 1, 2, 4 or 8");
     if (threshold < -1 || threshold > 255)
         return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: threshold must lie in -1 .. 255");
-    if (!c) return rt_fail(RT_EINVAL, "render: null context");
-    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
-    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) || (long long)W * samples > INT32_MAX ||
-        (long long)H * samples > INT32_MAX)
-        return rt_fail(RT_EINVAL, "render: bad image size");
+    SampledLaunch L{};                                      // P: the sample grid's, the refine kernel's ray set-up
+    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
     const size_t npx = (size_t)W * (size_t)H;
     const AdaptiveLayout lay = rt_adaptive_layout(npx);
     if (!workspace || workspace_bytes < lay.bytes || (uintptr_t)workspace % 16 != 0)
         return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: null, misaligned or too small workspace "
                                   "(rt_adaptive_workspace_bytes)");
-    rt_camera cam_s;
-    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
-    if (rc) return rc;
-    RenderParams P;                                         // the sample grid's: the refine kernel's ray set-up
-    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, &P);
-    if (rc) return rc;
-    P.ss_log2 = s;
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
     uint32_t* count = reinterpret_cast<uint32_t*>(ws);
@@ -1516,13 +1523,11 @@ extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, in
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_classify_kernel: ") + hipGetErrorString(e));
     // S = 1: a refined pixel's only sample is the base sample itself, already in place
     if (s == 0 || (!rgba32f && !rgba8 && !rgb64f && !raycount2)) return RT_OK;
-    RefineLaunch L;
-    L.variant = c->tree ? 2 : c->transparent ? 1 : 0;
+    L.variant = trace_variant(c->tree, c->transparent);
     const size_t per_wave = (size_t)64 >> (2 * s);
     L.grid = (unsigned)std::min<size_t>((npx + per_wave - 1) / per_wave, kRefineGrid);
     L.stream = st;
     L.scene = c->d_scene;
-    L.P = P;
     L.out_w = W;
     L.count = count;
     L.list = list;
@@ -1530,16 +1535,7 @@ extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, in
     L.o8 = rgba8;
     L.o64 = rgb64f;
     L.orc2 = raycount2;
-    switch (depth) {
-        case 0: e = launch_refine<0>(L); break;
-        case 1: e = launch_refine<1>(L); break;
-        case 2: e = launch_refine<2>(L); break;
-        case 3: e = launch_refine<3>(L); break;
-        case 4: e = launch_refine<4>(L); break;
-        case 5: e = launch_refine<5>(L); break;
-        case 6: e = launch_refine<6>(L); break;
-        default: e = launch_refine<7>(L); break;
-    }
+    e = with_depth(depth, [&](auto B) { return launch_refine<decltype(B)::value>(L); });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_refine_kernel: ") + hipGetErrorString(e));
     return RT_OK;
 }
@@ -1549,79 +1545,45 @@ extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, in
 extern "C" int rt_render_adaptive(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
                                   int samples, int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                                   uint8_t* refined, rt_stats* stats, uint64_t* n_refined) {
-    if (!c) return rt_fail(RT_EINVAL, "rt_render_adaptive: null context");
-    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_adaptive: samples must be 1, 2, 4 or 8");
+    int rc = sampled_host_checks("rt_render_adaptive", c, W, H, samples);
+    if (rc) return rc;
     if (threshold < -1 || threshold > 255)
         return rt_fail(RT_EINVAL, "rt_render_adaptive: threshold must lie in -1 .. 255");
-    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31)) return rt_fail(RT_EINVAL, "rt_render_adaptive: bad image size");
-    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
-    if (rc) return rc;
-    RT_HIP(hipSetDevice(c->device));
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
     const size_t npx = (size_t)W * H;
-    const AdaptiveLayout lay = rt_adaptive_layout(npx);
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
-    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
-    for (int k = 0; k < 5; ++k)
-        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
-    void *d_ref = nullptr, *d_ws = nullptr;
-    if (refined && (rc = ctx_buffer(c, rt_ctx::kBufRefined, npx, &d_ref)) != RT_OK) return rc;
-    if ((rc = ctx_buffer(c, rt_ctx::kBufAdaptive, lay.bytes, &d_ws)) != RT_OK) return rc;
-    RT_HIP(hipEventRecord(c->ev0, c->rs));
-    rc = rt_render_adaptive_dev(c, cam, W, H, depth, samples, threshold, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
-                                (uint32_t*)d[3], (uint8_t*)d_ref, d_ws, lay.bytes, c->rs);
-    if (rc) return rc;
-    RT_HIP(hipEventRecord(c->ev1, c->rs));
-    if (stats) {
-        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
-        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
-                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
-        RT_HIP(hipGetLastError());
-    }
-    void* host[3] = {rgba32f, rgba8, rgb64f};
-    for (int k = 0; k < 3; ++k)
-        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
-    if (refined && (rc = copy_to_host(c, refined, d_ref, npx, c->rs))) return rc;
-    RT_HIP(hipStreamSynchronize(c->rs));
-    uint32_t n = 0;                                         // the work list's length: the refined pixels
-    RT_HIP(hipMemcpy(&n, d_ws, sizeof(n), hipMemcpyDeviceToHost));
-    if (n_refined) *n_refined = n;
-    if (stats) {
-        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
-        if (rc) return rc;
-        // every sample is a primary ray: one per unrefined pixel, S * S per refined one
-        const uint64_t prim = (uint64_t)(npx - n) + (uint64_t)n * (uint64_t)samples * (uint64_t)samples;
-        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
-        stats->primary_rays = prim;
-    }
-    return RT_OK;
+    const size_t ws_bytes = rt_adaptive_layout(npx).bytes;
+    ExtraBuf x[2] = {{rt_ctx::kBufRefined, refined ? npx : 0, refined, nullptr},
+                     {rt_ctx::kBufAdaptive, ws_bytes, nullptr, nullptr}};
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, x, 2,
+        [&](void* const* d) {
+            return rt_render_adaptive_dev(c, cam, W, H, depth, samples, threshold, (float*)d[0], (uint8_t*)d[1],
+                                          (double*)d[2], (uint32_t*)d[3], (uint8_t*)x[0].dev, x[1].dev, ws_bytes, c->rs);
+        },
+        [&](uint64_t* prim) {
+            uint32_t n = 0;                                 // the work list's length: the refined pixels
+            RT_HIP(hipMemcpy(&n, x[1].dev, sizeof(n), hipMemcpyDeviceToHost));
+            if (n_refined) *n_refined = n;
+            // one primary ray per unrefined pixel, S * S per refined one
+            *prim = (uint64_t)(npx - n) + (uint64_t)n * (uint64_t)samples * (uint64_t)samples;
+            return RT_OK;
+        });
 }
 
 // ---- depth of field (include/rt_api.h, ABI 10) --------------------------------------------------------------------
-// One launch of rt_dof_kernel (rt_dof.hpp) on `stream`: S x S lens samples per pixel through the generic trace path.
-// Nothing per view: no rt_prepare_kernel, no calibration, no dispatch table, and no field of the context is written,
-// so the context's cone and level masks and its tile order stay what the last rt_render_dev left.  No shortcut for
-// aperture 0 or samples 1.
+// One launch of rt_dof_kernel (rt_sampled.hpp) on `stream`: S x S lens samples per pixel through the generic trace
+// path.  Nothing per view: no rt_prepare_kernel, no calibration, no dispatch table, and no field of the context is
+// written, so the context's cone and level masks and its tile order stay what the last rt_render_dev left.  No
+// shortcut for aperture 0 or samples 1.
 extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
                                  double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                                  uint32_t* raycount2, void* stream) {
-    const int s = ss_log2_of(samples);
-    if (s < 0) return rt_fail(RT_EINVAL, "rt_render_dof_dev: samples must be 1, 2, 4 or 8");
     if (!(aperture >= 0.0) || !std::isfinite(aperture))
         return rt_fail(RT_EINVAL, "rt_render_dof_dev: aperture must be finite and >= 0");
-    if (!c) return rt_fail(RT_EINVAL, "render: null context");
-    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
-    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31) || (long long)W * samples > INT32_MAX ||
-        (long long)H * samples > INT32_MAX)
-        return rt_fail(RT_EINVAL, "rt_render_dof_dev: bad image size (width, height)");
-    rt_camera cam_s;
-    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
+    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
     if (rc) return rc;
-    DofLaunch L;                                            // P: the sample grid's, the kernel's ray set-up
-    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, &L.P);   // (at most 2^31 samples)
-    if (rc) return rc;
-    L.P.ss_log2 = s;
-    L.variant = c->tree ? 2 : c->transparent ? 1 : 0;
+    L.variant = trace_variant(c->tree, c->transparent);
     L.stream = (hipStream_t)stream;
     L.scene = c->d_scene;
     L.aperture = aperture;
@@ -1631,17 +1593,7 @@ extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, 
     L.orc2 = raycount2;
     if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
-    hipError_t e;
-    switch (depth) {
-        case 0: e = launch_dof<0>(L); break;
-        case 1: e = launch_dof<1>(L); break;
-        case 2: e = launch_dof<2>(L); break;
-        case 3: e = launch_dof<3>(L); break;
-        case 4: e = launch_dof<4>(L); break;
-        case 5: e = launch_dof<5>(L); break;
-        case 6: e = launch_dof<6>(L); break;
-        default: e = launch_dof<7>(L); break;
-    }
+    const hipError_t e = with_depth(depth, [&](auto B) { return launch_dof<decltype(B)::value>(L); });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_dof_kernel: ") + hipGetErrorString(e));
     return RT_OK;
 }
@@ -1650,45 +1602,19 @@ extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, 
 extern "C" int rt_render_dof(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
                              int samples, double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                              rt_stats* stats) {
-    if (!c) return rt_fail(RT_EINVAL, "rt_render_dof: null context");
-    if (ss_log2_of(samples) < 0) return rt_fail(RT_EINVAL, "rt_render_dof: samples must be 1, 2, 4 or 8");
+    int rc = sampled_host_checks("rt_render_dof", c, W, H, samples);
+    if (rc) return rc;
     if (!(aperture >= 0.0) || !std::isfinite(aperture))
         return rt_fail(RT_EINVAL, "rt_render_dof: aperture must be finite and >= 0");
-    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31))
-        return rt_fail(RT_EINVAL, "rt_render_dof: bad image size (width, height)");
-    int rc = rt_set_scene(c, scene);                    // no device work when the scene is unchanged
-    if (rc) return rc;
-    RT_HIP(hipSetDevice(c->device));
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
     const size_t npx = (size_t)W * H;
-    void* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const size_t bytes[5] = {npx * 16, npx * 4, npx * 24, npx * 8, 2 * sizeof(unsigned long long)};
-    const bool want[5] = {rgba32f != nullptr, rgba8 != nullptr, rgb64f != nullptr, stats != nullptr, stats != nullptr};
-    for (int k = 0; k < 5; ++k)
-        if (want[k] && (rc = ctx_buffer(c, k, bytes[k], &d[k])) != RT_OK) return rc;
-    RT_HIP(hipEventRecord(c->ev0, c->rs));
-    rc = rt_render_dof_dev(c, cam, W, H, depth, samples, aperture, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
-                           (uint32_t*)d[3], c->rs);
-    if (rc) return rc;
-    RT_HIP(hipEventRecord(c->ev1, c->rs));
-    if (stats) {
-        RT_HIP(hipMemsetAsync(d[4], 0, 2 * sizeof(unsigned long long), c->rs));
-        hipLaunchKernelGGL(rt_raysum2_kernel, dim3((unsigned)std::min<size_t>((npx + kThreads - 1) / kThreads, 1024)),
-                           dim3(kThreads), 0, c->rs, (const uint32_t*)d[3], npx, (unsigned long long*)d[4]);
-        RT_HIP(hipGetLastError());
-    }
-    void* host[3] = {rgba32f, rgba8, rgb64f};
-    for (int k = 0; k < 3; ++k)
-        if (host[k] && (rc = copy_to_host(c, host[k], d[k], bytes[k], c->rs))) return rc;
-    RT_HIP(hipStreamSynchronize(c->rs));
-    if (stats) {
-        rc = read_stats(c, npx, (const unsigned long long*)d[4], stats);
-        if (rc) return rc;
-        // every lens sample is a primary ray: the summed segment counters hold S * S of them per pixel
-        const uint64_t prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples;
-        stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
-        stats->primary_rays = prim;
-    }
-    return RT_OK;
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return rt_render_dof_dev(c, cam, W, H, depth, samples, aperture, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                                     (uint32_t*)d[3], c->rs);
+        },
+        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }
 
 // ---- copy_mode 3: device-to-host frames on an SDMA engine (HSA runtime, hsa_amd_memory_async_copy_on_engine) ----
@@ -1889,7 +1815,7 @@ static int render_packed_queue(rt_ctx* c, const rt_scene* scene, const rt_camera
                          f ? RT_PIXEL_RGBA8 : format, f ? nullptr : px, nullptr, (uint32_t*)rcb, c->rs);
     if (rc) return rc;
     if (with_stats) RT_HIP(hipEventRecord(c->ev1, c->rs));
-    if (with_stats && (rc = queue_raysum(c, npx, (uint32_t*)rcb, (unsigned long long*)*sums))) return rc;
+    if (with_stats && (rc = queue_raysum(c, npx, 1, (uint32_t*)rcb, (unsigned long long*)*sums))) return rc;
     if (mode == 3) {
         RT_HIP(sdma_fire(c, slot, c->sd_writer));      // the frame is in px
         RT_HIP(hipEventRecord(c->sd_fired[slot], c->rs));
@@ -2021,18 +1947,10 @@ static int trace_rays_launch(rt_ctx* c, const double* starts, const double* ends
                              uint32_t* raycount, hipStream_t st, const ScreenArgs& sa) {
     RT_HIP(hipSetDevice(c->device));
     const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
-    const int v = c->tree ? 2 : c->transparent ? 1 : 0;
-    hipError_t e;
-    switch (depth) {
-        case 0: e = launch_trace_rays<0>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 1: e = launch_trace_rays<1>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 2: e = launch_trace_rays<2>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 3: e = launch_trace_rays<3>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 4: e = launch_trace_rays<4>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 5: e = launch_trace_rays<5>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        case 6: e = launch_trace_rays<6>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-        default: e = launch_trace_rays<7>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa); break;
-    }
+    const int v = trace_variant(c->tree, c->transparent);
+    const hipError_t e = with_depth(depth, [&](auto B) {
+        return launch_trace_rays<decltype(B)::value>(v, grid, st, c->d_scene, starts, ends, n, rgb64f, raycount, sa);
+    });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_trace_rays_kernel: ") + hipGetErrorString(e));
     return RT_OK;
 }
@@ -2176,17 +2094,7 @@ extern "C" int rt_diag_tile_order(rt_ctx* c, int mode) {
 extern "C" int rt_diag_kernel_resources(int depth, int variant, int* vgprs, int* scratch_bytes) {
     if (depth < 0 || depth > RT_MAX_B || variant < 0 || variant > 5 || !vgprs || !scratch_bytes)
         return rt_fail(RT_EINVAL, "rt_diag_kernel_resources: bad arguments");
-    const void* f = nullptr;
-    switch (depth) {
-        case 0: f = render_kernel_ptr<0>(variant); break;
-        case 1: f = render_kernel_ptr<1>(variant); break;
-        case 2: f = render_kernel_ptr<2>(variant); break;
-        case 3: f = render_kernel_ptr<3>(variant); break;
-        case 4: f = render_kernel_ptr<4>(variant); break;
-        case 5: f = render_kernel_ptr<5>(variant); break;
-        case 6: f = render_kernel_ptr<6>(variant); break;
-        default: f = render_kernel_ptr<7>(variant); break;
-    }
+    const void* f = with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(variant); });
     if (!f) return rt_fail(RT_EINVAL, "rt_diag_kernel_resources: kernel not built");
     hipFuncAttributes a;
     RT_HIP(hipFuncGetAttributes(&a, f));
@@ -2200,17 +2108,7 @@ extern "C" int rt_diag_kernel_resources(int depth, int variant, int* vgprs, int*
 extern "C" int rt_diag_kernel_occupancy(int depth, int variant, int lds_bytes, int* blocks_per_cu) {
     if (depth < 0 || depth > RT_MAX_B || variant < 0 || variant > 5 || lds_bytes < 0 || !blocks_per_cu)
         return rt_fail(RT_EINVAL, "rt_diag_kernel_occupancy: bad arguments");
-    const void* f = nullptr;
-    switch (depth) {
-        case 0: f = render_kernel_ptr<0>(variant); break;
-        case 1: f = render_kernel_ptr<1>(variant); break;
-        case 2: f = render_kernel_ptr<2>(variant); break;
-        case 3: f = render_kernel_ptr<3>(variant); break;
-        case 4: f = render_kernel_ptr<4>(variant); break;
-        case 5: f = render_kernel_ptr<5>(variant); break;
-        case 6: f = render_kernel_ptr<6>(variant); break;
-        default: f = render_kernel_ptr<7>(variant); break;
-    }
+    const void* f = with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(variant); });
     if (!f) return rt_fail(RT_EINVAL, "rt_diag_kernel_occupancy: kernel not built");
     RT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, RT_WG_FAST, (size_t)lds_bytes));
     return RT_OK;

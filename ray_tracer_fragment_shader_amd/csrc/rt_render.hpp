@@ -27,6 +27,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "../../include/rt_api.h"
 #include "rt_device.hpp"
 
@@ -316,6 +318,62 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 
     }
 }
 
+// ---- The sample-grid contract of include/rt_api.h (rt_render_ss_dev), spelled once for render_body's supersampled
+// instances and the two list-free sampled kernels of rt_sampled.hpp (rt_refine_kernel, rt_dof_kernel). ----
+
+// Screen point of pixel (ic, j) of the frame P describes (for a sampled render: the sample grid),
+//     sp = (look + (pitch (ic + bottom_x)) right) + (pitch (j + bottom_y)) up',
+// one IEEE operation per parenthesis and component, in this order (-ffp-contract=off): the end of the primary ray
+// Line(camera, sp), SURVEY.md Appendix B (basis: rayTraceScreen :1270-1279).
+__device__ __forceinline__ d3 screen_point(const RenderParams& P, int ic, int j, d3 right, d3 upp) {
+    return add(add(ld3(P.look), scl(P.pitch * (double)(ic + P.bottom_x), right)),
+               scl(P.pitch * (double)(j + P.bottom_y), upp));
+}
+
+// The S x S samples of a pixel, S = 2^s, one per lane: sample (a, b) sits a lanes and b * stride lanes past the
+// pixel's first lane (stride 8 in an 8 x 8 tile of the sample grid, S where a pixel's samples are consecutive lanes).
+// Colour and the two ray counters are summed per channel, the colour in FP64, as the fixed pairwise tree of
+// include/rt_api.h: an xor butterfly with partners 1, 2, .. S/2 (along a), then stride, 2 stride, .. stride S/2
+// (along b), every lane of the wave active; then the exact scale 1 / S^2 (a power of two).  IEEE addition is
+// commutative bit for bit for non-NaN operands, so every lane of a pixel's block ends with the same bits, the
+// contract's; a NaN's sign and payload may differ by lane: unspecified.
+__device__ __forceinline__ void reduce_samples(int s, int stride, d3& col, uint32_t& seg, uint32_t& sh) {
+    const auto step = [&](int m) {
+        col.x += __shfl_xor(col.x, m);
+        col.y += __shfl_xor(col.y, m);
+        col.z += __shfl_xor(col.z, m);
+        seg += __shfl_xor(seg, m);
+        sh += __shfl_xor(sh, m);
+    };
+    // (one loop, whose step from S/2 goes on at stride: with stride = S it folds to plain doubling up to S^2 / 2)
+    const int S = 1 << s;
+    for (int m = 1; m <= stride * (S - 1); m = 2 * m == S ? stride : 2 * m) step(m);
+    col = scl(ldexp(1.0, -2 * s), col);
+}
+
+// Store output pixel k of a sampled render: RGBA32F / RGBA8, RGB64F, and the counters as two words per pixel
+// (summed over S^2 ray trees the packed 16 + 16-bit word of the plain render would overflow).
+__device__ __forceinline__ void store_sampled(const RenderParams& P, size_t k, d3 col, uint32_t seg, uint32_t sh,
+                                              void* o32, void* o8, double* o64, uint32_t* orc2) {
+    store_pixel<false>(P, k, col, o32, o8);
+    if (o64) { o64[3 * k] = col.x; o64[3 * k + 1] = col.y; o64[3 * k + 2] = col.z; }
+    if (orc2) { orc2[2 * k] = seg; orc2[2 * k + 1] = sh; }
+}
+
+// rayTraceRay on Line(p0, p1) through the generic path: no per-tile cone or level masks, V.hits_ok as the caller set
+// it.  lds: the workgroup's trace() slots (slot_bytes(B, TRANSP, WG); unused by ray trees).  (rt_trace_rays_kernel
+// below spells the same call itself: through this helper its depth-3 FULL instance came out with other instructions.)
+template <int B, bool TRANSP, bool TREE, int WG>
+__device__ __forceinline__ d3 trace_generic(const SceneView& V, d3 p0, d3 p1, char* lds, uint32_t* seg, uint32_t* sh) {
+    if constexpr (TREE) {
+        return trace_tree<B>(V, p0, p1, seg, sh);
+    } else {
+        double* slot = reinterpret_cast<double*>(lds) + threadIdx.x;
+        int* mslot = reinterpret_cast<int*>(lds + 3 * 8 * colour_slots(B, TRANSP) * WG) + threadIdx.x;
+        return trace<B, false, TRANSP, false, WG>(V, p0, p1, ~0ull, seg, sh, slot, mslot);
+    }
+}
+
 template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG = kThreads, bool TREE = false,
           bool PACKED = false, bool FIX64 = false, bool ACHRO = false, bool SS = false>
 __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene, RenderParams P,
@@ -427,9 +485,7 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     const int ic = i < P.width ? i : P.width - 1, lrc = lr < P.local_rows ? lr : P.local_rows - 1;
     const int j = global_row_of(P, lrc);
     const d3 right = ld3(P.right), upp = ld3(P.upp);
-    // Primary ray Line(camera, sp), SURVEY.md Appendix B (basis: rayTraceScreen :1270-1279).
-    const d3 sp = add(add(ld3(P.look), scl(P.pitch * (double)(ic + P.bottom_x), right)),
-                      scl(P.pitch * (double)(j + P.bottom_y), upp));
+    const d3 sp = screen_point(P, ic, j, right, upp);    // primary ray Line(camera, sp)
 #if RT_WAVE_TRACE
     const uint64_t t_mid = __builtin_amdgcn_s_memrealtime();   // prologue done: the primary ray is formed
 #endif
@@ -467,28 +523,10 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
         const int i_e = tx * TW + (tid_e >> 6) * bw + (lane_e & 7), lr_e = ty_st * kTileH + (lane_e >> 3);
         if constexpr (SS) {
             // Supersampled instance: lane (x, y) of the 8 x 8 tile holds sample (x mod S, y mod S) of output pixel
-            // (tile_x * 8 / S + x / S, tile_row * 8 / S + y / S).  The S x S samples of a pixel are summed per channel
-            // in FP64 as the fixed pairwise tree of include/rt_api.h (rt_render_ss_dev): an xor butterfly over lane
-            // bits 0..2 (x: partners 1, 2, .. S/2), then bits 3..5 (y: 8, 16, .. 8 S/2), every lane active.  IEEE
-            // addition is commutative bit for bit for non-NaN operands, so all lanes of a pixel's block end with the
-            // same bits (a NaN's sign and payload may differ by lane: unspecified); 1 / S^2 is a power of two.
+            // (tile_x * 8 / S + x / S, tile_row * 8 / S + y / S): reduce_samples with lane stride 8.
             static_assert(WG == 64 && !PACKED && !LDS, "supersampling: one-wave RGBA direct-store instances only");
             const int s = P.ss_log2, S1 = (1 << s) - 1;
-            for (int m = 1; m <= S1; m <<= 1) {
-                col.x += __shfl_xor(col.x, m);
-                col.y += __shfl_xor(col.y, m);
-                col.z += __shfl_xor(col.z, m);
-                seg += __shfl_xor(seg, m);
-                sh += __shfl_xor(sh, m);
-            }
-            for (int m = 8; m <= 8 * S1; m <<= 1) {
-                col.x += __shfl_xor(col.x, m);
-                col.y += __shfl_xor(col.y, m);
-                col.z += __shfl_xor(col.z, m);
-                seg += __shfl_xor(seg, m);
-                sh += __shfl_xor(sh, m);
-            }
-            col = scl(ldexp(1.0, -2 * s), col);                // 1.0 / (S * S), exact
+            reduce_samples(s, 8, col, seg, sh);
             // P.width and P.local_rows are the sample frame's: S x the output's width and local rows, and S divides
             // 8, so an S x S block lies either wholly inside the sample frame or wholly outside it: the block of an
             // in-frame pixel never holds a clamped out-of-frame sample, and the test on the block's first lane is
@@ -496,10 +534,7 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
             if (((lane_e & 7) & S1) == 0 && ((lane_e >> 3) & S1) == 0 && i_e < P.width && lr_e < P.local_rows) {
                 const RenderOuts O = late_outputs();
                 const size_t k = (size_t)(lr_e >> s) * (size_t)(P.width >> s) + (size_t)(i_e >> s);
-                store_pixel<false>(P, k, col, O.o32, O.o8);
-                if (O.o64) { O.o64[3 * k] = col.x; O.o64[3 * k + 1] = col.y; O.o64[3 * k + 2] = col.z; }
-                // two words per pixel (summed over S^2 ray trees the packed 16 + 16-bit word would overflow)
-                if (O.orc) { O.orc[2 * k] = seg; O.orc[2 * k + 1] = sh; }
+                store_sampled(P, k, col, seg, sh, O.o32, O.o8, O.o64, O.orc);
             }
         } else
         if (i_e < P.width && lr_e < P.local_rows) {
@@ -640,11 +675,13 @@ constexpr bool kernarg_offsets_match(void (*)(A...)) {
            K::offset(5) == offsetof(RenderArgs, o32) && K::offset(6) == offsetof(RenderArgs, o8) &&
            K::offset(7) == offsetof(RenderArgs, o64) && K::offset(8) == offsetof(RenderArgs, orc);
 }
-static_assert(kernarg_offsets_match(&rt_render_kernel<1, 0, 1, false, false>),
+// (The kernels are named inside decltype, an unevaluated operand: their types are all the check needs, so no
+// translation unit instantiates or emits a kernel for it.)
+static_assert(kernarg_offsets_match(decltype(&rt_render_kernel<1, 0, 1, false, false>){}),
               "rt_render_kernel's parameters must lay out as RenderArgs (late_outputs)");
-static_assert(kernarg_offsets_match(&rt_render_kernel_sg<1, 1, false, false>),
+static_assert(kernarg_offsets_match(decltype(&rt_render_kernel_sg<1, 1, false, false>){}),
               "rt_render_kernel_sg's parameters must lay out as RenderArgs (late_outputs)");
-static_assert(kernarg_offsets_match(&rt_render_kernel_sg8<1, 1, false, false>),
+static_assert(kernarg_offsets_match(decltype(&rt_render_kernel_sg8<1, 1, false, false>){}),
               "rt_render_kernel_sg8's parameters must lay out as RenderArgs (late_outputs)");
 
 // rayTraceRay on a list of rays Line(starts[k], ends[k]).  Rays from arbitrary starts: whether their hit
@@ -780,6 +817,25 @@ const void* render_kernel_ptr(int variant);   // rt_diag_kernel_resources: 0 fas
 RT_DECLARE_DEPTH(0) RT_DECLARE_DEPTH(1) RT_DECLARE_DEPTH(2) RT_DECLARE_DEPTH(3)
 RT_DECLARE_DEPTH(4) RT_DECLARE_DEPTH(5) RT_DECLARE_DEPTH(6) RT_DECLARE_DEPTH(7)
 #undef RT_DECLARE_DEPTH
+
+// f(std::integral_constant<int, B>) for the bounce depth B = depth of a checked render (0 .. 7: rt_api.h RT_MAX_DEPTH),
+// the one place a runtime depth becomes a template argument.
+template <class F>
+auto with_depth(int depth, F&& f) {
+    switch (depth) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        default: return f(std::integral_constant<int, 7>{});
+    }
+}
+
+// The `variant` of the generic-path launches (launch_trace_rays and rt_sampled.hpp's) for a scene kind.
+inline int trace_variant(bool tree, bool transparent) { return tree ? 2 : transparent ? 1 : 0; }
 
 // Body of the per-depth instance files.
 template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG, bool TREE, bool PACKED = false, bool FIX64 = false,

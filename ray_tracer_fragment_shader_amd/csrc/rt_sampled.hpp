@@ -1,0 +1,161 @@
+// rt_sampled.hpp — the two list-free sampled kernels: S x S rays per output pixel, one per lane, reduced in the wave.
+//
+//   rt_refine_kernel<B, TRANSP, TREE>  adaptive supersampling (rt_render_adaptive_dev, include/rt_api.h): the samples
+//                                      of the pixels on a compacted work list.
+//   rt_dof_kernel<B, TRANSP, TREE>     depth of field (rt_render_dof_dev): thin-lens rays over the whole frame.
+//
+// Both take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
+// share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
+// screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
+// the reduced pixel.  Neither has a tile of neighbouring rays from one origin, so there are no cone or level masks:
+// the rays take the generic path (trace_generic, as rt_trace_rays_kernel) with hits_ok_from of their start.  trace()
+// reduces over the whole wave, so every lane stays active: lanes without a sample of their own trace a clamped one
+// and store nothing.
+//
+// The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
+// rt_adaptive.hip (rt_adaptive_b<B>.o) and rt_dof.hip (rt_dof_b<B>.o).
+#pragma once
+
+#include "rt_render.hpp"
+
+namespace rtk {
+
+// One-wave workgroups; a fixed grid (the pixel count is only known on the device: rt_classify_kernel, rt_kernel.hip,
+// writes the list and its length) walks the list with a grid-stride loop.  A wave takes 64 / S^2 listed pixels per
+// step: lane l traces sample (a, b) of the pixel of its group l >> 2 log2 S, a = the low log2 S bits of l, b the next
+// log2 S: reduce_samples with lane stride S.  Lanes past the end of the list repeat its last pixel.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_refine_kernel(const DevScene* __restrict__ S, RenderParams P, int out_w,
+                                                       const uint32_t* __restrict__ count,
+                                                       const uint32_t* __restrict__ list, void* o32, void* o8,
+                                                       double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const uint32_t n = *count;                              // pixels on the list
+    const int s = P.ss_log2, s2 = 2 * s;
+    const uint32_t per_wave = 64u >> s2;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const d3 eye = ld3(P.eye);
+    V.hits_ok = hits_ok_from(S, eye);
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const int a = lane & ((1 << s) - 1), b = (lane >> s) & ((1 << s) - 1);
+    for (uint64_t g = blockIdx.x; g * per_wave < n; g += gridDim.x) {
+        const uint32_t q = (uint32_t)(g * per_wave) + (uint32_t)(lane >> s2);
+        const uint32_t pix = list[q < n ? q : n - 1];       // j * out_w + i
+        const int j0 = (int)(pix / (uint32_t)out_w), i0 = (int)(pix - (uint32_t)j0 * (uint32_t)out_w);
+        const d3 sp = screen_point(P, (i0 << s) + a, (j0 << s) + b, right, upp);
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64>(V, eye, sp, smem, &seg, &sh);
+        reduce_samples(s, 1 << s, col, seg, sh);
+        if ((lane & ((1 << s2) - 1)) == 0 && q < n) store_sampled(P, pix, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
+constexpr int kDofGridY = 32768;               // tile rows per grid.z slice (grid.y and grid.z stay below 65536)
+
+// One-wave workgroups; a wave owns one 8 x 8 block of the sample grid — an (8 / S) x (8 / S) tile of output pixels —
+// with lane bits 0..2 = x and bits 3..5 = y, as render_body's supersampled instances: lane (x, y) holds sample
+// (a, b) = (x mod S, y mod S) of output pixel (8 tx / S + x / S, 8 ty / S + y / S): reduce_samples with lane stride 8,
+// and the lanes of a wave trace neighbouring pixels (the coherence the scattered refine kernel lacks).
+//
+// The ray's end is its sample's screen point; its start is the lens point
+//     e(a, b) = (eye + (A t_a) right) + (A t_b) up',   t_a = (2 a + 1 - S) / S,
+// one IEEE operation per parenthesis and component, in this order; hits_ok_from(e) per lane.  A = 0 and S = 1 run this
+// same code.  The sample frame is S times the output, and S divides 8, so an S x S block lies wholly inside the sample
+// frame or wholly outside it; lanes outside (and the padding tile rows of the last grid.z slice) store nothing.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_dof_kernel(const DevScene* __restrict__ S, RenderParams P, double aperture,
+                                                    int tile_rows, void* o32, void* o8, double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const d3 sp = screen_point(P, ic, j, right, upp);
+    // Ray start: t = (2 a + 1 - S) / S, an exact quotient (S is a power of two: the product with 2^-s is the same bits)
+    const double inv_s = ldexp(1.0, -s);
+    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    V.hits_ok = hits_ok_from(S, e);
+    uint32_t seg = 0, sh = 0;
+    d3 col = trace_generic<B, TRANSP, TREE, 64>(V, e, sp, smem, &seg, &sh);
+    reduce_samples(s, 8, col, seg, sh);
+    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
+// A launch of either kernel.
+struct SampledLaunch {
+    int variant;                               // trace_variant()
+    hipStream_t stream;
+    const DevScene* scene;
+    RenderParams P;                            // the sample grid's (ss_log2 set)
+    void* o32;
+    void* o8;
+    double* o64;
+    uint32_t* orc2;
+    // rt_refine_kernel
+    unsigned grid;
+    int out_w;
+    const uint32_t* count;
+    const uint32_t* list;
+    // rt_dof_kernel
+    double aperture;                           // half-width of the lens
+};
+
+// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip) and rt_dof_b<B>.o (rt_dof.hip).
+template <int B>
+hipError_t launch_refine(const SampledLaunch& L);
+template <int B>
+hipError_t launch_dof(const SampledLaunch& L);
+#define RT_DECLARE_SAMPLED(B)                           \
+    template <>                                         \
+    hipError_t launch_refine<B>(const SampledLaunch& L); \
+    template <>                                         \
+    hipError_t launch_dof<B>(const SampledLaunch& L);
+RT_DECLARE_SAMPLED(0) RT_DECLARE_SAMPLED(1) RT_DECLARE_SAMPLED(2) RT_DECLARE_SAMPLED(3)
+RT_DECLARE_SAMPLED(4) RT_DECLARE_SAMPLED(5) RT_DECLARE_SAMPLED(6) RT_DECLARE_SAMPLED(7)
+#undef RT_DECLARE_SAMPLED
+
+// The scene kind's instance of a kernel template <B, TRANSP, TREE> with one-wave workgroups:
+// launch(TRANSP, TREE, lds bytes) (two std::bool_constant) launches it.
+template <int B, class Launch>
+hipError_t launch_sampled(int variant, Launch&& launch) {
+    if constexpr (B > RT_MAX_B) {
+        return hipErrorInvalidValue;
+    } else {
+        if (variant == 2) launch(std::true_type{}, std::true_type{}, (size_t)0);
+        else if (variant == 1) launch(std::true_type{}, std::false_type{}, (size_t)slot_bytes(B, true, 64));
+        else launch(std::false_type{}, std::false_type{}, (size_t)slot_bytes(B, false, 64));
+        return hipGetLastError();
+    }
+}
+
+template <int B>
+hipError_t launch_refine_impl(const SampledLaunch& L) {
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_refine_kernel<B, decltype(transp)::value, decltype(tree)::value>), dim3(L.grid), dim3(64),
+                           lds, L.stream, L.scene, L.P, L.out_w, L.count, L.list, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_dof_impl(const SampledLaunch& L) {
+    const int tiles_x = (L.P.width + 7) / 8, tile_rows = (L.P.height + 7) / 8;
+    const dim3 g((unsigned)tiles_x, (unsigned)std::min(tile_rows, kDofGridY),
+                 (unsigned)((tile_rows + kDofGridY - 1) / kDofGridY));
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_dof_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.P, L.aperture, tile_rows, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+}  // namespace rtk
