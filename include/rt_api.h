@@ -339,6 +339,54 @@ int rt_render_dof_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, 
 int rt_render_dof(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int width, int height, int depth,
                   int samples, double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
+/* ---- soft shadows (ABI 10: new symbols only) -------------------------------------------------------- */
+/* Square area lights: the S x S samples of a pixel see every light at S x S points of a square panel, so shadow
+ * edges become penumbrae.  Deterministic, and defined entirely by rt_set_scene and rt_trace_rays_dev on scenes and
+ * rays this text spells out.  For a full width x height frame, S = `samples` in {1, 2, 4, 8}, A = `aperture` and
+ * R = `light_size`, both finite and >= 0:
+ *  1. Rays.  Exactly rt_render_dof_dev rules 1-2: sample (a, b) of pixel (i, j) is the ray
+ *     Line(e(a, b), sp_s(S i + a, S j + b)), with e(a, b) on the square lens of half-width A.
+ *  2. Lights of a sample.  Every light i of the uploaded scene is a square panel of half-width R centred at the
+ *     light's position L_i, in the world xz-plane (parallel to the reference's board, whose normal is (0, -1, 0)).
+ *     Sample (a, b) sees light i at
+ *         (L_i.x + (R * t_a), L_i.y, L_i.z + (R * t_b)),   t_a = (double)(2 a + 1 - S) / (double)S
+ *     (an exact quotient), each parenthesis and each sum one IEEE operation.  Colours are unchanged, one R serves all
+ *     lights, and the light point is paired with the lens point and the sub-pixel point of the same (a, b).
+ *  3. Value.  The colour and the counters of a sample are what rt_trace_rays_dev gives its ray after rt_set_scene of
+ *     the scene with the lights of rule 2: rayTraceRay(scene_ab, lights_ab, Line(start, end), colour, depth).
+ *  4. Reduction and outputs follow rt_render_ss_dev rules 3-5 exactly: the fixed pairwise tree along a, then along
+ *     b, then * 1 / (S S); rgb64f, rgba32f and rgba8 derive from the reduced value; raycount2 holds two uint32 per
+ *     pixel, summed over the samples; a channel with a NaN sample is NaN (sign and payload unspecified), its rgba8 0.
+ *  5. Pins that follow, with NO shortcut in the implementation (all run the same kernel as any other R): R = 0
+ *     writes the images and counters rt_render_dof_dev writes, for any A; A = 0 and R = 0 writes what
+ *     rt_render_ss_dev writes; S = 1 writes the images rt_render_dev writes for any A and R (t = 0; the counters are
+ *     still two words).  The pins assume that no light has a -0.0 x or z component (L + (+-0) is L only then), as
+ *     the lens pins assume for the eye.
+ *  6. Full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host synchronisation, so the
+ *     call may be captured in a hipGraph.  No per-view state, as rt_render_dof_dev rule 8.  The displaced lights are
+ *     formed in the kernel: the call neither writes nor re-uploads the context's scene record, and later
+ *     rt_render_dev, rt_render_dof_dev and other calls on the context give exactly what they gave before.
+ *  7. RT_EINVAL (rt_last_error names the argument) for `samples` outside {1, 2, 4, 8}, an `aperture` or a
+ *     `light_size` that is negative, NaN or infinite, a bad frame size (the sample frame S width x S height holds at
+ *     most 2^31 samples), and an int32 overflow of the sample-grid camera.  A rejected call writes no pixel.
+ *  8. Not offered: per-light sizes, disc-shaped or jittered panels, and a pairing of light, lens and sub-pixel
+ *     points other than by (a, b).  A penumbra is therefore a ramp of at most S * S steps, the same in every pixel.
+ *     rt_render_multi, the packed and asynchronous host paths and the drop-in draw() keep point lights.
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, A = 0, RGBA32F + RGBA8, tools/bench_soft.py): S = 2 130 us
+ * and S = 4 525 us per frame, 1.07 x and 1.08 x rt_render_dof_dev at the same S and A (the price of a shadow test
+ * without the point light's cone filter), 1.53 x rt_render_ss_dev, and 3.9 x and 3.1 x faster than S x S calls of
+ * rt_trace_rays_dev on pre-uploaded displaced scenes with the reduction in further passes (5.3 x and 4.5 x with the
+ * rt_set_scene uploads).  Other scenes and depths: not measured. */
+/* Device pointers, each output nullable, width * height pixels. */
+int rt_render_soft_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples,
+                       double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                       uint32_t* raycount2, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_ss.  *stats: primary_rays = width * height * S * S, reflect_rays
+ * and shadow_rays from the summed counters. */
+int rt_render_soft(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int width, int height, int depth,
+                   int samples, double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                   rt_stats* stats);
+
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.
  * GRAY formats hold the R channel only and are accepted only for an ACHROMATIC scene (rt_scene_achromatic):

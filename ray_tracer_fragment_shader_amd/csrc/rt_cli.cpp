@@ -28,6 +28,9 @@
 //                                                  depth of field: the S x S samples start on a square lens of
 //                                                  half-width 8 around the eye (rt_render_dof); --focus moves the
 //                                                  focal plane to RATIO times the look-at distance (rt_camera_focus)
+//   rt_render --config c2 --samples 4 --light-size 40 [--aperture 8 [--focus 0.8]] --out c2_soft.ppm
+//                                                  soft shadows: every light a square panel of half-width 40 in the
+//                                                  world xz-plane, one of its S x S points per sample (rt_render_soft)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -62,6 +65,8 @@ struct Options {
     double aperture = 0.0;
     bool focus = false;                      // --focus RATIO: rt_camera_focus before a --aperture render
     double focus_ratio = 1.0;
+    bool soft = false;                       // --light-size R: rt_render_soft with panel half-width R (needs --samples)
+    double light_size = 0.0;
 };
 
 // A finite number that fills the whole argument, or a usage error.
@@ -203,9 +208,11 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive") { o.adaptive = true; o.threshold = std::atoi(next().c_str()); }
         else if (a == "--aperture") { o.dof = true; o.aperture = number_arg(a, next()); }
         else if (a == "--focus") { o.focus = true; o.focus_ratio = number_arg(a, next()); }
+        else if (a == "--light-size") { o.soft = true; o.light_size = number_arg(a, next()); }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
-                                    "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | --aperture A [--focus RATIO]]] "
+                                    "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
+                                    "[--aperture A [--focus RATIO]]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
     }
@@ -221,6 +228,15 @@ int main(int argc, char** argv) {
     }
     if (o.dof && o.aperture < 0.0) {
         std::fprintf(stderr, "rt_render: --aperture must be >= 0\n");
+        return 2;
+    }
+    if (o.soft && (o.samples == 0 || o.adaptive || o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --light-size needs --samples, excludes --adaptive and applies to plain frames "
+                             "(not --faithful or --gpus)\n");
+        return 2;
+    }
+    if (o.soft && o.light_size < 0.0) {
+        std::fprintf(stderr, "rt_render: --light-size must be >= 0\n");
         return 2;
     }
     if (o.focus && (!o.dof || !(o.focus_ratio > 0.0))) {
@@ -339,7 +355,10 @@ int main(int argc, char** argv) {
     uint64_t n_refined = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < o.repeat; ++k) {
-        if (o.dof)
+        if (o.soft)
+            check(rt_render_soft(ctx, &scene, &cam, W, H, depth, o.samples, o.aperture, o.light_size, nullptr,
+                                 rgba8.data(), nullptr, &st), "rt_render_soft");
+        else if (o.dof)
             check(rt_render_dof(ctx, &scene, &cam, W, H, depth, o.samples, o.aperture, nullptr, rgba8.data(), nullptr,
                                 &st), "rt_render_dof");
         else if (o.adaptive)
@@ -360,7 +379,11 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.dof)
+    if (o.soft)
+        std::printf("rt_render: soft shadows, light half-width %g, lens half-width %g: %d x %d light samples per "
+                    "pixel, %llu primary rays\n", o.light_size, o.aperture, o.samples, o.samples,
+                    (unsigned long long)st.primary_rays);
+    else if (o.dof)
         std::printf("rt_render: depth of field, lens half-width %g, focus ratio %g: %d x %d lens samples per pixel\n",
                     o.aperture, o.focus_ratio, o.samples, o.samples);
     else if (o.adaptive)

@@ -1305,6 +1305,37 @@ __device__ __forceinline__ bool occluded(const SceneView& V, const Ray& r, int l
     else return occluded_ret<FULL, CULL>(V, r, li, mask, skip);
 }
 
+// The same shadow test for a ray whose end is NOT the stored light position (area lights, shade AREA: the light point
+// is displaced per lane).  Nothing proven for lines through the stored light holds for it, so neither the light-cone
+// records nor a shadow mask are read: the spheres pass the generic ray filter (sphere_reject32 on the ray's own FP32
+// image, r's set_origin_f32 and set_dir) and then the exact test, after the board, in closest_hit's visiting order.
+// What is kept argues from the ray's origin alone, which is still a hit point: the bounding-sphere shortcut
+// (hits_inside: a hit point lies inside the shortcut radius, so the cull passes for every direction, bound_pass_dp)
+// and `skip` (origin_skip: "any ray from q" misses the board / sphere q lies on).  Opaque scenes only (any hit blocks).
+__device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray& r, int skip = -1) {
+    const DevScene* S = V.S;
+    if (!(RT_HITS_INSIDE && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return false;
+    const double eps = S->eps;
+    bool blocked = false;
+    if (S->has_board && skip != 0) {
+        d3 q;
+        blocked = board_hit(S, r.p0, r.d, &q);
+    }
+    for (int k0 = 0; k0 < V.np; k0 += kChunk) {
+        uint32_t pass = 0;
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(V.sphf[k0 + j], r) ? 0u : 1u) << j;
+        pass = blocked ? 0u : drop_self(pass, skip - 1, k0);
+        while (pass) {
+            const int k = k0 + __builtin_ctz(pass);
+            d3 q;
+            blocked = sphere_hit(V.sph[k], r.p0, r.u, eps, &q);
+            pass = blocked ? 0u : pass & (pass - 1);
+        }
+    }
+    return blocked;
+}
+
 // Material of a hit (checker parity for the board, :1101-1111).
 // (int)(x / square) for the checker, both quotients sharing one reciprocal r = rcp_core(square) (the
 // compiler's own Newton steps): for |x| in [2^-969, 2^500] and a normal `square` div_core is the IEEE
@@ -1415,11 +1446,19 @@ __device__ __forceinline__ uint64_t* level_masks_out();
 // ACHRO (an achromatic scene, rt_scene_achromatic: every light colour and every material term an object uses has
 // R = G = B): the three channels are the same operations on equal values, so only R is computed and the colour is
 // (R, R, R) — bit for bit the reference's (G and B are R's operations repeated).  Not with FULL (transparency weights).
-template <bool FULL, bool CULL, bool ACC = false, int SS = 256, bool ACHRO = false>
+// AREA (soft shadows, rt_render_soft_dev): this lane sees every light displaced by `ls` in the world xz-plane,
+// lpos = (L.x + ls.x, L.y, L.z + ls.z), one addition per component.  The shadow ray then ends off the stored light
+// position: no cone records, no shadow or level masks (occluded_anywhere); FULL already decides shadows with the
+// generic closest hit.
+struct LightShift {
+    double x, z;
+};
+template <bool FULL, bool CULL, bool ACC = false, int SS = 256, bool ACHRO = false, bool AREA = false>
 __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, int mat, double ks,
                                     int skip = -1, double* acc = nullptr, const LevelMasks* lm = nullptr,
-                                    int lslot = 0) {
+                                    int lslot = 0, LightShift ls = LightShift{0.0, 0.0}) {
     static_assert(!(ACHRO && FULL), "achromatic shading is for opaque scenes");
+    static_assert(!(AREA && (CULL || ACHRO)), "area lights take the generic path");
     const DevScene* S = V.S;
     d3 color = mk(0.0, 0.0, 0.0);
     if (ACC) {
@@ -1431,9 +1470,10 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
     }
     Ray sr;
     sr.p0 = p;
-    if (FULL) set_origin_f32(S, &sr);                       // closest-hit shadows use the ray filter
+    if (FULL || AREA) set_origin_f32(S, &sr);               // closest-hit (and area-light) shadows use the ray filter
     for (int i = 0; i < V.nl; ++i) {
         d3 lpos = ld3(S->light[i].pos);
+        if (AREA) lpos = mk(lpos.x + ls.x, lpos.y, lpos.z + ls.z);
         d3 sd = sub(lpos, p);                               // shadowRay end - start (:1216)
         double dl;                                          // shadowRay.length()
         d3 sdir = unit(sd, &dl);                            // shadowRay.direction()
@@ -1441,7 +1481,9 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         const double kd = fabs(dot(n, sdir));               // before the shadow test: fewer live registers
         uint64_t m = ~0ull;
         const int t = lm ? lm->tile : -1;
-        if (CULL && !FULL && (V.np >= kConeMin || t >= 0)) {
+        if (AREA) {
+            // (no mask: the cached and the computed ones are proven for lines through the stored light)
+        } else if (CULL && !FULL && (V.np >= kConeMin || t >= 0)) {
             // (light i's shadow mask at this level: cached per tile for a calibrated static view, LevelMasks; also
             // computed for a fast scene when this render writes the cache)
             const uint64_t* in = t >= 0 ? level_masks_in() : nullptr;
@@ -1460,7 +1502,8 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         bool lit = false;
         if (hit)
             lit = !(FULL ? occluded_transparent(V, sr)
-                         : occluded<false, CULL, RT_OCCL_FLAT && (ACHRO || !CULL)>(V, sr, i, m, skip));
+                    : AREA ? occluded_anywhere(V, sr, skip)
+                           : occluded<false, CULL, RT_OCCL_FLAT && (ACHRO || !CULL)>(V, sr, i, m, skip));
         if (lit && ACHRO) {                                 // R only (same operations as below, channel x)
             const double a = S->att / (S->att + dl * dl);   // attenuation (:1181)
             const double lc = a * S->light[i].col[0];       // :1223
@@ -1664,10 +1707,12 @@ __device__ __forceinline__ bool cull_level(const SceneView& V, int lvl, bool fir
     return true;
 }
 
-template <int B, bool PRIMARY, bool TRANSP, bool CULL, int SS = kSlotStride, bool ACHRO = false>
+// AREA: every light displaced by `ls` for this lane (shade AREA); generic path only (no PRIMARY, no CULL, no masks).
+template <int B, bool PRIMARY, bool TRANSP, bool CULL, int SS = kSlotStride, bool ACHRO = false, bool AREA = false>
 __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t cone,
                                     uint32_t* seg, uint32_t* shadow, double* slot, int* mslot,
-                                    LevelMasks lm = LevelMasks{-1}) {
+                                    LevelMasks lm = LevelMasks{-1}, LightShift ls = LightShift{0.0, 0.0}) {
+    static_assert(!(AREA && (PRIMARY || CULL || ACHRO)), "area lights take the generic path");
     const DevScene* S = V.S;
     int levels = 0;
     Ray r;
@@ -1753,7 +1798,8 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
                     ndsl[2 * SS] = nd.z;
                     asm volatile("" ::: "memory");          // keep it in LDS across the light loop
                 }
-                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO>(V, true, p, n, mat, ks, skip, psl, &lm, B + lvl * V.nl);
+                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA>(V, true, p, n, mat, ks, skip, psl, &lm,
+                                                                         B + lvl * V.nl, ls);
                 if ((kPark || RT_PARK_NU) && lvl < B) {
                     asm volatile("" ::: "memory");
                     nd = mk(ndsl[0], ndsl[SS], ndsl[2 * SS]);
@@ -1803,9 +1849,10 @@ struct TreeNode {
     int state;                         // 0: transmitted child next, 1: reflected child next, 2: done
 };
 
-// Trace Line(a, a + d) as node k: closest hit, local colour; false on a miss.
+// Trace Line(a, a + d) as node k: closest hit, local colour; false on a miss.  AREA, ls: shade's.
+template <bool AREA = false>
 __device__ __forceinline__ bool tree_eval(const SceneView& V, d3 a, d3 d, TreeNode* node, uint32_t* nseg,
-                                          uint32_t* nsh) {
+                                          uint32_t* nsh, LightShift ls = LightShift{0.0, 0.0}) {
     Ray r;
     r.p0 = a;
     set_dir(&r, d, unit(d));
@@ -1819,7 +1866,7 @@ __device__ __forceinline__ bool tree_eval(const SceneView& V, d3 a, d3 d, TreeNo
     surface(V, kind, p, r.u, &n, &mat, &pe);
     const d3 rd = sub(pe, p);                               // reflectedRay = Line(p, p + r)
     const double ks = fabs(dot(r.u, unit(rd)));             // |u . reflectedRay.direction()|
-    node->acc = shade<true, false>(V, true, p, n, mat, ks);
+    node->acc = shade<true, false, false, 256, false, AREA>(V, true, p, n, mat, ks, -1, nullptr, nullptr, 0, ls);
     *nsh += V.nl;
     node->p = p;
     node->rd = rd;
@@ -1829,12 +1876,13 @@ __device__ __forceinline__ bool tree_eval(const SceneView& V, d3 a, d3 d, TreeNo
     return true;
 }
 
-template <int B>
-__device__ __forceinline__ d3 trace_tree(const SceneView& V, d3 p0, d3 p1, uint32_t* seg, uint32_t* shadow) {
+template <int B, bool AREA = false>
+__device__ __forceinline__ d3 trace_tree(const SceneView& V, d3 p0, d3 p1, uint32_t* seg, uint32_t* shadow,
+                                         LightShift ls = LightShift{0.0, 0.0}) {
     TreeNode st[B + 1];
     uint32_t nseg = 0, nsh = 0;
     d3 col = mk(0.0, 0.0, 0.0);
-    if (tree_eval(V, p0, sub(p1, p0), &st[0], &nseg, &nsh)) {
+    if (tree_eval<AREA>(V, p0, sub(p1, p0), &st[0], &nseg, &nsh, ls)) {
         int k = 0;
         for (;;) {
             TreeNode& f = st[k];
@@ -1842,14 +1890,14 @@ __device__ __forceinline__ d3 trace_tree(const SceneView& V, d3 p0, d3 p1, uint3
                 const DevMat& M = V.S->mat[f.mat];
                 if (f.state == 0) {
                     f.state = 1;
-                    if (M.transmit && tree_eval(V, f.p, f.td, &st[k + 1], &nseg, &nsh)) {
+                    if (M.transmit && tree_eval<AREA>(V, f.p, f.td, &st[k + 1], &nseg, &nsh, ls)) {
                         ++k;
                         continue;
                     }
                 }
                 if (f.state == 1) {
                     f.state = 2;
-                    if (M.reflect && tree_eval(V, f.p, f.rd, &st[k + 1], &nseg, &nsh)) {
+                    if (M.reflect && tree_eval<AREA>(V, f.p, f.rd, &st[k + 1], &nseg, &nsh, ls)) {
                         ++k;
                         continue;
                     }

@@ -1617,6 +1617,60 @@ extern "C" int rt_render_dof(rt_ctx* c, const rt_scene* scene, const rt_camera* 
         [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }
 
+// ---- soft shadows (include/rt_api.h, ABI 10: new symbols only) ----------------------------------------------------
+// One launch of rt_soft_kernel (rt_sampled.hpp) on `stream`: the lens kernel's rays, sample (a, b) lit by point (a, b)
+// of every light's square panel.  The displacement is formed in the kernel from light_size: the context's scene record
+// is read, never written or re-uploaded, and nothing per view is kept, as rt_render_dof_dev.  No shortcut for
+// light_size 0, aperture 0 or samples 1.
+static int soft_arg_checks(const char* who, double aperture, double light_size) {
+    if (!(aperture >= 0.0) || !std::isfinite(aperture))
+        return rt_fail(RT_EINVAL, std::string(who) + ": aperture must be finite and >= 0");
+    if (!(light_size >= 0.0) || !std::isfinite(light_size))
+        return rt_fail(RT_EINVAL, std::string(who) + ": light_size must be finite and >= 0");
+    return RT_OK;
+}
+
+extern "C" int rt_render_soft_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                  double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                  uint32_t* raycount2, void* stream) {
+    int s, rc = soft_arg_checks("rt_render_soft_dev", aperture, light_size);
+    if (rc) return rc;
+    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
+    L.variant = trace_variant(c->tree, c->transparent);
+    L.stream = (hipStream_t)stream;
+    L.scene = c->d_scene;
+    L.aperture = aperture;
+    L.light_size = light_size;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    const hipError_t e = with_depth(depth, [&](auto B) { return launch_soft<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_soft_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// rt_render for a soft-shadow frame (rt_render_soft_dev into the context's device buffers, then the copies back).
+extern "C" int rt_render_soft(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                              int samples, double aperture, double light_size, float* rgba32f, uint8_t* rgba8,
+                              double* rgb64f, rt_stats* stats) {
+    int rc = sampled_host_checks("rt_render_soft", c, W, H, samples);
+    if (rc || (rc = soft_arg_checks("rt_render_soft", aperture, light_size))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    const size_t npx = (size_t)W * H;
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return rt_render_soft_dev(c, cam, W, H, depth, samples, aperture, light_size, (float*)d[0], (uint8_t*)d[1],
+                                      (double*)d[2], (uint32_t*)d[3], c->rs);
+        },
+        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
+}
+
 // ---- copy_mode 3: device-to-host frames on an SDMA engine (HSA runtime, hsa_amd_memory_async_copy_on_engine) ----
 struct SdmaAgents {
     uint32_t domain = 0, bdf = 0;

@@ -361,16 +361,16 @@ __device__ __forceinline__ void store_sampled(const RenderParams& P, size_t k, d
 }
 
 // rayTraceRay on Line(p0, p1) through the generic path: no per-tile cone or level masks, V.hits_ok as the caller set
-// it.  lds: the workgroup's trace() slots (slot_bytes(B, TRANSP, WG); unused by ray trees).  (rt_trace_rays_kernel
-// below spells the same call itself: through this helper its depth-3 FULL instance came out with other instructions.)
-template <int B, bool TRANSP, bool TREE, int WG>
-__device__ __forceinline__ d3 trace_generic(const SceneView& V, d3 p0, d3 p1, char* lds, uint32_t* seg, uint32_t* sh) {
-    if constexpr (TREE) {
-        return trace_tree<B>(V, p0, p1, seg, sh);
-    } else {
+// it.  lds: the workgroup's trace() slots (slot_bytes(B, TRANSP, WG); unused by ray trees).  AREA, ls: shade()'s (the
+// lane's lights displaced).  (rt_trace_rays_kernel spells the call itself: through this its depth-3 FULL code differed.)
+template <int B, bool TRANSP, bool TREE, int WG, bool AREA = false>
+__device__ __forceinline__ d3 trace_generic(const SceneView& V, d3 p0, d3 p1, char* lds, uint32_t* seg, uint32_t* sh,
+                                            LightShift ls = LightShift{0.0, 0.0}) {
+    if constexpr (TREE) return trace_tree<B, AREA>(V, p0, p1, seg, sh, ls);
+    else {
         double* slot = reinterpret_cast<double*>(lds) + threadIdx.x;
         int* mslot = reinterpret_cast<int*>(lds + 3 * 8 * colour_slots(B, TRANSP) * WG) + threadIdx.x;
-        return trace<B, false, TRANSP, false, WG>(V, p0, p1, ~0ull, seg, sh, slot, mslot);
+        return trace<B, false, TRANSP, false, WG, false, AREA>(V, p0, p1, ~0ull, seg, sh, slot, mslot, {-1}, ls);
     }
 }
 

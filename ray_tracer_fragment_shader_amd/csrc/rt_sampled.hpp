@@ -1,19 +1,19 @@
-// rt_sampled.hpp — the two list-free sampled kernels: S x S rays per output pixel, one per lane, reduced in the wave.
+// rt_sampled.hpp — the list-free sampled kernels: S x S rays per output pixel, one per lane, reduced in the wave.
 //
 //   rt_refine_kernel<B, TRANSP, TREE>  adaptive supersampling (rt_render_adaptive_dev, include/rt_api.h): the samples
 //                                      of the pixels on a compacted work list.
 //   rt_dof_kernel<B, TRANSP, TREE>     depth of field (rt_render_dof_dev): thin-lens rays over the whole frame.
-//
-// Both take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
+//   rt_soft_kernel<B, TRANSP, TREE>    soft shadows (rt_render_soft_dev): those rays, each lit by its own light points.
+// All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
-// the reduced pixel.  Neither has a tile of neighbouring rays from one origin, so there are no cone or level masks:
+// the reduced pixel.  None has a tile of neighbouring rays from one origin, so there are no cone or level masks:
 // the rays take the generic path (trace_generic, as rt_trace_rays_kernel) with hits_ok_from of their start.  trace()
 // reduces over the whole wave, so every lane stays active: lanes without a sample of their own trace a clamped one
 // and store nothing.
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
-// rt_adaptive.hip (rt_adaptive_b<B>.o) and rt_dof.hip (rt_dof_b<B>.o).
+// rt_adaptive.hip (rt_adaptive_b<B>.o), rt_dof.hip (rt_dof_b<B>.o) and rt_soft.hip (rt_soft_b<B>.o).
 #pragma once
 
 #include "rt_render.hpp"
@@ -92,7 +92,45 @@ __global__ __launch_bounds__(64) void rt_dof_kernel(const DevScene* __restrict__
     }
 }
 
-// A launch of either kernel.
+// Soft shadows: rt_dof_kernel's wave layout, rays and store path, and sample (a, b) also sees every light of the scene
+// displaced to
+//     (L.x + (R t_a), L.y, L.z + (R t_b)),
+// point (a, b) of a square panel of half-width R = light_size in the world xz-plane, paired with the lens point and the
+// sub-pixel point of the same (a, b).  The shift reaches shade() through trace_generic<.., AREA = true> (rt_device.hpp:
+// no light-cone records and no masks for the displaced shadow rays).  R = 0, A = 0 and S = 1 run this same code.
+// A sibling of rt_dof_kernel, not an instance of a shared body: called through one, the lens kernel's instances came
+// out with another register allocation, and they are required to compile to the code they had.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_soft_kernel(const DevScene* __restrict__ S, RenderParams P, double aperture,
+                                                     double light_size, int tile_rows, void* o32, void* o8,
+                                                     double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const d3 sp = screen_point(P, ic, j, right, upp);
+    const double inv_s = ldexp(1.0, -s);                    // t = (2 a + 1 - S) / S, exact (as rt_dof_kernel)
+    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    V.hits_ok = hits_ok_from(S, e);
+    uint32_t seg = 0, sh = 0;
+    d3 col = trace_generic<B, TRANSP, TREE, 64, true>(V, e, sp, smem, &seg, &sh,
+                                                      LightShift{light_size * ta, light_size * tb});
+    reduce_samples(s, 8, col, seg, sh);
+    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
+// A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
     hipStream_t stream;
@@ -107,20 +145,27 @@ struct SampledLaunch {
     int out_w;
     const uint32_t* count;
     const uint32_t* list;
-    // rt_dof_kernel
+    // rt_dof_kernel, rt_soft_kernel
     double aperture;                           // half-width of the lens
+    // rt_soft_kernel
+    double light_size;                         // half-width of the lights' panels
 };
 
-// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip) and rt_dof_b<B>.o (rt_dof.hip).
+// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), rt_dof_b<B>.o (rt_dof.hip) and rt_soft_b<B>.o
+// (rt_soft.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
 hipError_t launch_dof(const SampledLaunch& L);
+template <int B>
+hipError_t launch_soft(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                           \
     template <>                                         \
     hipError_t launch_refine<B>(const SampledLaunch& L); \
     template <>                                         \
-    hipError_t launch_dof<B>(const SampledLaunch& L);
+    hipError_t launch_dof<B>(const SampledLaunch& L);    \
+    template <>                                         \
+    hipError_t launch_soft<B>(const SampledLaunch& L);
 RT_DECLARE_SAMPLED(0) RT_DECLARE_SAMPLED(1) RT_DECLARE_SAMPLED(2) RT_DECLARE_SAMPLED(3)
 RT_DECLARE_SAMPLED(4) RT_DECLARE_SAMPLED(5) RT_DECLARE_SAMPLED(6) RT_DECLARE_SAMPLED(7)
 #undef RT_DECLARE_SAMPLED
@@ -147,14 +192,31 @@ hipError_t launch_refine_impl(const SampledLaunch& L) {
     });
 }
 
+// The grid of rt_dof_kernel and rt_soft_kernel: one wave per 8 x 8 tile of the sample grid.
+inline dim3 lens_grid(const RenderParams& P, int* tile_rows) {
+    const int tiles_x = (P.width + 7) / 8;
+    *tile_rows = (P.height + 7) / 8;
+    return dim3((unsigned)tiles_x, (unsigned)std::min(*tile_rows, kDofGridY),
+                (unsigned)((*tile_rows + kDofGridY - 1) / kDofGridY));
+}
+
 template <int B>
 hipError_t launch_dof_impl(const SampledLaunch& L) {
-    const int tiles_x = (L.P.width + 7) / 8, tile_rows = (L.P.height + 7) / 8;
-    const dim3 g((unsigned)tiles_x, (unsigned)std::min(tile_rows, kDofGridY),
-                 (unsigned)((tile_rows + kDofGridY - 1) / kDofGridY));
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
     return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
         hipLaunchKernelGGL((rt_dof_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
                            L.stream, L.scene, L.P, L.aperture, tile_rows, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_soft_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_soft_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.P, L.aperture, L.light_size, tile_rows, L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

@@ -157,6 +157,27 @@ class Tracer:
         bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
         return self.render_dof_into(cam, width, height, depth, samples, aperture, bufs, stream)
 
+    # --------------------------------------------------------------------------------------- soft shadows
+    def render_soft_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int,
+                         aperture: float, light_size: float, bufs: dict,
+                         stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_soft_dev into alloc_ss() buffers (full frames): the rays of render_dof_into(), sample (a, b)
+        lit by point (a, b) of every light's square panel of half-width `light_size` in the world xz-plane;
+        asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_soft_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
+                                               float(aperture), float(light_size), _ptr(bufs.get("rgba32f")),
+                                               _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")),
+                                               _ptr(bufs.get("raycount")), ctypes.c_void_p(st.cuda_stream)),
+                  "rt_render_soft_dev")
+        return bufs
+
+    def render_soft(self, cam, width, height, depth, samples, aperture, light_size, rgba32f=True, rgba8=False,
+                    rgb64f=False, raycount=False, stream=None):
+        """-> the buffers of alloc_ss() (the keys of render_ss())."""
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_soft_into(cam, width, height, depth, samples, aperture, light_size, bufs, stream)
+
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):
         """rt_render_dev_packed: the float image in float_format (RT_PIXEL_RGBA32F / GRAY32F) and the byte
