@@ -50,6 +50,19 @@ int rt_diag_kernel_resources(int depth, int variant, int* vgprs, int* scratch_by
 /* Workgroups per CU the HIP runtime allows the render kernel (depth, variant) with lds_bytes of dynamic LDS. */
 int rt_diag_kernel_occupancy(int depth, int variant, int lds_bytes, int* blocks_per_cu);
 
+/* Which render-kernel instance a frame runs: the library's one selector, called with the facts it decides on.  No
+ * context, no device.  The scene kind (tree, transparent, n_padded spheres rounded up to 4, the stride n_stride of
+ * its per-sphere arrays, achromatic, lds_bytes of its record), the context's knobs (use_lds: RT_SCENE_IN_LDS,
+ * wg_staging: RT_WG_STAGING, min_waves: RT_MIN_WAVES, 5 by default, achro_off: RT_ACHRO_OFF), the depth (0..7), the
+ * output mode (0 RGBA images, 1 packed GRAY / RGB formats, 2 supersampled) and level_mask (1: not the frame itself but
+ * the launch that writes a fast scene's level masks behind its calibration render).  out[0..10]: the instance's
+ * kernel template (0 rt_render_kernel, 1 rt_render_kernel_sg, 2 rt_render_kernel_sg8) and its template arguments
+ * LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS; out[11] the launch's dynamic LDS bytes; out[12] the tile
+ * width in pixels.  RT_EINVAL for bad arguments, and (out written) when the build has no such instance. */
+int rt_diag_render_route(int tree, int transparent, int n_padded, int n_stride, int achromatic, int lds_bytes,
+                         int use_lds, int wg_staging, int min_waves, int achro_off, int depth, int mode, int level_mask,
+                         int out[13]);
+
 /* How this context's last rt_render_packed / rt_render_packed_async frame reached host memory: *mode 0 the copy
  * kernel on the copy stream, 1 behind the render on the render stream (copy kernel, or hipMemcpyAsync for pageable
  * memory), 2 stored by the render straight into mapped pinned memory, 3 an SDMA engine, -1 no packed frame yet;

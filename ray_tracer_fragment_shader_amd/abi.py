@@ -200,9 +200,11 @@ SIGNATURES = {
     "rt_diag_kernel_resources": (c_int, [c_int, c_int, _P(c_int), _P(c_int)]),
     "rt_diag_kernel_occupancy": (c_int, [c_int, c_int, c_int, _P(c_int)]),
     "rt_diag_copy_path": (c_int, [c_void_p, _P(c_int), _P(c_int)]),
+    "rt_diag_render_route": (c_int, [c_int] * 13 + [_P(c_int)]),
 }
 
-_DIAG = {"rt_diag_tile_order", "rt_diag_kernel_resources", "rt_diag_kernel_occupancy", "rt_diag_copy_path"}
+_DIAG = {"rt_diag_tile_order", "rt_diag_kernel_resources", "rt_diag_kernel_occupancy", "rt_diag_copy_path",
+         "rt_diag_render_route"}
 _lib = None
 
 

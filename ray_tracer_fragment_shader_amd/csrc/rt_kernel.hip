@@ -974,6 +974,287 @@ static int render_params(const rt_ctx* c, const rt_camera* cam, int W, int H, in
 static bool float_format(int f) { return f == RT_PIXEL_RGBA32F || f == RT_PIXEL_GRAY32F; }
 static bool byte_format(int f) { return f == RT_PIXEL_RGBA8 || f == RT_PIXEL_RGB8 || f == RT_PIXEL_GRAY8; }
 
+// render_route() (rt_render.hpp) for this context's scene kind and A/B knobs.
+static RenderRoute ctx_route(const rt_ctx* c, int depth, int mode, bool level_mask) {
+    return render_route(RouteScene{c->tree, c->transparent, c->n_padded, c->n_stride, c->achromatic, c->lds_bytes},
+                        RouteKnobs{c->use_lds != 0, c->wg_staging != 0, c->min_waves, c->achro_off}, depth, mode, level_mask);
+}
+
+// One render_dev_impl call: what it was asked for, and what its steps (below, in the order they run) decide.
+struct RenderJob {
+    const rt_camera* cam;
+    int W, H, depth;
+    const rt_rows* rows;
+    void *pf, *p8;                                      // the outputs, each nullable
+    double* o64;
+    uint32_t* orc;
+    hipStream_t st;
+    int ss_log2;
+    RenderParams P;                                     // step 1
+    int mode;                                           // kModePlain / kModePacked / kModeSS
+    RenderRoute route;                                  // the kernel instance, its LDS bytes and tile width
+    int tiles_x, tiles_y;                               // step 2
+    size_t tiles;
+    bool capturing, cull_kernel;                        // (cull_kernel: the render kernel itself writes the level masks)
+    int lm_stride;                                      // level-mask slots per tile (0: none)
+    rt_ctx::ViewKey key;
+    bool calibrate, cone_calib, lm_calib;               // this render times its tiles / records cone / level masks
+    bool prepare;                                       // ... writes the per-eye scene records first
+};
+
+// Step 1: the kernel parameters, the pixel formats and the output mode; the kernel instance of the frame.
+static int render_job_params(rt_ctx* c, int fmt_f, int fmt_8, RenderJob& J) {
+    RenderParams& P = J.P;
+    int rc = render_params(c, J.cam, J.W, J.H, J.depth, J.rows, &P);
+    if (rc) return rc;
+    const bool ss = J.ss_log2 >= 0;
+    if (ss) {
+        P.ss_log2 = J.ss_log2;
+        P.wg_staging = 0;                           // one-wave direct-store instances only
+    }
+    if ((J.pf && !float_format(fmt_f)) || (J.p8 && !byte_format(fmt_8)))
+        return rt_fail(RT_EINVAL, "render: bad pixel format for the float / byte image");
+    if (((J.pf && fmt_f == RT_PIXEL_GRAY32F) || (J.p8 && fmt_8 == RT_PIXEL_GRAY8)) && !c->achromatic)
+        return rt_fail(RT_EINVAL, "render: GRAY pixel formats need an achromatic scene (rt_scene_achromatic)");
+    P.fmt_f = fmt_f == RT_PIXEL_GRAY32F ? kFmtF_GRAY : kFmtF_RGBA;
+    P.fmt_8 = fmt_8 == RT_PIXEL_GRAY8 ? kFmt8_GRAY : fmt_8 == RT_PIXEL_RGB8 ? kFmt8_RGB : kFmt8_RGBA;
+    const bool packed = (J.pf && P.fmt_f != kFmtF_RGBA) || (J.p8 && P.fmt_8 != kFmt8_RGBA);
+    if (packed) P.wg_staging = 0;                   // the LDS-staged stores (A/B variant) write RGBA only
+    J.mode = ss ? kModeSS : packed ? kModePacked : kModePlain;
+    // One-wave workgroups (8 x 8 tiles) by default: measured faster than 256-thread workgroups (32 x 8
+    // tiles) at every config (c2 -1%, c3 -3%, c5 -12%: a finished wave's slot is refilled without
+    // waiting for three siblings).  The A/B instances that share a workgroup-wide LDS copy (scene in LDS,
+    // staged row stores) keep 256 threads; packed formats and supersampling have one-wave instances only.
+    J.route = ctx_route(c, J.depth, J.mode, false);
+    return RT_OK;
+}
+
+// Step 2: the tiles, and which render of its view this is — a later one in calibrated order, one of a moving camera,
+// the calibration render, or the first (identity order).
+static int render_plan_view(rt_ctx* c, RenderJob& J) {
+    RenderParams& P = J.P;
+    const bool big = J.route.key.WG == kThreads;    // 32 x 8 tiles, four waves each
+    J.tiles_x = (J.W + J.route.tile_w - 1) / J.route.tile_w;
+    J.tiles_y = (P.local_rows + kTileH - 1) / kTileH;
+    J.tiles = (size_t)J.tiles_x * J.tiles_y;
+    P.tile_rows_n = J.tiles_y;
+    P.tiles_x = J.tiles_x;
+    // A render captured into a hipGraph must be self-contained: it always prepares its eye's data and uses
+    // the identity tile-row order (the context's order buffer belongs to whatever view it last calibrated).
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    RT_HIP(hipStreamIsCapturing(J.st, &cap));
+    J.capturing = cap != hipStreamCaptureStatusNone;
+    if (J.capturing) c->ever_captured = true;
+    J.calibrate = J.cone_calib = J.lm_calib = false;
+    // level masks per tile (opaque scenes, one-wave tiles): B ray masks + (B + 1) nl shadow masks.  The culling
+    // kernels compute them in their calibration render; for the fast kernels' scenes (< kConeMin spheres) a culling
+    // kernel writes them in a launch of its own right after the calibration render (no image outputs), and later
+    // renders skip the filter batches they rule out
+    const bool opaque_tiles = !c->tree && !c->transparent && !big && RT_WG_FAST == 64;
+    J.cull_kernel = c->n_padded >= kConeMin && opaque_tiles;
+    J.lm_stride = opaque_tiles && c->level_masks && c->cone_cache ? J.depth + (J.depth + 1) * c->n_lights : 0;
+    if (J.lm_stride > kLevelMaskSlotsMax) J.lm_stride = 0;
+    J.key = rt_ctx::ViewKey{};
+    // (dispatch records pack the tile as ty << 16 | tx)
+    if (!J.capturing && c->order_mode == 0 && J.tiles_y <= c->n_tile_rows && J.tiles_x < 65536 && J.tiles_y < 65536) {
+        // Key of the frame's work: camera, size, outputs, row plan, depth and scene generation.
+        unsigned char* kp = J.key.data();               // fixed size: no host allocation per render
+        memcpy(kp, J.cam, sizeof(rt_camera)); kp += sizeof(rt_camera);
+        // which outputs are written (and in which format) changes the rows' relative cost (an RGB64F parity
+        // render writes 24 B per pixel): each output set gets its own calibration
+        // (and a supersampled render its own: it shares the camera and size of a plain render of its sample grid,
+        // not its stores)
+        const int outs = (J.pf ? 1 : 0) | (J.p8 ? 2 : 0) | (J.o64 ? 4 : 0) | (J.orc ? 8 : 0) | (P.fmt_f << 4) |
+                         (P.fmt_8 << 6) | ((J.mode == kModeSS ? J.ss_log2 + 1 : 0) << 8);
+        const int ints[6] = {J.W, J.H, J.depth, J.tiles_x, J.tiles_y, outs};
+        memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
+        if (J.rows) memcpy(kp, J.rows, sizeof(rt_rows));
+        kp += sizeof(rt_rows);
+        memcpy(kp, &c->scene_gen, sizeof(uint64_t));
+        constexpr size_t kCam = sizeof(rt_camera);
+        const bool same_shape = c->order_valid &&
+                                memcmp(J.key.data() + kCam, c->order_key.data() + kCam, J.key.size() - kCam) == 0;
+        if (c->order_valid && J.key == c->order_key) {
+            P.disp = c->d_disp;
+            // (the cached masks hold one mask per one-wave 8 x 8 tile: the 256-thread A/B instances never read them)
+            P.cone_use = c->cone_valid && !big ? 1 : 0;
+            if (c->lmask_valid && J.lm_stride > 0 && c->lmask_stride == J.lm_stride) {   // this view's level masks
+                P.lmask_in = c->d_lmask;
+                P.lmask_stride = J.lm_stride;
+            }
+        } else if (same_shape && c->moving_order) {
+            P.disp = c->d_disp;                         // another camera: the last calibrated order, its own masks
+            if (c->recalibrate > 0 && ++c->stale >= c->recalibrate) {   // ... re-timed every recalibrate-th render
+                J.calibrate = true;
+                c->order_valid = false;
+            }
+        } else if (c->seen_valid && J.key == c->seen_key) {   // (by default a moving camera's views come here: the
+                                                              // first render of a view in identity order, its second
+                                                              // the calibration — a camera that stops is calibrated)
+            J.calibrate = true;                         // calibration render (identity order)
+            c->order_valid = false;                     // rt_disp_kernel rewrites d_disp below
+            // the calibration records one mask per tile from lane 0 of its wave: one-wave workgroups only
+            J.cone_calib = c->cone_cache && c->n_padded >= kPrimaryConeMin && !c->tree && !c->transparent && !big &&
+                           RT_WG_FAST == 64;
+            J.lm_calib = J.cone_calib && J.lm_stride > 0;
+        } else {
+            c->seen_key = J.key;                        // first render of this view: identity order
+            c->seen_valid = true;
+        }
+    }
+    J.prepare = J.capturing || c->ever_captured || !c->eye_valid || memcmp(c->eye, J.cam->eye, sizeof(c->eye)) != 0;
+    return RT_OK;
+}
+
+// Step 3: order this render against the renders queued on other streams (a captured render carries its own prepare
+// launch and touches no view state).
+static int render_order_streams(rt_ctx* c, const RenderJob& J) {
+    if (J.capturing) return RT_OK;
+    // read-after-write / write-after-write: the last write of the view state was queued on another stream
+    if (c->view_rec && c->view_st != J.st) RT_HIP(hipStreamWaitEvent(J.st, c->view_ev, 0));
+    if (J.prepare || J.calibrate) {
+        // write-after-read: renders queued on other streams may still read what this render rewrites (or frees)
+        if ((c->readers && (c->readers_multi || c->reader_st != J.st)) || (J.calibrate && J.tiles > c->view_cap) ||
+            (J.lm_calib && J.tiles * (size_t)J.lm_stride > c->lmask_cap))
+            RT_HIP(hipDeviceSynchronize());
+        c->readers = c->readers_multi = false;      // same-stream renders are ordered before the rewrite
+    }
+    if (!c->readers) {                              // this render reads the view state on st
+        c->readers = true;
+        c->reader_st = J.st;
+    } else if (c->reader_st != J.st) {
+        c->readers_multi = true;
+    }
+    return RT_OK;
+}
+
+// Step 4 (calibration renders): the buffers the render writes every tile's wave time and, a static view's, its cone
+// and level masks to.  They grow here: step 3 drained the device.
+static void render_grow_calibration(rt_ctx* c, RenderJob& J) {
+    RenderParams& P = J.P;
+    c->cone_valid = false;
+    c->lmask_valid = false;
+    if (!rt_grow_view_bufs(c, J.tiles)) {           // out of memory: identity order, masks in the kernel
+        J.calibrate = J.cone_calib = J.lm_calib = false;
+        P.disp = nullptr;
+        P.cone_use = 0;
+    } else {
+        P.tile_cost = c->d_tile_cost;
+        if (J.cone_calib) P.cone_out = c->d_cone_tile;
+    }
+    if (J.lm_calib && J.tiles * (size_t)J.lm_stride > c->lmask_cap) {
+        if (c->d_lmask) (void)hipFree(c->d_lmask);
+        c->d_lmask = nullptr;
+        c->lmask_cap = 0;
+        if (hipMalloc(&c->d_lmask, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t)) == hipSuccess)
+            c->lmask_cap = J.tiles * (size_t)J.lm_stride;
+        else
+            (void)hipGetLastError();                // out of memory: the masks stay in the kernel
+    }
+    if (J.lm_calib && c->d_lmask) {
+        if (J.cull_kernel) {                        // (fast scenes: the level-mask launch of step 6 writes them)
+            P.lmask_out = c->d_lmask;
+            P.lmask_stride = J.lm_stride;
+        }
+    } else {
+        J.lm_calib = false;
+    }
+}
+
+// Step 5: the primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
+// that carry their own prepare launch exist).
+static int render_prepare_eye(rt_ctx* c, const RenderJob& J) {
+    c->eye_valid = false;
+    dim3 pg((unsigned)((std::max(c->n_padded, 1) + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(rt_prepare_kernel, pg, dim3(kThreads), 0, J.st, c->d_scene, J.cam->eye[0], J.cam->eye[1],
+                       J.cam->eye[2]);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_prepare_kernel: ") + hipGetErrorString(e));
+    memcpy(c->eye, J.cam->eye, sizeof(c->eye));
+    c->eye_valid = true;
+    return RT_OK;
+}
+
+// Step 6: the render, and behind a fast scene's calibration render the launch that writes its level masks.
+static int render_launch(rt_ctx* c, const RenderJob& J) {
+    RenderLaunch L;
+    L.key = J.route.key;
+    L.grid = dim3((unsigned)J.tiles_x, (unsigned)std::min(J.tiles_y, kGridY), (unsigned)((J.tiles_y + kGridY - 1) / kGridY));
+    L.lds = (size_t)J.route.lds;
+    L.stream = J.st;
+    L.scene = c->d_scene;
+    L.P = J.P;
+    L.o32 = J.pf;
+    L.o8 = J.p8;
+    L.o64 = J.o64;
+    L.orc = J.orc;
+    hipError_t e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
+    if (J.lm_calib && !J.cull_kernel) {
+        // a fast kernel's scene: the level masks of the view from a culling kernel that stores nothing else (identity
+        // order, its own primary cone masks, no image) — stream-ordered before the renders that read them
+        const RenderRoute mask = ctx_route(c, J.depth, J.mode, true);
+        RenderLaunch M = L;
+        M.key = mask.key;
+        M.lds = (size_t)mask.lds;
+        M.P.lmask_out = c->d_lmask;
+        M.P.lmask_in = nullptr;
+        M.P.lmask_stride = J.lm_stride;
+        M.P.disp = nullptr;
+        M.P.cone_use = 0;
+        M.P.cone_out = nullptr;
+        M.P.tile_cost = nullptr;
+        M.o32 = M.o8 = nullptr;
+        M.o64 = nullptr;
+        M.orc = nullptr;
+        e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(M); });
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("level-mask launch: ") + hipGetErrorString(e));
+    }
+    return RT_OK;
+}
+
+// Step 7 (calibration renders): the dispatch table of this view, stream-ordered after the render that wrote the tile
+// times; only then does the context call the view calibrated.
+static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
+    const int tiles = (int)J.tiles, tiles_x = J.tiles_x, tiles_y = J.tiles_y;
+    const hipStream_t st = J.st;
+    hipError_t e;
+    const dim3 tg((unsigned)((J.tiles + 255) / 256));
+    const uint64_t* cones = J.cone_calib ? c->d_cone_tile : nullptr;
+    if (c->order_policy == 1) {                     // tiles longest first
+        hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, c->d_sort_in, (int)tiles);
+        size_t tmp = c->sort_tmp_bytes;
+        e = hipcub::DeviceRadixSort::SortPairsDescending(c->d_sort_tmp, tmp, c->d_tile_cost, c->d_sort_keys,
+                                                         c->d_sort_in, c->d_sort_out, (int)tiles, 0, 32, st);
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, c->d_sort_out, cones, tiles_x, tiles_y,
+                           c->d_disp);
+    } else {                                        // tile rows longest first
+        hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, c->d_tile_cost, tiles_x,
+                           c->d_row_cost);
+        hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, c->d_row_cost, tiles_y, c->d_tile_rows);
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, c->d_tile_rows, nullptr, cones, tiles_x, tiles_y,
+                           c->d_disp);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("dispatch table: ") + hipGetErrorString(e));
+    c->order_key = J.key;                           // only once the order kernel is queued
+    c->order_valid = true;
+    c->cone_valid = J.cone_calib;
+    c->lmask_valid = J.lm_calib;
+    c->lmask_stride = J.lm_calib ? J.lm_stride : 0;
+    c->stale = 0;
+    return RT_OK;
+}
+
+// Step 8: later renders on other streams wait for this render's writes of the view state.
+static int render_record_view(rt_ctx* c, const RenderJob& J) {
+    RT_HIP(hipEventRecord(c->view_ev, J.st));
+    c->view_st = J.st;
+    c->view_rec = true;
+    return RT_OK;
+}
+
 // The device render behind rt_render_dev / rt_render_dev_packed: the float image (fmt_f) and the byte image
 // (fmt_8) in their formats, the FP64 colour and the ray counters, each nullable.
 // ss_log2 >= 0 (rt_render_ss_dev): cam, W, H and rows describe the SAMPLE grid of a supersampled render with
@@ -983,257 +1264,17 @@ static bool byte_format(int f) { return f == RT_PIXEL_RGBA8 || f == RT_PIXEL_RGB
 static int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
                            int fmt_f, void* pf, int fmt_8, void* p8, double* rgb64f, uint32_t* raycount,
                            void* stream, int ss_log2 = -1) {
-    RenderParams P;
-    int rc = render_params(c, cam, W, H, depth, rows, &P);
-    if (rc) return rc;
-    const bool ss = ss_log2 >= 0;
-    if (ss) {
-        P.ss_log2 = ss_log2;
-        P.wg_staging = 0;                           // one-wave direct-store instances only
-    }
-    if ((pf && !float_format(fmt_f)) || (p8 && !byte_format(fmt_8)))
-        return rt_fail(RT_EINVAL, "render: bad pixel format for the float / byte image");
-    if (((pf && fmt_f == RT_PIXEL_GRAY32F) || (p8 && fmt_8 == RT_PIXEL_GRAY8)) && !c->achromatic)
-        return rt_fail(RT_EINVAL, "render: GRAY pixel formats need an achromatic scene (rt_scene_achromatic)");
-    P.fmt_f = fmt_f == RT_PIXEL_GRAY32F ? kFmtF_GRAY : kFmtF_RGBA;
-    P.fmt_8 = fmt_8 == RT_PIXEL_GRAY8 ? kFmt8_GRAY : fmt_8 == RT_PIXEL_RGB8 ? kFmt8_RGB : kFmt8_RGBA;
-    const bool packed = (pf && P.fmt_f != kFmtF_RGBA) || (p8 && P.fmt_8 != kFmt8_RGBA);
-    if (packed) P.wg_staging = 0;                   // the LDS-staged stores (A/B variant) write RGBA only
-    if (P.local_rows == 0) return RT_OK;
+    RenderJob J{cam, W, H, depth, rows, pf, p8, rgb64f, raycount, (hipStream_t)stream, ss_log2};
+    int rc = render_job_params(c, fmt_f, fmt_8, J);                             // 1
+    if (rc || J.P.local_rows == 0) return rc;
     RT_HIP(hipSetDevice(c->device));
-    // One-wave workgroups (8 x 8 tiles) by default: measured faster than 256-thread workgroups (32 x 8
-    // tiles) at every config (c2 -1%, c3 -3%, c5 -12%: a finished wave's slot is refilled without
-    // waiting for three siblings).  The A/B variants that share a workgroup-wide LDS copy (scene in LDS,
-    // staged row stores) keep 256 threads.
-    const bool big = !packed && !ss && (c->use_lds || c->wg_staging);    // packed formats, supersampling: one-wave variants only
-    const int tw = big ? kTileW : RT_WG_FAST / 8;
-    const int tiles_x = (W + tw - 1) / tw;
-    const int tiles_y = (P.local_rows + kTileH - 1) / kTileH;
-    P.tile_rows_n = tiles_y;
-    P.tiles_x = tiles_x;
-    hipStream_t st = (hipStream_t)stream;
-    // A render captured into a hipGraph must be self-contained: it always prepares its eye's data and uses
-    // the identity tile-row order (the context's order buffer belongs to whatever view it last calibrated).
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    RT_HIP(hipStreamIsCapturing(st, &cap));
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (capturing) c->ever_captured = true;
-    bool calibrate = false, cone_calib = false, lm_calib = false;
-    // level masks per tile (opaque scenes, one-wave tiles): B ray masks + (B + 1) nl shadow masks.  The culling
-    // kernels compute them in their calibration render; for the fast kernels' scenes (< kConeMin spheres) a culling
-    // kernel writes them in a launch of its own right after the calibration render (no image outputs), and later
-    // renders skip the filter batches they rule out
-    const bool opaque_tiles = !c->tree && !c->transparent && !big && RT_WG_FAST == 64;
-    const bool cull_kernel = c->n_padded >= kConeMin && opaque_tiles;
-    int lm_stride = opaque_tiles && c->level_masks && c->cone_cache ? depth + (depth + 1) * c->n_lights : 0;
-    if (lm_stride > kLevelMaskSlotsMax) lm_stride = 0;
-    rt_ctx::ViewKey key{};
-    // (dispatch records pack the tile as ty << 16 | tx)
-    if (!capturing && c->order_mode == 0 && tiles_y <= c->n_tile_rows && tiles_x < 65536 && tiles_y < 65536) {
-        // Key of the frame's work: camera, size, outputs, row plan, depth and scene generation.
-        unsigned char* kp = key.data();                 // fixed size: no host allocation per render
-        memcpy(kp, cam, sizeof(rt_camera)); kp += sizeof(rt_camera);
-        // which outputs are written (and in which format) changes the rows' relative cost (an RGB64F parity
-        // render writes 24 B per pixel): each output set gets its own calibration
-        // (and a supersampled render its own: it shares the camera and size of a plain render of its sample grid,
-        // not its stores)
-        const int outs = (pf ? 1 : 0) | (p8 ? 2 : 0) | (rgb64f ? 4 : 0) | (raycount ? 8 : 0) | (P.fmt_f << 4) |
-                         (P.fmt_8 << 6) | ((ss ? ss_log2 + 1 : 0) << 8);
-        const int ints[6] = {W, H, depth, tiles_x, tiles_y, outs};
-        memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
-        if (rows) memcpy(kp, rows, sizeof(rt_rows));
-        kp += sizeof(rt_rows);
-        memcpy(kp, &c->scene_gen, sizeof(uint64_t));
-        constexpr size_t kCam = sizeof(rt_camera);
-        const bool same_shape = c->order_valid &&
-                                memcmp(key.data() + kCam, c->order_key.data() + kCam, key.size() - kCam) == 0;
-        if (c->order_valid && key == c->order_key) {
-            P.disp = c->d_disp;
-            // (the cached masks hold one mask per one-wave 8 x 8 tile: the 256-thread A/B variants never read them)
-            P.cone_use = c->cone_valid && !big ? 1 : 0;
-            if (c->lmask_valid && lm_stride > 0 && c->lmask_stride == lm_stride) {   // this view's level masks
-                P.lmask_in = c->d_lmask;
-                P.lmask_stride = lm_stride;
-            }
-        } else if (same_shape && c->moving_order) {
-            P.disp = c->d_disp;                         // another camera: the last calibrated order, its own masks
-            if (c->recalibrate > 0 && ++c->stale >= c->recalibrate) {   // ... re-timed every recalibrate-th render
-                calibrate = true;
-                c->order_valid = false;
-            }
-        } else if (c->seen_valid && key == c->seen_key) {   // (by default a moving camera's views come here: the
-                                                            // first render of a view in identity order, its second
-                                                            // the calibration — a camera that stops is calibrated)
-            calibrate = true;                           // calibration render (identity order)
-            c->order_valid = false;                     // rt_disp_kernel rewrites d_disp below
-            // the calibration records one mask per tile from lane 0 of its wave: one-wave workgroups only
-            cone_calib = c->cone_cache && c->n_padded >= kPrimaryConeMin && !c->tree && !c->transparent && !big &&
-                         RT_WG_FAST == 64;
-            lm_calib = cone_calib && lm_stride > 0;
-        } else {
-            c->seen_key = key;                          // first render of this view: identity order
-            c->seen_valid = true;
-        }
-    }
-    const bool prepare = capturing || c->ever_captured || !c->eye_valid || memcmp(c->eye, cam->eye, sizeof(c->eye)) != 0;
-    const size_t tiles = (size_t)tiles_x * tiles_y;
-    if (!capturing) {                                   // (a captured render carries its own prepare launch)
-        // read-after-write / write-after-write: the last write of the view state was queued on another stream
-        if (c->view_rec && c->view_st != st) RT_HIP(hipStreamWaitEvent(st, c->view_ev, 0));
-        if (prepare || calibrate) {
-            // write-after-read: renders queued on other streams may still read what this render rewrites (or frees)
-            if ((c->readers && (c->readers_multi || c->reader_st != st)) || (calibrate && tiles > c->view_cap) ||
-                (lm_calib && tiles * (size_t)lm_stride > c->lmask_cap))
-                RT_HIP(hipDeviceSynchronize());
-            c->readers = c->readers_multi = false;      // same-stream renders are ordered before the rewrite
-        }
-        if (!c->readers) {                              // this render reads the view state on st
-            c->readers = true;
-            c->reader_st = st;
-        } else if (c->reader_st != st) {
-            c->readers_multi = true;
-        }
-    }
-    if (calibrate) {
-        // the calibration render writes every tile's wave time (and, a static view's, its cone mask); the buffers
-        // grow here (the device was drained above)
-        c->cone_valid = false;
-        c->lmask_valid = false;
-        if (!rt_grow_view_bufs(c, tiles)) {             // out of memory: identity order, masks in the kernel
-            calibrate = cone_calib = lm_calib = false;
-            P.disp = nullptr;
-            P.cone_use = 0;
-        } else {
-            P.tile_cost = c->d_tile_cost;
-            if (cone_calib) P.cone_out = c->d_cone_tile;
-        }
-        if (lm_calib && tiles * (size_t)lm_stride > c->lmask_cap) {     // (the device was drained above)
-            if (c->d_lmask) (void)hipFree(c->d_lmask);
-            c->d_lmask = nullptr;
-            c->lmask_cap = 0;
-            if (hipMalloc(&c->d_lmask, tiles * (size_t)lm_stride * sizeof(uint64_t)) == hipSuccess)
-                c->lmask_cap = tiles * (size_t)lm_stride;
-            else
-                (void)hipGetLastError();                // out of memory: the masks stay in the kernel
-        }
-        if (lm_calib && c->d_lmask) {
-            if (cull_kernel) {                          // (fast scenes: the mask launch below writes them)
-                P.lmask_out = c->d_lmask;
-                P.lmask_stride = lm_stride;
-            }
-        } else {
-            lm_calib = false;
-        }
-    }
-    const dim3 grid((unsigned)tiles_x, (unsigned)std::min(tiles_y, kGridY), (unsigned)((tiles_y + kGridY - 1) / kGridY));
-    hipError_t e;
-    // Primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
-    // that carry their own prepare launch exist).
-    if (prepare) {
-        c->eye_valid = false;
-        dim3 pg((unsigned)((std::max(c->n_padded, 1) + kThreads - 1) / kThreads));
-        hipLaunchKernelGGL(rt_prepare_kernel, pg, dim3(kThreads), 0, st, c->d_scene, cam->eye[0], cam->eye[1],
-                           cam->eye[2]);
-        e = hipGetLastError();
-        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_prepare_kernel: ") + hipGetErrorString(e));
-        memcpy(c->eye, cam->eye, sizeof(c->eye));
-        c->eye_valid = true;
-    }
-    RenderLaunch L;
-    // achromatic opaque scenes: the one-channel instances (rt_device.hpp shade ACHRO; RT_ACHRO_OFF=1 for A/B)
-    L.achro = c->achromatic && !c->transparent && !c->tree && !c->achro_off && !ss;
-    L.grid = grid;
-    L.stream = st;
-    L.scene = c->d_scene;
-    L.P = P;
-    L.o32 = pf;
-    L.o8 = p8;
-    L.o64 = rgb64f;
-    L.orc = raycount;
-    const bool cull = c->n_padded >= kConeMin, mw5 = c->min_waves >= 5 && depth <= 3;
-    if (c->tree) {
-        L.variant = kVarTree;
-        L.lds = 0;
-    } else if (c->transparent) {
-        L.variant = kVarTransp;
-        L.lds = slot_bytes(depth, true, 64);
-    } else if (c->use_lds) {
-        L.variant = kVarLds;
-        L.lds = c->lds_bytes + slot_bytes(depth, false);
-    } else if (c->wg_staging) {
-        L.variant = mw5 ? kVarStaging : kVarStagingAnyW;
-        L.lds = 4096 + 6144 + 1024 + 1024 + slot_bytes(depth, false);
-    } else {
-        // >= kConeMin spheres: the wave-culling variant (secondary and shadow rays, rt_device.hpp CULL).
-        L.variant = cull ? (mw5 ? kVarCull : kVarCullAnyW) : (mw5 ? kVarFast : kVarFastAnyW);
-        L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
-    }
-    if (packed) {                                       // the instances with runtime pixel-format stores
-        if (c->tree) L.variant = kVarTreePacked;
-        else if (c->transparent) L.variant = kVarTranspPacked;
-        else L.variant = cull ? kVarCullPacked : kVarFastPacked;
-        if (!c->tree && !c->transparent) L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
-    }
-    if (ss) {                                           // the supersampled instances, one per scene kind
-        if (c->tree) L.variant = kVarTreeSS;
-        else if (c->transparent) L.variant = kVarTranspSS;
-        else L.variant = cull ? kVarCullSS : kVarFastSS;
-        if (!c->tree && !c->transparent) L.lds = slot_bytes(depth, false, RT_WG_FAST, cull);
-    }
-    e = with_depth(depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
-    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
-    if (lm_calib && !cull_kernel) {
-        // a fast kernel's scene: the level masks of the view from a culling kernel that stores nothing else (identity
-        // order, its own primary cone masks, no image) — stream-ordered before the renders that read them
-        RenderLaunch M = L;
-        M.P.lmask_out = c->d_lmask;
-        M.P.lmask_in = nullptr;
-        M.P.lmask_stride = lm_stride;
-        M.P.disp = nullptr;
-        M.P.cone_use = 0;
-        M.P.cone_out = nullptr;
-        M.P.tile_cost = nullptr;
-        M.o32 = M.o8 = nullptr;
-        M.o64 = nullptr;
-        M.orc = nullptr;
-        M.variant = mw5 ? kVarCull : kVarCullAnyW;
-        M.lds = slot_bytes(depth, false, RT_WG_FAST, true);
-        e = with_depth(depth, [&](auto B) { return launch_render<decltype(B)::value>(M); });
-        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("level-mask launch: ") + hipGetErrorString(e));
-    }
-    if (calibrate) {
-        // the dispatch table of this view (stream-ordered after the calibration render, which wrote the tile times)
-        const dim3 tg((unsigned)((tiles + 255) / 256));
-        const uint64_t* cones = cone_calib ? c->d_cone_tile : nullptr;
-        if (c->order_policy == 1) {                     // tiles longest first
-            hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, c->d_sort_in, (int)tiles);
-            size_t tmp = c->sort_tmp_bytes;
-            e = hipcub::DeviceRadixSort::SortPairsDescending(c->d_sort_tmp, tmp, c->d_tile_cost, c->d_sort_keys,
-                                                             c->d_sort_in, c->d_sort_out, (int)tiles, 0, 32, st);
-            if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
-            hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, c->d_sort_out, cones, tiles_x, tiles_y,
-                               c->d_disp);
-        } else {                                        // tile rows longest first
-            hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, c->d_tile_cost, tiles_x,
-                               c->d_row_cost);
-            hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, c->d_row_cost, tiles_y, c->d_tile_rows);
-            hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, c->d_tile_rows, nullptr, cones, tiles_x, tiles_y,
-                               c->d_disp);
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("dispatch table: ") + hipGetErrorString(e));
-        c->order_key = key;                             // only once the order kernel is queued
-        c->order_valid = true;
-        c->cone_valid = cone_calib;
-        c->lmask_valid = lm_calib;
-        c->lmask_stride = lm_calib ? lm_stride : 0;
-        c->stale = 0;
-    }
-    if ((prepare || calibrate) && !capturing) {
-        RT_HIP(hipEventRecord(c->view_ev, st));         // later renders on other streams wait for these writes
-        c->view_st = st;
-        c->view_rec = true;
-    }
+    if ((rc = render_plan_view(c, J))) return rc;                               // 2
+    if ((rc = render_order_streams(c, J))) return rc;                           // 3
+    if (J.calibrate) render_grow_calibration(c, J);                             // 4
+    if (J.prepare && (rc = render_prepare_eye(c, J))) return rc;                // 5
+    if ((rc = render_launch(c, J))) return rc;                                  // 6
+    if (J.calibrate && (rc = render_build_dispatch(c, J))) return rc;           // 7
+    if ((J.prepare || J.calibrate) && !J.capturing) return render_record_view(c, J);   // 8
     return RT_OK;
 }
 
@@ -2142,13 +2183,42 @@ extern "C" int rt_diag_tile_order(rt_ctx* c, int mode) {
     return RT_OK;
 }
 
-// Diagnostics (include/rt_diag.h): registers and scratch of the render kernel instance rt_render_dev
-// launches for `depth` and scene kind `variant` (0 spheres + board, 1 >= kConeMin spheres (CULL),
-// 2 meshes / transparency, 3 ray trees) — the tests assert the default instances never spill.
+// Diagnostics (include/rt_diag.h): render_route() itself, no context and no device.  out: the key's fields in
+// RenderKey's order, the launch's LDS bytes, the tile width.
+extern "C" int rt_diag_render_route(int tree, int transparent, int n_padded, int n_stride, int achromatic,
+                                    int lds_bytes, int use_lds, int wg_staging, int min_waves, int achro_off, int depth,
+                                    int mode, int level_mask, int out[13]) {
+    if (depth < 0 || depth > RT_MAX_DEPTH || mode < kModePlain || mode > kModeSS || n_padded < 0 || !out)
+        return rt_fail(RT_EINVAL, "rt_diag_render_route: bad arguments");
+    const RenderRoute r = render_route(RouteScene{tree != 0, transparent != 0, n_padded, n_stride, achromatic != 0, lds_bytes},
+                                       RouteKnobs{use_lds != 0, wg_staging != 0, min_waves, achro_off != 0}, depth, mode,
+                                       level_mask != 0);
+    const RenderKey& k = r.key;
+    const int v[13] = {k.kernel, k.LDS, k.MINW, k.TRANSP, k.CULL, k.WG, k.TREE, k.PACKED, k.FIX64, k.ACHRO, k.SS, r.lds,
+                       r.tile_w};
+    memcpy(out, v, sizeof(v));
+    if (!with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(k); }))
+        return rt_fail(RT_EINVAL, "rt_diag_render_route: no such instance");
+    return RT_OK;
+}
+
+// The instance a render at the default knobs launches for `depth` and the scene kind `variant` of rt_diag_kernel_*
+// (0 spheres + board, 1 a culling scene of stride kCullStride, 2 meshes / transparency, 3 ray trees, 4 / 5 the
+// achromatic instances of 0 / 1), or nullptr: the build has none.
+static const void* diag_kernel(int depth, int variant) {
+    const int np = variant == 1 || variant == 5 ? kCullStride : kChunk;
+    const RouteScene s{variant == 3, variant == 2, np, sphere_stride(np), variant >= 4, 0};
+    const RenderKey k = render_route(s, RouteKnobs{false, false, 5, false}, depth, kModePlain, false).key;
+    if (variant >= 4 && !k.ACHRO) return nullptr;   // (deeper than RT_ACHRO_MAX_B: three channels)
+    return with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(k); });
+}
+
+// Diagnostics (include/rt_diag.h): registers and scratch of that instance — the tests assert the default instances
+// never spill.
 extern "C" int rt_diag_kernel_resources(int depth, int variant, int* vgprs, int* scratch_bytes) {
     if (depth < 0 || depth > RT_MAX_B || variant < 0 || variant > 5 || !vgprs || !scratch_bytes)
         return rt_fail(RT_EINVAL, "rt_diag_kernel_resources: bad arguments");
-    const void* f = with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(variant); });
+    const void* f = diag_kernel(depth, variant);
     if (!f) return rt_fail(RT_EINVAL, "rt_diag_kernel_resources: kernel not built");
     hipFuncAttributes a;
     RT_HIP(hipFuncGetAttributes(&a, f));
@@ -2162,7 +2232,7 @@ extern "C" int rt_diag_kernel_resources(int depth, int variant, int* vgprs, int*
 extern "C" int rt_diag_kernel_occupancy(int depth, int variant, int lds_bytes, int* blocks_per_cu) {
     if (depth < 0 || depth > RT_MAX_B || variant < 0 || variant > 5 || lds_bytes < 0 || !blocks_per_cu)
         return rt_fail(RT_EINVAL, "rt_diag_kernel_occupancy: bad arguments");
-    const void* f = with_depth(depth, [&](auto B) { return render_kernel_ptr<decltype(B)::value>(variant); });
+    const void* f = diag_kernel(depth, variant);
     if (!f) return rt_fail(RT_EINVAL, "rt_diag_kernel_occupancy: kernel not built");
     RT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, RT_WG_FAST, (size_t)lds_bytes));
     return RT_OK;

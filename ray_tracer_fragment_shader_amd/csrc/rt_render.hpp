@@ -757,34 +757,95 @@ struct ScreenArgs {
     uint32_t seq = 0;
 };
 
-// Render-kernel variants rt_render_dev chooses between (rt_kernel.hip).
-enum RenderVariant {
-    kVarFast = 0,          // spheres + board (the benchmark kernels), launch bounds RT_MINW (depth <= 3)
-    kVarFastAnyW,          // ... no occupancy bound (depth > 3, or RT_MIN_WAVES < 5)
-    kVarCull,              // >= kConeMin spheres: per-wave culling, RT_MINW_CULL (depth <= 3)
-    kVarCullAnyW,
-    kVarTransp,            // meshes / transparent materials (FULL)
-    kVarTree,              // ray trees (trace_tree)
-    kVarLds,               // A/B: scene in LDS, 256-thread workgroups
-    kVarStaging,           // A/B: LDS-staged row stores, 256-thread workgroups, RT_MINW
-    kVarStagingAnyW,
-    // packed pixel formats (rt_render_dev_packed: GRAY / RGB images), one per scene kind
-    kVarFastPacked,
-    kVarCullPacked,
-    kVarTranspPacked,
-    kVarTreePacked,
-    // supersampled renders (rt_render_ss_dev: render_body SS), one per scene kind: three channels, RGBA formats,
-    // one-wave workgroups, no SGPR cap (an achromatic scene's bits are the same in the three-channel kernel)
-    kVarFastSS,
-    kVarCullSS,
-    kVarTranspSS,
-    kVarTreeSS,
-    kVarCount
+// The SGPR-capped fast kernel (rt_render_kernel_sg) for the depths whose fast kernels fit 7 waves by VGPRs (c2: 63,
+// c3: 67).
+#ifndef RT_SG_MAX_B
+#define RT_SG_MAX_B 2
+#endif
+// The achromatic (one-channel, rt_device.hpp shade ACHRO) instances: the benchmark depths' fast and culling kernels.
+#ifndef RT_ACHRO
+#define RT_ACHRO 1
+#endif
+#ifndef RT_ACHRO_MAX_B
+#define RT_ACHRO_MAX_B 3
+#endif
+// The supersampled instances (SS = 1; one-wave tiles).  0: not built (experiment builds; rt_render_ss_dev then fails).
+#ifndef RT_SS
+#define RT_SS (RT_WG_FAST == 64)
+#endif
+// Launch-bound waves per SIMD of the bounded fast instances of depth B (the culling ones': cull_min_waves).
+constexpr int fast_min_waves(int B) { return RT_MINW != 0 ? RT_MINW : kDefaultMinWaves(B); }
+
+// ---- Which instance of the render kernels a frame runs: the key, the selector (here), the list (below) ----
+
+// An instance's key: the kernel template and exactly its template arguments after the depth B.  (The SGPR-capped
+// templates take MINW, CULL, PACKED and ACHRO; their bodies fix the other fields, RenderRow checks which values.)
+enum RenderTemplate { kKernel = 0, kKernelSg = 1, kKernelSg8 = 2 };   // rt_render_kernel, .._sg, .._sg8
+struct RenderKey {
+    int kernel;                                // RenderTemplate
+    int LDS, MINW;
+    bool TRANSP, CULL;
+    int WG;
+    bool TREE, PACKED, FIX64, ACHRO, SS;
+};
+constexpr bool operator==(const RenderKey& a, const RenderKey& b) {
+    return a.kernel == b.kernel && a.LDS == b.LDS && a.MINW == b.MINW && a.TRANSP == b.TRANSP && a.CULL == b.CULL &&
+           a.WG == b.WG && a.TREE == b.TREE && a.PACKED == b.PACKED && a.FIX64 == b.FIX64 && a.ACHRO == b.ACHRO &&
+           a.SS == b.SS;
+}
+
+// What render_route() decides on: the scene kind (rt_ctx / DevScene) and the context's A/B knobs (RT_SCENE_IN_LDS,
+// RT_WG_STAGING, RT_MIN_WAVES — >= 5 keeps the launch bounds of depth <= 3 —, RT_ACHRO_OFF), beside depth and mode.
+struct RouteScene { bool tree, transparent; int n_padded, n_stride; bool achromatic; int lds_bytes; };
+struct RouteKnobs { bool use_lds, wg_staging; int min_waves; bool achro_off; };
+enum RenderMode { kModePlain = 0, kModePacked = 1, kModeSS = 2 };   // RGBA images; GRAY / RGB images; supersampled
+struct RenderRoute {
+    RenderKey key;
+    int lds;                                   // dynamic LDS bytes of the launch
+    int tile_w;                                // tile width in pixels: 32 for the 256-thread instances, else RT_WG_FAST / 8
 };
 
+// The instance a frame of scene s runs at `depth` in `mode` under the knobs k — or, level_mask, the launch that
+// follows a fast scene's calibration render to write its level masks (a culling instance at the scene's own stride).
+// Pure, and the one place this is decided (render_dev_impl, rt_diag_kernel_*, rt_diag_render_route); DESIGN.md §5g
+// has the rules as a table, tests/test_route.py pins them.
+inline RenderRoute render_route(const RouteScene& s, const RouteKnobs& k, int depth, int mode, bool level_mask) {
+    const bool plain = mode == kModePlain, ss = mode == kModeSS;
+    // bounded (MINW > 1): depth <= 3; plain frames and the level-mask launch only with RT_MIN_WAVES >= 5
+    const bool bounded = depth <= 3 && (k.min_waves >= 5 || !(plain || level_mask));
+    const bool achro = RT_ACHRO && s.achromatic && !s.transparent && !s.tree && !k.achro_off && !ss &&
+                       depth <= RT_ACHRO_MAX_B && bounded;
+    const bool frame = !level_mask, knobs = plain && frame;   // (packed and supersampled frames take no A/B knob)
+    RenderKey K{kKernel, 0, 1, false, false, 64, false, mode == kModePacked && frame, false, false, ss && frame};
+    int lds = 0;
+    if (s.tree && frame) {
+        K.TRANSP = K.TREE = true;
+    } else if (s.transparent && frame) {
+        K.TRANSP = true;
+        lds = slot_bytes(depth, true, 64);
+    } else if (knobs && k.use_lds) {
+        K.LDS = 1;
+        K.WG = kThreads;
+        lds = s.lds_bytes + slot_bytes(depth, false);
+    } else if (knobs && k.wg_staging) {         // (the tile's four staged output images behind the slots)
+        K.WG = kThreads;
+        K.MINW = bounded ? fast_min_waves(depth) : 1;
+        lds = 4096 + 6144 + 1024 + 1024 + slot_bytes(depth, false);
+    } else {                                    // culling from kConeMin spheres (rt_device.hpp CULL), else fast
+        K.CULL = level_mask || s.n_padded >= kConeMin;
+        K.WG = RT_WG_FAST;
+        K.MINW = !bounded ? 1 : K.CULL ? cull_min_waves(depth) : fast_min_waves(depth);
+        K.FIX64 = K.CULL && RT_CULL_FIX64 && s.n_stride == kCullStride;
+        K.ACHRO = achro;
+        if (!K.CULL && !ss && bounded && depth <= RT_SG_MAX_B && RT_FAST_SGPRS > 0)   // the SGPR-capped templates
+            K.kernel = achro && depth == RT_SG8_B && RT_FAST8_SGPRS > 0 ? kKernelSg8 : kKernelSg;
+        lds = slot_bytes(depth, false, RT_WG_FAST, K.CULL);
+    }
+    return RenderRoute{K, lds, K.WG == kThreads ? kTileW : RT_WG_FAST / 8};
+}
+
 struct RenderLaunch {
-    int variant;
-    bool achro;                                // achromatic scene: the one-channel instances (opaque variants)
+    RenderKey key;                             // the instance (render_route)
     dim3 grid;
     size_t lds;
     hipStream_t stream;
@@ -804,7 +865,7 @@ hipError_t launch_trace_rays(int variant /* 0 opaque, 1 FULL, 2 tree */, dim3 gr
                              const DevScene* s, const double* a, const double* b, int n, double* rgb, uint32_t* rc,
                              const ScreenArgs& sa);
 template <int B>
-const void* render_kernel_ptr(int variant);   // rt_diag_kernel_resources: 0 fast, 1 cull, 2 FULL, 3 tree
+const void* render_kernel_ptr(const RenderKey& k);   // the depth-B instance with key k, or nullptr: there is none
 
 #define RT_DECLARE_DEPTH(B)                                                                                   \
     template <>                                                                                                \
@@ -813,7 +874,7 @@ const void* render_kernel_ptr(int variant);   // rt_diag_kernel_resources: 0 fas
     hipError_t launch_trace_rays<B>(int, dim3, hipStream_t, const DevScene*, const double*, const double*, int,   \
                                     double*, uint32_t*, const ScreenArgs&);                                    \
     template <>                                                                                                \
-    const void* render_kernel_ptr<B>(int);
+    const void* render_kernel_ptr<B>(const RenderKey&);
 RT_DECLARE_DEPTH(0) RT_DECLARE_DEPTH(1) RT_DECLARE_DEPTH(2) RT_DECLARE_DEPTH(3)
 RT_DECLARE_DEPTH(4) RT_DECLARE_DEPTH(5) RT_DECLARE_DEPTH(6) RT_DECLARE_DEPTH(7)
 #undef RT_DECLARE_DEPTH
@@ -837,123 +898,109 @@ auto with_depth(int depth, F&& f) {
 // The `variant` of the generic-path launches (launch_trace_rays and rt_sampled.hpp's) for a scene kind.
 inline int trace_variant(bool tree, bool transparent) { return tree ? 2 : transparent ? 1 : 0; }
 
-// Body of the per-depth instance files.
-template <int B, int LDS, int MINW, bool TRANSP, bool CULL, int WG, bool TREE, bool PACKED = false, bool FIX64 = false,
-          bool ACHRO = false, bool SS = false>
-hipError_t launch_render_one(const RenderLaunch& L) {
-    auto kern = rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS>;
+// ---- The per-depth instance files' bodies ----
+
+// The three kernel templates share one parameter list (RenderArgs), so one pointer type holds any instance.
+using RenderKernelFn = void (*)(const DispRec*, int32_t, int32_t, const DevScene*, RenderParams, void*, void*, double*,
+                                uint32_t*);
+
+// One row of a depth's instance list: whether this build has the instance (ON) and its key.  The key's fields are the
+// very template arguments kernel<B>() instantiates, so what is matched and what is launched cannot disagree.
+template <bool ON, int KERNEL, int LDS, int MINW, bool TRANSP, bool CULL, int WG, bool TREE = false, bool PACKED = false,
+          bool FIX64 = false, bool ACHRO = false, bool SS = false>
+struct RenderRow {
+    static constexpr bool on = ON;
+    static constexpr RenderKey key{KERNEL, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS};
+    static_assert(KERNEL == kKernel || (LDS == 0 && !TRANSP && WG == RT_WG_FAST && !TREE && !FIX64 && !SS),
+                  "the SGPR-capped kernels' bodies fix these fields");
+    template <int B>
+    static RenderKernelFn kernel() {
+        if constexpr (!ON) return nullptr;
+        else if constexpr (KERNEL == kKernelSg) return rt_render_kernel_sg<B, MINW, CULL, PACKED, ACHRO>;
+        else if constexpr (KERNEL == kKernelSg8) return rt_render_kernel_sg8<B, MINW, CULL, PACKED, ACHRO>;
+        else return rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS>;
+    }
+};
+template <class... Rows>
+struct RenderRows {};
+
+// The render-kernel instances of depth B: every kernel an instance file emits, one row each.  render_route() returns
+// rows of this list only (tests/test_route.py walks its inputs).  Rows marked * are compiled but never chosen at some
+// depths — the bounded rows beyond depth 3 (any-waves there) and the uncapped twin of an SGPR-capped row up to depth
+// RT_SG_MAX_B: the instance files have always emitted them, and this list keeps the set of kernels as it was.
+template <int B>
+struct RenderInstances {
+    static constexpr bool kAll = B <= RT_MAX_B;                               // (experiment builds stop earlier)
+    static constexpr bool kSg = kAll && B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0;
+    static constexpr bool kAc = kAll && RT_ACHRO && B <= RT_ACHRO_MAX_B;
+    static constexpr bool kSs = kAll && RT_SS;
+    static constexpr int F = RT_WG_FAST, T = kThreads;
+    static constexpr int MW = fast_min_waves(B), MC = cull_min_waves(B);     // bounded: plain and achromatic rows
+    static constexpr int PW = B <= 3 ? MW : 1, PC = B <= 3 ? MC : 1;          // packed and supersampled rows
+    static constexpr int SGA = use_sg8<B, true>() ? kKernelSg8 : kKernelSg;   // the achromatic rows' capped template
+    using rows = RenderRows<
+        //        ON    template   LDS MINW TRANSP CULL WG TREE PACKED FIX64 ACHRO SS
+        RenderRow<kSg,  kKernelSg,  0,  MW,  0,    0,   F>,                             // fast, bounded, SGPR cap
+        RenderRow<kAll, kKernel,    0,  MW,  0,    0,   F>,                             // fast, bounded *
+        RenderRow<kAll, kKernel,    0,  1,   0,    0,   F>,                             // fast, any waves
+        RenderRow<kAll, kKernel,    0,  MC,  0,    1,   F,  0,   0,     1>,             // culling, bounded, stride 64 *
+        RenderRow<kAll, kKernel,    0,  MC,  0,    1,   F>,                             // culling, bounded *
+        RenderRow<kAll, kKernel,    0,  1,   0,    1,   F,  0,   0,     1>,             // culling, any waves, stride 64
+        RenderRow<kAll, kKernel,    0,  1,   0,    1,   F>,                             // culling, any waves
+        RenderRow<kAll, kKernel,    0,  1,   1,    0,   64>,                            // transparent
+        RenderRow<kAll, kKernel,    0,  1,   1,    0,   64, 1>,                         // ray tree
+        RenderRow<kAll, kKernel,    1,  1,   0,    0,   T>,                             // A/B: scene in LDS
+        RenderRow<kAll, kKernel,    0,  MW,  0,    0,   T>,                             // A/B: staged stores, bounded *
+        RenderRow<kAll, kKernel,    0,  1,   0,    0,   T>,                             // A/B: staged stores, any waves
+        // achromatic (one channel)
+        RenderRow<kSg && kAc, SGA,  0,  MW,  0,    0,   F,  0,   0,     0,    1>,       // fast, SGPR cap
+        RenderRow<kAc,  kKernel,    0,  MW,  0,    0,   F,  0,   0,     0,    1>,       // fast *
+        RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   0,     1,    1>,       // culling, stride 64
+        RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   0,     0,    1>,       // culling
+        // packed pixel formats (runtime format branches at the stores)
+        RenderRow<kSg,  kKernelSg,  0,  MW,  0,    0,   F,  0,   1>,                    // fast, SGPR cap
+        RenderRow<kAll, kKernel,    0,  PW,  0,    0,   F,  0,   1>,                    // fast *
+        RenderRow<kAll, kKernel,    0,  PC,  0,    1,   F,  0,   1,     1>,             // culling, stride 64
+        RenderRow<kAll, kKernel,    0,  PC,  0,    1,   F,  0,   1>,                    // culling
+        RenderRow<kAll, kKernel,    0,  1,   1,    0,   64, 0,   1>,                    // transparent
+        RenderRow<kAll, kKernel,    0,  1,   1,    0,   64, 1,   1>,                    // ray tree
+        RenderRow<kSg && kAc, SGA,  0,  MW,  0,    0,   F,  0,   1,     0,    1>,       // achromatic fast, SGPR cap
+        RenderRow<kAc,  kKernel,    0,  MW,  0,    0,   F,  0,   1,     0,    1>,       // achromatic fast *
+        RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   1,     1,    1>,       // achromatic culling, stride 64
+        RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   1,     0,    1>,       // achromatic culling
+        // supersampled (three channels, RGBA stores, no SGPR cap)
+        RenderRow<kSs,  kKernel,    0,  PW,  0,    0,   F,  0,   0,     0,    0,    1>, // fast
+        RenderRow<kSs,  kKernel,    0,  PC,  0,    1,   F,  0,   0,     1,    0,    1>, // culling, stride 64
+        RenderRow<kSs,  kKernel,    0,  PC,  0,    1,   F,  0,   0,     0,    0,    1>, // culling
+        RenderRow<kSs,  kKernel,    0,  1,   1,    0,   64, 0,   0,     0,    0,    1>, // transparent
+        RenderRow<kSs,  kKernel,    0,  1,   1,    0,   64, 1,   0,     0,    0,    1>  // ray tree
+        >;
+};
+
+// The kernel of the row whose key equals k, or nullptr.
+template <int B, class... Rows>
+RenderKernelFn find_render_kernel(RenderRows<Rows...>, const RenderKey& k) {
+    RenderKernelFn f = nullptr;
+    (void)((Rows::on && Rows::key == k && ((f = Rows::template kernel<B>()), true)) || ...);
+    return f;
+}
+
+template <int B>
+const void* render_kernel_ptr_impl(const RenderKey& k) {
+    return (const void*)find_render_kernel<B>(typename RenderInstances<B>::rows{}, k);
+}
+
+template <int B>
+hipError_t launch_render_impl(const RenderLaunch& L) {
+    const RenderKernelFn kern = find_render_kernel<B>(typename RenderInstances<B>::rows{}, L.key);
+    if (!kern) return hipErrorInvalidValue;
     if (L.lds > 65536) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, L.grid, dim3(WG), L.lds, L.stream, L.P.disp, L.P.tiles_x, L.P.tile_rows_n * L.P.tiles_x, L.scene, L.P, L.o32, L.o8, L.o64, L.orc);
+    hipLaunchKernelGGL(kern, L.grid, dim3(L.key.WG), L.lds, L.stream, L.P.disp, L.P.tiles_x, L.P.tile_rows_n * L.P.tiles_x,
+                       L.scene, L.P, L.o32, L.o8, L.o64, L.orc);
     return hipGetLastError();
-}
-
-// The SGPR-capped fast kernel (rt_render_kernel_sg) for the depths whose fast kernels fit 7 waves by VGPRs (c2: 63,
-// c3: 67).
-#ifndef RT_SG_MAX_B
-#define RT_SG_MAX_B 2
-#endif
-template <int B, int MINW, bool PACKED, bool ACHRO = false>
-hipError_t launch_render_sg(const RenderLaunch& L) {
-    if constexpr (use_sg8<B, ACHRO>())
-        hipLaunchKernelGGL((rt_render_kernel_sg8<B, MINW, false, PACKED, ACHRO>), L.grid, dim3(RT_WG_FAST), L.lds,
-                           L.stream, L.P.disp, L.P.tiles_x, L.P.tile_rows_n * L.P.tiles_x, L.scene, L.P, L.o32, L.o8, L.o64, L.orc);
-    else
-        hipLaunchKernelGGL((rt_render_kernel_sg<B, MINW, false, PACKED, ACHRO>), L.grid, dim3(RT_WG_FAST), L.lds,
-                           L.stream, L.P.disp, L.P.tiles_x, L.P.tile_rows_n * L.P.tiles_x, L.scene, L.P, L.o32, L.o8, L.o64, L.orc);
-    return hipGetLastError();
-}
-
-// The achromatic (one-channel, rt_device.hpp shade ACHRO) instances: the benchmark depths' fast and culling kernels.
-#ifndef RT_ACHRO
-#define RT_ACHRO 1
-#endif
-#ifndef RT_ACHRO_MAX_B
-#define RT_ACHRO_MAX_B 3
-#endif
-// The supersampled instances (kVar*SS; one-wave tiles).  0: not built (experiment builds; rt_render_ss_dev then fails).
-#ifndef RT_SS
-#define RT_SS (RT_WG_FAST == 64)
-#endif
-
-template <int B>
-hipError_t launch_render_impl(const RenderLaunch& L) {
-    if constexpr (B > RT_MAX_B) {
-        return hipErrorInvalidValue;
-    } else {
-        constexpr int MW = RT_MINW != 0 ? RT_MINW : kDefaultMinWaves(B);
-        constexpr bool kAchro = RT_ACHRO && B <= RT_ACHRO_MAX_B;
-        if constexpr (kAchro) {
-            if (L.achro) {
-                switch (L.variant) {
-                    case kVarFast:
-                        if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) return launch_render_sg<B, MW, false, true>(L);
-                        return launch_render_one<B, 0, MW, false, false, RT_WG_FAST, false, false, false, true>(L);
-                    case kVarCull:
-                        if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                            return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false, false, true,
-                                                     true>(L);
-                        return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false, false, false,
-                                                 true>(L);
-                    case kVarFastPacked:
-                        if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) return launch_render_sg<B, MW, true, true>(L);
-                        return launch_render_one<B, 0, MW, false, false, RT_WG_FAST, false, true, false, true>(L);
-                    case kVarCullPacked:
-                        if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                            return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false, true, true,
-                                                     true>(L);
-                        return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false, true, false,
-                                                 true>(L);
-                    default: break;                     // the other variants: three channels
-                }
-            }
-        }
-        switch (L.variant) {
-            case kVarFast:
-                if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) return launch_render_sg<B, MW, false>(L);
-                return launch_render_one<B, 0, MW, false, false, RT_WG_FAST, false>(L);
-            case kVarFastAnyW: return launch_render_one<B, 0, 1, false, false, RT_WG_FAST, false>(L);
-            case kVarCull:
-                if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                    return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false, false, true>(L);
-                return launch_render_one<B, 0, cull_min_waves(B), false, true, RT_WG_FAST, false>(L);
-            case kVarCullAnyW:
-                if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                    return launch_render_one<B, 0, 1, false, true, RT_WG_FAST, false, false, true>(L);
-                return launch_render_one<B, 0, 1, false, true, RT_WG_FAST, false>(L);
-            case kVarTransp: return launch_render_one<B, 0, 1, true, false, 64, false>(L);
-            case kVarTree: return launch_render_one<B, 0, 1, true, false, 64, true>(L);
-            case kVarLds: return launch_render_one<B, 1, 1, false, false, kThreads, false>(L);
-            case kVarStaging: return launch_render_one<B, 0, MW, false, false, kThreads, false>(L);
-            case kVarStagingAnyW: return launch_render_one<B, 0, 1, false, false, kThreads, false>(L);
-            case kVarFastPacked:
-                if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) return launch_render_sg<B, MW, true>(L);
-                return launch_render_one<B, 0, (B <= 3 ? MW : 1), false, false, RT_WG_FAST, false, true>(L);
-            case kVarCullPacked:
-                if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                    return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, true,
-                                             true>(L);
-                return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, true>(L);
-            case kVarTranspPacked: return launch_render_one<B, 0, 1, true, false, 64, false, true>(L);
-            case kVarTreePacked: return launch_render_one<B, 0, 1, true, false, 64, true, true>(L);
-#if RT_SS
-            case kVarFastSS:
-                return launch_render_one<B, 0, (B <= 3 ? MW : 1), false, false, RT_WG_FAST, false, false, false, false,
-                                         true>(L);
-            case kVarCullSS:
-                if (RT_CULL_FIX64 && L.P.ns == kCullStride)
-                    return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, false,
-                                             true, false, true>(L);
-                return launch_render_one<B, 0, (B <= 3 ? cull_min_waves(B) : 1), false, true, RT_WG_FAST, false, false,
-                                         false, false, true>(L);
-            case kVarTranspSS: return launch_render_one<B, 0, 1, true, false, 64, false, false, false, false, true>(L);
-            case kVarTreeSS: return launch_render_one<B, 0, 1, true, false, 64, true, false, false, false, true>(L);
-#endif
-            default: return hipErrorInvalidValue;
-        }
-    }
 }
 
 template <int B>
@@ -990,39 +1037,6 @@ hipError_t launch_trace_rays_impl(int variant, dim3 grid, hipStream_t st, const 
     }
 }
 
-template <int B>
-const void* render_kernel_ptr_impl(int variant) {
-    if constexpr (B > RT_MAX_B) {
-        return nullptr;
-    } else {
-        constexpr int kFast = B <= 3 ? (RT_MINW != 0 ? RT_MINW : kDefaultMinWaves(B)) : 1;
-        constexpr int kCull = B <= 3 ? cull_min_waves(B) : 1;
-        switch (variant) {
-            case 0:
-                if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) return (const void*)rt_render_kernel_sg<B, kFast, false, false>;
-                return (const void*)rt_render_kernel<B, 0, kFast, false, false, RT_WG_FAST, false>;
-            case 1: return (const void*)rt_render_kernel<B, 0, kCull, false, true, RT_WG_FAST, false, false, (bool)RT_CULL_FIX64>;
-            case 2: return (const void*)rt_render_kernel<B, 0, 1, true, false, 64, false>;
-            case 3: return (const void*)rt_render_kernel<B, 0, 1, true, false, 64, true>;
-            case 4:                                     // the achromatic (one-channel) instances of 0 and 1
-                if constexpr (RT_ACHRO && B <= RT_ACHRO_MAX_B) {
-                    if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0 && use_sg8<B, true>())
-                        return (const void*)rt_render_kernel_sg8<B, kFast, false, false, true>;
-                    else if constexpr (B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0)
-                        return (const void*)rt_render_kernel_sg<B, kFast, false, false, true>;
-                    else return (const void*)rt_render_kernel<B, 0, kFast, false, false, RT_WG_FAST, false, false, false, true>;
-                }
-                return nullptr;
-            case 5:
-                if constexpr (RT_ACHRO && B <= RT_ACHRO_MAX_B)
-                    return (const void*)rt_render_kernel<B, 0, kCull, false, true, RT_WG_FAST, false, false,
-                                                         (bool)RT_CULL_FIX64, true>;
-                return nullptr;
-            default: return nullptr;
-        }
-    }
-}
-
 }  // namespace rtk
 
 // One line per instance file: the depth-B definitions of the three declarations above.
@@ -1036,5 +1050,5 @@ const void* render_kernel_ptr_impl(int variant) {
         return launch_trace_rays_impl<B>(v, g, st, s, a, b, n, rgb, rc, sa);                                   \
     }                                                                                                          \
     template <>                                                                                                \
-    const void* render_kernel_ptr<B>(int v) { return render_kernel_ptr_impl<B>(v); }                           \
+    const void* render_kernel_ptr<B>(const RenderKey& k) { return render_kernel_ptr_impl<B>(k); }              \
     }

@@ -203,6 +203,37 @@ def test_workgroup_variants_agree(env, name):
         assert np.array_equal(out[1][k], want), f"{env}=0 render {k}"
 
 
+@pytest.mark.parametrize("env", ["RT_SCENE_IN_LDS", "RT_WG_STAGING"])
+@pytest.mark.parametrize("name", ["demo", "tree_demo"])
+def test_workgroup_knobs_leave_one_wave_scenes_whole(env, name):
+    """Transparent and ray-tree scenes have no 256-thread instance: under the A/B knobs they run their one-wave
+    kernels, and the frame's tiles are that instance's 8 x 8 (cut by the knob's 32 x 8 the one-wave kernel would trace a
+    quarter of the columns).  Every pixel and counter equals the frame without the knob, on each render of the view."""
+    scene = scenes.tree_case(name)[0] if name == "tree_demo" else scenes.CONFIGS[name].scene()
+    W, H, depth = 200, 150, 3
+    cam = scenes.CONFIGS["demo"].camera(W, H)
+    out = []
+    for mode in ("1", "0"):
+        os.environ[env] = mode
+        t = Tracer(0)
+        t.set_scene(scene)
+        frames = []
+        for _ in range(3):
+            b = t.alloc(W, H, None, rgba32f=False, rgb64f=True, raycount=True)
+            b["rgb64f"].fill_(-7.0)
+            b["raycount"].fill_(-7)
+            t.render_into(cam, W, H, depth, b)
+            torch.cuda.synchronize()
+            frames.append((b["rgb64f"].cpu().numpy(), b["raycount"].cpu().numpy()))
+        out.append(frames)
+        t.close()
+    os.environ.pop(env)
+    for k in range(3):
+        assert np.array_equal(out[0][k][0], out[1][k][0]), f"{env}=1 render {k}"
+        assert np.array_equal(out[0][k][1], out[1][k][1]), f"{env}=1 render {k}"
+        assert (out[1][k][1] != -7).all()
+
+
 @pytest.mark.parametrize("G,hb", [(2, 8), (3, 5), (8, 16), (4, 1)])
 def test_row_bands_and_unshuffle(tr, G, hb):
     cfg = scenes.CONFIGS["c2"]
