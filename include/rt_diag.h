@@ -70,6 +70,22 @@ int rt_diag_render_route(int tree, int transparent, int n_padded, int n_stride, 
  * engine is not set up).  RT_EINVAL for a null context. */
 int rt_diag_copy_path(rt_ctx* ctx, int* mode, int* writer);
 
+/* Sky tiles: 8 x 8 pixel tiles none of whose primary rays can hit anything — a proof from the tile's bounding cone
+ * against the board's edges and the spheres' cones, made per wave by the render kernel, which then stores the miss
+ * constants without tracing (RT_SKY_TILES=0 in the environment of rt_ctx_create turns the early-out off; the images
+ * are the same bytes either way).  rt_diag_sky_tiles evaluates the kernel's verdict on the host, no device needed:
+ * out[ty * tiles_x + tx] = 1 when tile (tx, ty) of the width x height frame (the rank's local rows when `rows` is
+ * given) is proved, else 0; tiles_x = ceil(width / 8), tile rows = ceil(local rows / 8), n their product.  Scenes the
+ * early-out does not cover (meshes, transparent materials, fewer than 8 or more than 64 spheres) give all zeros.
+ * RT_EINVAL for bad arguments or another n. */
+int rt_diag_sky_tiles(const rt_scene* scene, const rt_camera* cam, int width, int height, const rt_rows* rows,
+                      uint8_t* out, size_t n);
+
+/* The verdicts the waves themselves reached in this context's last calibration render (the second render of a
+ * static view; later renders of that view read them from their dispatch records): *tiles the view's tile count,
+ * *sky how many took the early-out.  Both 0 when no calibrated view holds verdicts.  Waits for the device. */
+int rt_diag_sky_count(rt_ctx* ctx, int* tiles, int* sky);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rt_cone.hpp"
 #include "rt_layout.hpp"
 
 // 1 (r06): the exact sqrt / quotient fast paths run unconditionally and their rare slow paths sit behind one
@@ -934,69 +935,28 @@ __device__ __host__ __forceinline__ float chord_of_sin(float s) {
     return s * sqrtf(2.0f / (1.0f + sqrtf(fmaxf(0.0f, 1.0f - s * s))));
 }
 
-// FP32 square root and reciprocal of the wave-culling tests (RT_FAST_MASK = 1): the hardware instructions
-// (v_sqrt_f32, v_rcp_f32, 1 ulp: relative error < 2^-22 on normal operands) instead of the correctly rounded
-// sequences (scaling, Newton and fixup steps around them: ~10 instructions each).  The culling tests only need
-// conservative bounds, and their margins (R inflated by 2^-12 relative, chord limits by 2^-14 absolute, shadow
-// cones by 2^-16 in cos) are > 2^6 times the extra error; 0, +inf and NaN keep their meaning (sqrt(0) = 0,
-// rcp(+inf) = 0, NaN propagates and fails the `>` compares, i.e. keeps the sphere).
-#ifndef RT_FAST_MASK
-#define RT_FAST_MASK 1                         // same-box A/B: c5 -5.7%, c2/c3 +-1%
-#endif
-__device__ __forceinline__ float msqrt(float x) {
-#if RT_FAST_MASK
-    return __builtin_amdgcn_sqrtf(x);
-#else
-    return sqrtf(x);
-#endif
-}
-__device__ __forceinline__ float mrcp(float x) {
-#if RT_FAST_MASK
-    return __builtin_amdgcn_rcpf(x);
-#else
-    return 1.0f / x;
-#endif
-}
-__device__ __forceinline__ float mdiv(float a, float b) {
-#if RT_FAST_MASK
-    return a * __builtin_amdgcn_rcpf(b);
-#else
-    return a / b;
-#endif
-}
-__device__ __forceinline__ float mchord_of_sin(float s) {
-    return s * msqrt(mdiv(2.0f, 1.0f + msqrt(fmaxf(0.0f, 1.0f - s * s))));
-}
+// (msqrt, mrcp, mdiv, mchord_of_sin — the FP32 square root and reciprocal of the wave-culling tests, RT_FAST_MASK —
+// are in rt_cone.hpp, with the primary cone's tests.)
 
-// Per-wave culling of primary rays (V.np >= kConeMin; all 64 lanes must be active).  The wave's rays go
-// from the eye through the screen points of its bw x bh block, all within R = half_diag pitch of the
-// block centre c (half_diag = |((bw - 1) / 2, (bh - 1) / 2)|), hence (exact geometry) within angle asin(R / |c - eye|) of a = unit(c - eye): chord
-// distance |u - a| <= rho.  A ray that hits sphere k has |u - v_k| <= chord_k (DevSphereCone, rounded
-// up, radius inflated for FP64 rounding), so |a - v_k| <= rho + chord_k + slack, where `slack` (host,
-// RenderParams) bounds the FP32 error of a and of the test itself.  Lane j evaluates sphere j; the
-// ballot is the mask of spheres this wave must test.  NaNs keep the sphere.
+// Per-wave culling of primary rays (V.np >= kPrimaryConeMin; all 64 lanes must be active).  The wave's rays lie
+// within chord distance rho of the block's axis a (rt_cone.hpp wave_axis).  A ray that hits sphere k has
+// |u - v_k| <= chord_k (DevSphereCone, rounded up, radius inflated for FP64 rounding), so |a - v_k| <= rho + chord_k
+// (rho includes `slack` (host, RenderParams), the bound on the FP32 error of a and of the test itself).  Lane j
+// evaluates sphere j; the ballot is the mask of spheres this wave must test.  NaNs keep the sphere.
+// *board_miss (wave-uniform): no ray of the wave can hit the board — lane j also evaluates board edge j mod 4
+// (DevScene::edge, rt_cone.hpp board_edge_record), and one edge with every ray on its outer side is a proof.
 __device__ __forceinline__ uint64_t primary_cone_mask(const SceneView& V, const float look[3],
                                                       const float right[3], const float upp[3],
                                                       const float eye[3], float pitch, float ci, float cj,
-                                                      float half_diag, float slack, int lane) {
-    const float a_r = pitch * ci, a_u = pitch * cj;
-    float dx = fmaf(a_u, upp[0], fmaf(a_r, right[0], look[0])) - eye[0];
-    float dy = fmaf(a_u, upp[1], fmaf(a_r, right[1], look[1])) - eye[1];
-    float dz = fmaf(a_u, upp[2], fmaf(a_r, right[2], look[2])) - eye[2];
-    const float dn = msqrt(fmaf(dx, dx, fmaf(dy, dy, dz * dz)));
-    const float sn = mdiv((half_diag * 1.001f) * pitch, dn);
-    if (!(sn < 0.5f)) return ~0ull;                         // eye too close to the screen: no culling
-    const float rho = mchord_of_sin(sn) + slack;
-    const float idn = mrcp(dn);
-    dx *= idn, dy *= idn, dz *= idn;
-    bool keep = false;
-    if (lane < V.np) {
-        const DevSphereCone& c = V.cone[lane];
-        const float ex = dx - c.vx, ey = dy - c.vy, ez = dz - c.vz;
-        const float lim = rho + c.chord;
-        keep = !(fmaf(ex, ex, fmaf(ey, ey, ez * ez)) > lim * lim);
-    }
-    return __ballot(keep);
+                                                      float half_diag, float slack, int lane, bool* board_miss) {
+    // (both records requested before the axis arithmetic: one vector round trip, not two)
+    const DevBoardEdge edge = V.S->edge[lane & 3];
+    const DevSphereCone cone = V.cone[lane < V.np ? lane : 0];
+    const WaveAxis w = wave_axis(look, right, upp, eye, pitch, ci, cj, half_diag, slack);
+    *board_miss = false;
+    if (!w.ok) return ~0ull;                                // eye too close to the screen: no culling
+    *board_miss = __ballot(edge_misses(w, edge)) != 0;
+    return __ballot(lane < V.np && cone_keeps(w, cone));
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "../../include/rt_api.h"
+#include "../../include/rt_diag.h"
+#include "rt_cone.hpp"
 #include "rt_internal.hpp"
 #include "rt_layout.hpp"
 
@@ -691,6 +693,58 @@ extern "C" int rt_scene_achromatic(const rt_scene* s, int* out) {
         ok = grey_mat(s->meshes[m].kind == RT_MESH_TETRAHEDRON ? s->tetrahedron_material : s->cube_material);
     for (int k = 0; k < s->n_lights && ok; ++k) ok = grey(s->lights[k].color);
     *out = ok ? 1 : 0;
+    return RT_OK;
+}
+
+// The sky verdict of every 8 x 8 tile of a frame (include/rt_diag.h), evaluated on the host with the functions the
+// render kernel's cone phase runs (rt_cone.hpp): the per-eye records as rt_prepare_kernel writes them, the tile
+// geometry as render_body forms it.
+extern "C" int rt_diag_sky_tiles(const rt_scene* scene, const rt_camera* cam, int width, int height,
+                                 const rt_rows* rows, uint8_t* out, size_t n) {
+    if (!cam || !out || width <= 0 || height <= 0) return rt_fail(RT_EINVAL, "rt_diag_sky_tiles: bad arguments");
+    std::vector<unsigned char> blob;
+    int rc = rt_build_dev_scene(scene, &blob);
+    if (rc) return rc;
+    int nl = 0;
+    rc = rt_local_rows(height, rows, &nl);
+    if (rc) return rc;
+    const int tiles_x = (width + 7) / 8, tiles_y = (nl + 7) / 8;
+    if (n != (size_t)tiles_x * tiles_y) return rt_fail(RT_EINVAL, "rt_diag_sky_tiles: out must hold one byte per tile");
+    memset(out, 0, n);
+    const rt::DevScene* d = reinterpret_cast<const rt::DevScene*>(blob.data());
+    const int np = d->n_padded;
+    // the instances that take the early-out: opaque, mesh-free scenes whose cone mask covers every sphere
+    if (d->tree || d->transparent || d->n_meshes > 0 || np < rt::kPrimaryConeMin || np > 64) return RT_OK;
+    const rt::DevSphere* sph = reinterpret_cast<const rt::DevSphere*>(d + 1);
+    const double* eye = cam->eye;
+    rt::DevSphereCone cone[64];
+    for (int k = 0; k < np; ++k) {
+        const HP dP = hp(sph[k].c) - hp(eye);                                   // as rt_prepare_kernel
+        cone[k] = rt::sphere_cone_record(dP.x, dP.y, dP.z, dot(dP, dP), sph[k].r2);
+    }
+    rt::DevBoardEdge edge[4];
+    for (int e = 0; e < 4; ++e) edge[e] = rt::board_edge_record(d, eye[0], eye[1], eye[2], e);
+    double right[3], upp[3];
+    rt_camera_basis(cam, right, upp);
+    const rt::ConeCam C = rt::cone_camera(cam->look_at, right, upp, eye, cam->pitch, cam->bottom_x, cam->bottom_y,
+                                          width, height);
+    // image row (within its frame) of local row lr, defined past the last row as the kernel's global_row_of is
+    const bool banded = rows && rows->n_ranks > 1;
+    const int frames = frames_of(rows), frame_rows = nl / frames;
+    const int hb = banded ? rows->band_height : height, G = banded ? rows->n_ranks : 1, rank = banded ? rows->rank : 0;
+    auto row_of = [&](int lr) {
+        if (frames > 1) lr %= frame_rows;
+        return G <= 1 ? lr : ((lr / hb) * G + rank) * hb + (lr - (lr / hb) * hb);
+    };
+    const float h = 3.5f, half_diag = sqrtf(h * h + h * h);
+    for (int ty = 0; ty < tiles_y; ++ty) {
+        // the block's rows must be 8 consecutive image rows of one frame (the gate of primary_cone_mask)
+        const int lr0 = ty * 8, ja = row_of(lr0), jb = row_of(lr0 + 7);
+        if (!(frames <= 1 || lr0 / frame_rows == (lr0 + 7) / frame_rows) || jb - ja != 7) continue;
+        for (int tx = 0; tx < tiles_x; ++tx)
+            out[(size_t)ty * tiles_x + tx] = rt::sky_tile(C, cone, np, edge, (float)(tx * 8 + cam->bottom_x) + h,
+                                                          (float)(ja + cam->bottom_y) + h, half_diag);
+    }
     return RT_OK;
 }
 

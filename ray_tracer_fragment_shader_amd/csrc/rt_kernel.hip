@@ -4,7 +4,7 @@
 // rt_render_b<B>.hip; the rest live here)
 //   rt_render_kernel<...>     one work-item per pixel, FP64, iterative bounce loop (rt_render.hpp)
 //   rt_trace_rays_kernel<B>   rayTraceRay on an arbitrary ray list (rt_render.hpp)
-//   rt_prepare_kernel         per-eye sphere data, board numerator and cull flag (once per camera eye)
+//   rt_prepare_kernel         per-eye sphere data, board numerator, board edges and cull flag (once per camera eye)
 //   rt_scene_init_kernel      device-side reciprocals of constant divisors (once per scene)
 //   rt_rowsum_kernel, rt_order_kernel, rt_disp_kernel
 //                             the dispatch table of a calibrated view: tile rows (or tiles, hipCUB radix sort)
@@ -104,7 +104,8 @@ __global__ __launch_bounds__(256) void rt_iota_kernel(int32_t* __restrict__ v, i
 // The dispatch table of a calibrated view: position L (linear workgroup id, L = gy * tiles_x + bx) traces tile
 // by_pos[L] (tile order: tile indices by decreasing calibrated time) or, row order (by_pos = nullptr), tile column
 // tile_col(bx, gy) of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
-// `cone` (else 0).  Stored at cone_slot(L): grouped by the XCD workgroup L runs on.
+// `cone` (else 0), and their sky verdicts (cone[n + tile], n the tile count).  Stored at cone_slot(L): grouped by the
+// XCD workgroup L runs on.
 __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict__ row_order,
                                                       const int32_t* __restrict__ by_pos,
                                                       const uint64_t* __restrict__ cone, int tiles_x, int tiles_y,
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     r.cone_lo = (uint32_t)m;
     r.cone_hi = (uint32_t)(m >> 32);
     r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
-    r.pad = 0;
+    r.sky = cone ? (uint32_t)cone[n + (size_t)ty * tiles_x + tx] : 0;   // (the verdicts follow the n masks)
     disp[cone_slot(k, n)] = r;
 }
 
@@ -161,6 +162,8 @@ __global__ __launch_bounds__(kThreads) void rt_prepare_kernel(DevScene* __restri
         g->prim_bound_ok = (g->bound_on != 0) & (g->hits_inside != 0) & (g->eps < 0.5) &
                            (D2 >= R1 * R1 * (1.0 + 0x1p-30)) & (D2 <= R1 * R1 * 0x1p40);
     }
+    // the board's four edges seen from this eye (the wave-level board miss of primary_cone_mask)
+    if (k < 4) g->edge[k] = board_edge_record(g, ex, ey, ez, k);
     if (k >= np) return;
     d3 dP = sub(ld3(sph[k].c), eye);
     double dd = dot(dP, dP);
@@ -175,26 +178,8 @@ __global__ __launch_bounds__(kThreads) void rt_prepare_kernel(DevScene* __restri
     f.dx = (float)dP.x; f.dy = (float)dP.y; f.dz = (float)dP.z;
     f.c0 = __double2float_ru(c0);
     primf[k] = f;
-    // Cone of directions from the eye that can hit sphere k (primary_cone_mask).  r' covers the FP64
-    // test's rounding (disc error < 4 ulp of 3 D^2 < D^2 2^-48): r'^2 = r2 (1 + 2^-20) + D^2 2^-46.
-    DevSphereCone cn;
-    if (!(r2 >= 0.0)) {                                     // padding: never kept
-        cn.vx = cn.vy = cn.vz = 1e30f;
-        cn.chord = 0.0f;
-    } else {
-        double D = sqrt(dd);
-        double rp = sqrt(r2 * (1.0 + 0x1p-20) + dd * 0x1p-46);
-        double sn = rp / D;
-        if (!(sn < 0.999)) {                                // eye inside / at the sphere: always kept
-            cn.vx = cn.vy = cn.vz = 0.0f;
-            cn.chord = 4.0f;
-        } else {
-            double ch = sn * sqrt(2.0 / (1.0 + sqrt(1.0 - sn * sn))) + 0x1p-20;
-            cn.vx = (float)(dP.x / D); cn.vy = (float)(dP.y / D); cn.vz = (float)(dP.z / D);
-            cn.chord = __double2float_ru(ch);
-        }
-    }
-    cone[k] = cn;
+    // Cone of directions from the eye that can hit sphere k (primary_cone_mask)
+    cone[k] = sphere_cone_record(dP.x, dP.y, dP.z, dd, r2);
 }
 
 // Eye-independent reciprocals of the division shortcuts (run by rt_set_scene): rcp_core of the checker
@@ -639,6 +624,11 @@ struct rt_ctx {
     int lmask_stride = 0;
     bool lmask_valid = false;
     bool level_masks = true;
+    // Sky tiles (rt_render.hpp render_body): waves whose primary rays provably all miss store the miss constants
+    // without tracing.  RT_SKY_TILES=0: every wave traces (A/B; the images are the same bytes).  The calibration render
+    // leaves its waves' verdicts behind the cone masks in d_cone_tile (sky_tiles_n of them: rt_diag_sky_count).
+    bool sky_tiles = true;
+    size_t sky_tiles_n = 0;
     // Cross-stream ordering of the per-view state: the per-eye records inside d_scene (rt_prepare_kernel) and the
     // calibration buffers (d_row_cost, d_tile_rows, d_tile_cost, d_cone_tile, d_disp).  Every render reads the per-eye
     // records; a render that prepares a new eye or calibrates also writes.  A writer records view_ev on its stream
@@ -753,7 +743,7 @@ static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
     const size_t slots = cone_slots(tiles);
     bool ok = hipMalloc(&c->d_disp, slots * sizeof(DispRec)) == hipSuccess &&
               hipMalloc(&c->d_tile_cost, tiles * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&c->d_cone_tile, tiles * sizeof(uint64_t)) == hipSuccess &&
+              hipMalloc(&c->d_cone_tile, 2 * tiles * sizeof(uint64_t)) == hipSuccess &&   // masks, then sky verdicts
               hipMalloc(&c->d_sort_keys, tiles * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&c->d_sort_in, tiles * sizeof(int32_t)) == hipSuccess &&
               hipMalloc(&c->d_sort_out, tiles * sizeof(int32_t)) == hipSuccess;
@@ -835,6 +825,7 @@ extern "C" int rt_ctx_create(int device, rt_ctx** out) {
     if (const char* e = getenv("RT_COPY_KERNEL")) c->copy_kernel = std::min(std::max(atoi(e), -1), 1);
     if (const char* e = getenv("RT_CONE_CACHE")) c->cone_cache = atoi(e) != 0;
     if (const char* e = getenv("RT_LEVEL_MASKS")) c->level_masks = atoi(e) != 0;
+    if (const char* e = getenv("RT_SKY_TILES")) c->sky_tiles = atoi(e) != 0;
     if (const char* e = getenv("RT_ORDER_POLICY")) c->order_policy = std::min(std::max(atoi(e), 0), 1);
     if (const char* e = getenv("RT_ACHRO_OFF")) c->achro_off = atoi(e) != 0;
     if (hipMalloc(&c->d_tile_rows, sizeof(int32_t) * kOrderMax) != hipSuccess ||
@@ -952,22 +943,17 @@ static int render_params(const rt_ctx* c, const rt_camera* cam, int W, int H, in
 #if RT_WAVE_TRACE
     P->wtrace = g_wtrace;
 #endif
-    // FP32 camera for the per-wave cone culling, and the bound on its error as a chord distance: every
-    // FP32 coordinate is below M in magnitude and carries < 16 roundings, and |sp - eye| >= |look - eye|
-    // (right, up' are orthogonal to look - eye), so direction errors are < 64 eps32 M / |look - eye|.
-    double M = 1.0, D2 = 0.0;
+    // FP32 camera for the per-wave cone culling, and the bound on its error (rt_cone.hpp)
+    const ConeCam C = cone_camera(P->look, P->right, P->upp, P->eye, P->pitch, P->bottom_x, P->bottom_y, W, H);
     for (int q = 0; q < 3; ++q) {
-        P->look32[q] = (float)P->look[q];
-        P->right32[q] = (float)P->right[q];
-        P->upp32[q] = (float)P->upp[q];
-        P->eye32[q] = (float)P->eye[q];
-        M = std::max(M, std::fabs(P->look[q]) + std::fabs(P->eye[q]));
-        D2 += (P->look[q] - P->eye[q]) * (P->look[q] - P->eye[q]);
+        P->look32[q] = C.look[q];
+        P->right32[q] = C.right[q];
+        P->upp32[q] = C.upp[q];
+        P->eye32[q] = C.eye[q];
     }
-    P->pitch32 = (float)P->pitch;
-    M += std::fabs(P->pitch) * (std::abs((double)P->bottom_x) + std::abs((double)P->bottom_y) + W + H + 16.0);
-    const double slack = 0x1p-16 + 64.0 * 0x1p-24 * M / std::sqrt(D2);
-    P->cone_slack = (D2 > 0.0 && slack < 0.25) ? (float)slack : 8.0f;   // 8: keep every sphere
+    P->pitch32 = C.pitch;
+    P->cone_slack = C.slack;
+    P->sky = c->sky_tiles ? 1 : 0;
     return RT_OK;
 }
 
@@ -1241,6 +1227,7 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
     c->order_key = J.key;                           // only once the order kernel is queued
     c->order_valid = true;
     c->cone_valid = J.cone_calib;
+    c->sky_tiles_n = J.cone_calib ? J.tiles : 0;
     c->lmask_valid = J.lm_calib;
     c->lmask_stride = J.lm_calib ? J.lm_stride : 0;
     c->stale = 0;
@@ -2180,6 +2167,23 @@ extern "C" int rt_diag_tile_order(rt_ctx* c, int mode) {
     c->order_mode = mode;
     c->order_valid = false;
     c->seen_valid = false;
+    return RT_OK;
+}
+
+// Diagnostics (include/rt_diag.h): the sky verdicts the waves of the context's last calibration render reached (and
+// every cached render of that view reads from its dispatch records), counted on the host.
+extern "C" int rt_diag_sky_count(rt_ctx* c, int* tiles, int* sky) {
+    if (!c || !tiles || !sky) return rt_fail(RT_EINVAL, "rt_diag_sky_count: bad args");
+    *tiles = *sky = 0;
+    if (!c->order_valid || !c->cone_valid || c->sky_tiles_n == 0) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipDeviceSynchronize());
+    std::vector<uint64_t> v(c->sky_tiles_n);
+    RT_HIP(hipMemcpy(v.data(), c->d_cone_tile + c->sky_tiles_n, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    int n = 0;
+    for (uint64_t x : v) n += x != 0;
+    *tiles = (int)v.size();
+    *sky = n;
     return RT_OK;
 }
 

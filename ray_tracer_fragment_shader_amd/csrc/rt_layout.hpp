@@ -16,7 +16,7 @@
 // then address every record at a constant offset from the scene pointer instead of holding six array pointers
 // in SGPRs (the SGPR budget of a seventh wave per SIMD).  The two *Prim arrays and DevSphereCone depend on
 // the camera eye and are (re)written on the device by rt_prepare_kernel whenever rt_render_dev sees a
-// new eye.
+// new eye, as are the header's per-eye fields (board_num, edge, hits_ok, prim_bound_ok).
 #pragma once
 
 #include <stdint.h>
@@ -112,6 +112,10 @@ struct alignas(16) DevSphereCone {     // primary rays: f32(unit(C - eye)) and t
     float vx, vy, vz, chord;           // sphere's cone of directions seen from the eye (rounded up)
 };
 
+struct alignas(16) DevBoardEdge {      // primary rays: f32 unit normal of the plane through the eye and one board
+    float mx, my, mz, mg;              // edge, towards the board, and the test's margin (rt_cone.hpp board_edge_record)
+};
+
 struct alignas(16) DevSphereLightF {   // shadow rays to light i: f32(unit(C - L)) and cos(phi) - margin,
     float vx, vy, vz, c;               // phi = asin(r / |C - L|); c = -inf: always test, +inf: never (padding)
 };
@@ -154,6 +158,7 @@ struct alignas(16) DevScene {
     DevTri tri[2];                     // board triangles T1 = (P1,P2,P3), T2 = (P1,P3,P4)   (:840-841)
     DevMat mat[5];                     // 0 white square, 1 black square, 2 sphere, 3 tetrahedron, 4 cube
     DevLight light[16];
+    DevBoardEdge edge[4];              // per eye: the board's four edges seen from the camera `eye` (rt_prepare_kernel)
 };
 
 inline constexpr int padded_spheres(int n) { return (n + kChunk - 1) / kChunk * kChunk; }

@@ -138,12 +138,13 @@ __host__ __device__ __forceinline__ size_t cone_slot(size_t L, size_t n) { retur
 __host__ __device__ __forceinline__ size_t cone_slots(size_t n) { return ((n + 7) >> 3) << 3; }
 
 // One dispatch position of a calibrated view (rt_kernel.hip rt_disp_kernel): the tile its workgroup traces
-// (ty << 16 | tx) and that tile's primary cone mask (valid when RenderParams::cone_use).  The table is indexed by
-// cone_slot(position): one 16-byte scalar load per wave brings both.
+// (ty << 16 | tx), that tile's primary cone mask and its sky verdict (1: no primary ray of the tile hits anything;
+// both valid when RenderParams::cone_use).  The table is indexed by cone_slot(position): one 16-byte scalar load per
+// wave brings all three.
 struct alignas(16) DispRec {
     uint32_t cone_lo, cone_hi;
     uint32_t tile;
-    uint32_t pad;
+    uint32_t sky;
 };
 
 struct RenderParams {
@@ -172,7 +173,9 @@ struct RenderParams {
     int32_t tiles_x;                           // tiles per tile row (= grid.x)
     uint64_t* wtrace;                          // RT_WAVE_TRACE builds: per-wave {start, end, HW_ID}
     int32_t cone_use;                          // 1: disp's cone masks are this view's (cached primary cone masks)
-    uint64_t* cone_out;                        // calibration render: each tile's mask, by tile (or nullptr)
+    int32_t sky;                               // 1: sky tiles take the early-out (RT_SKY_TILES; in cone_use's padding)
+    uint64_t* cone_out;                        // calibration render: each tile's mask, by tile, then each tile's sky
+                                               // verdict (tile_rows_n * tiles_x further on), or nullptr
     int32_t ns;                                // stride of the scene's per-sphere arrays (DevScene::n_stride)
     // Per-tile level masks (rt_device.hpp LevelMasks; culling kernels, one-wave tiles): lmask_stride slots per tile,
     // written by the calibration render (lmask_out) and read by later renders of exactly that view (lmask_in)
@@ -407,7 +410,6 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     constexpr bool kFixed = !LDS && !TRANSP && !CULL && !TREE && WG == RT_WG_FAST && RT_WG_FAST != kThreads;
     // (FIX64: the culling instance for scenes whose arrays have the stride kCullStride, see rt_layout.hpp)
     const SceneView V = view_of(S, gscene, P.np, kFixed ? kFastStride : FIX64 ? kCullStride : P.ns, P.nl);
-    const d3 eye = ld3(P.eye);
 
     const int wave = tid >> 6, lane = tid & 63;
     // The 32 x 8 tile (WG = 256) is cut into 4 wave blocks of 8 x 8 pixels (square blocks keep a wave's
@@ -425,6 +427,7 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     // early return: a branch here kept the compiler from issuing the scene loads until the tile had arrived).
     int tx = tile_col(bxd, gy, P.tiles_x), ty_raw = gy;
     uint64_t cone_cached = 0;
+    uint32_t sky_cached = 0;
     if (disp) {
 #if RT_DISP32
         // (32-bit index arithmetic: a frame's dispatch positions number < 2^31; cone_slot's value, fewer scalar ops
@@ -436,8 +439,9 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
         const size_t n = (size_t)geom.n, Lp = (size_t)gy * geom.tiles_x + bxd;
         const DispRec rec = disp[cone_slot(Lp < n ? Lp : n - 1, n)];   // (padding positions: in bounds, unused)
 #endif
-        asm volatile("" ::"s"(rec.cone_lo), "s"(rec.cone_hi), "s"(rec.tile));
+        asm volatile("" ::"s"(rec.cone_lo), "s"(rec.cone_hi), "s"(rec.tile), "s"(rec.sky));
         cone_cached = (uint64_t)rec.cone_lo | ((uint64_t)rec.cone_hi << 32);
+        sky_cached = rec.sky;
         tx = (int)(rec.tile & 0xffffu);
         ty_raw = Lp < n ? (int)(rec.tile >> 16) : P.tile_rows_n;
     }
@@ -457,22 +461,34 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
 
     // Per-wave sphere culling (all lanes active here).  The block's rows must be contiguous image rows.
     uint64_t cone = ~0ull;
+    // Sky tile (wave-uniform): no primary ray of the wave hits anything — the board provably missed (a proof like the
+    // cone mask's: rt_cone.hpp board_edge_record) and no sphere left in the cone mask, which covers every sphere of a
+    // scene of up to 64.  Opaque, mesh-free instances with one-wave tiles (the conditions of trace()'s lazy_u).
+    constexpr bool kSkyInst = !TRANSP && !TREE && !LDS && WG == 64;
+    bool sky = false;
     RT_COUNT(V.S, kCntWaves, 1);
     if (P.np >= kPrimaryConeMin && P.cone_use) {
-        // the mask this view's calibration render computed for this tile, in its dispatch record (rt_disp_kernel):
-        // no cone phase
+        // the mask and the verdict this view's calibration render computed for this tile, in its dispatch record
+        // (rt_disp_kernel): no cone phase
         cone = cone_cached;
+        sky = kSkyInst && sky_cached != 0;
     } else if (P.np >= kPrimaryConeMin) {
         // Within one frame global_row_of is increasing, so jb - ja == 7 means 8 consecutive rows.
         const int lr0 = ty * kTileH + by0, ja = global_row_of(P, lr0), jb = global_row_of(P, lr0 + bh - 1);
         const bool one_frame = P.frames <= 1 || lr0 / P.frame_rows == (lr0 + bh - 1) / P.frame_rows;
         const float hx = 0.5f * (float)(bw - 1), hy = 0.5f * (float)(bh - 1);
+        bool board_miss = false;
         if (one_frame && jb - ja == bh - 1)
             cone = primary_cone_mask(V, P.look32, P.right32, P.upp32, P.eye32, P.pitch32,
                                      (float)(tx * TW + bx0 + P.bottom_x) + hx, (float)(ja + P.bottom_y) + hy,
-                                     sqrtf(hx * hx + hy * hy), P.cone_slack, lane);
+                                     sqrtf(hx * hx + hy * hy), P.cone_slack, lane, &board_miss);
         RT_COUNT(V.S, kCntConeKept, __popcll(cone & sphere_bits(V.np)));
-        if (P.cone_out && tid == 0 && !pad) P.cone_out[(size_t)ty * P.tiles_x + tx] = cone;   // lane 0, vector store
+        sky = kSkyInst && P.sky && P.np <= 64 && board_miss && (cone & sphere_bits(V.np)) == 0;
+        if (P.cone_out && tid == 0 && !pad) {                // lane 0, vector stores
+            const size_t t = (size_t)ty * P.tiles_x + tx;
+            P.cone_out[t] = cone;
+            P.cone_out[(size_t)P.tile_rows_n * P.tiles_x + t] = sky;
+        }
     }
 #if RT_WAVE_TRACE >= 2
     asm volatile("" ::"s"(cone));
@@ -481,26 +497,38 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
 
     // Every lane traces (trace() reduces over the wave): lanes outside the frame trace a clamped pixel
     // and store nothing.
-    uint32_t seg = 0, sh = 0;
-    const int ic = i < P.width ? i : P.width - 1, lrc = lr < P.local_rows ? lr : P.local_rows - 1;
-    const int j = global_row_of(P, lrc);
-    const d3 right = ld3(P.right), upp = ld3(P.upp);
-    const d3 sp = screen_point(P, ic, j, right, upp);    // primary ray Line(camera, sp)
+    // A sky wave skips the screen points, the board test and trace(), and stores what trace() returns for 64 misses:
+    // colour 0, one ray segment, no shadow ray.  The epilogue below is the same for both.
+    // (The verdict is made a scalar again — it went through per-lane values on its way — so that the branch is a
+    // scalar one and no exec mask is held through trace().)
+    sky = __builtin_amdgcn_readfirstlane((int)sky) != 0;
+    uint32_t seg = 1, sh = 0;
+    d3 col = mk(0.0, 0.0, 0.0);
 #if RT_WAVE_TRACE
-    const uint64_t t_mid = __builtin_amdgcn_s_memrealtime();   // prologue done: the primary ray is formed
+    uint64_t t_mid = __builtin_amdgcn_s_memrealtime();      // (a sky wave: its verdict is known)
+#endif
+    if (!sky) {
+        const d3 eye = ld3(P.eye);
+        const int ic = i < P.width ? i : P.width - 1, lrc = lr < P.local_rows ? lr : P.local_rows - 1;
+        const int j = global_row_of(P, lrc);
+        const d3 right = ld3(P.right), upp = ld3(P.upp);
+        const d3 sp = screen_point(P, ic, j, right, upp);    // primary ray Line(camera, sp)
+#if RT_WAVE_TRACE
+        t_mid = __builtin_amdgcn_s_memrealtime();           // prologue done: the primary ray is formed
 #endif
 #if RT_ABLATE == 1
-    // (instruction-count ablation builds only, tools/ablate.sh: the prologue alone — no trace, no stores)
-    asm volatile("" ::"v"(sp.x), "v"(sp.y), "v"(sp.z), "s"(cone));
-    return;
+        // (instruction-count ablation builds only, tools/ablate.sh: the prologue alone — no trace, no stores)
+        asm volatile("" ::"v"(sp.x), "v"(sp.y), "v"(sp.z), "s"(cone));
+        return;
 #endif
-    d3 col;
-    LevelMasks lm{-1};
-    if (RT_LEVEL_MASKS && !TRANSP && !TREE && P.lmask_stride > 0 && !pad) lm.tile = (ty * P.tiles_x + tx) * P.lmask_stride;
-    if constexpr (TREE)
-        col = trace_tree<B>(V, eye, sp, &seg, &sh);
-    else
-        col = trace<B, true, TRANSP, CULL, WG, ACHRO>(V, eye, sp, cone, &seg, &sh, slot, mslot, lm);
+        LevelMasks lm{-1};
+        if (RT_LEVEL_MASKS && !TRANSP && !TREE && P.lmask_stride > 0 && !pad)
+            lm.tile = (ty * P.tiles_x + tx) * P.lmask_stride;
+        if constexpr (TREE)
+            col = trace_tree<B>(V, eye, sp, &seg, &sh);
+        else
+            col = trace<B, true, TRANSP, CULL, WG, ACHRO>(V, eye, sp, cone, &seg, &sh, slot, mslot, lm);
+    }
 #if RT_WAVE_TRACE >= 2
     asm volatile("" ::"v"(col.x), "v"(col.y), "v"(col.z));
     const uint64_t t_trace = __builtin_amdgcn_s_memrealtime();   // trace() done, the stores next
