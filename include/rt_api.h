@@ -387,6 +387,59 @@ int rt_render_soft(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int
                    int samples, double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                    rt_stats* stats);
 
+/* ---- motion blur (ABI 10: new symbols only) --------------------------------------------------------- */
+/* Moving spheres: the S x S samples of a pixel see the scene at S x S shutter times, so a moving sphere, its shadow and
+ * its reflections are blurred along its path.  Deterministic, and defined entirely by rt_set_scene and
+ * rt_trace_rays_dev on scenes and rays this text spells out.  For a full width x height frame, S = `samples` in
+ * {1, 2, 4, 8}, A = `aperture` and R = `light_size`, both finite and >= 0, F = `shutter`, finite and in [0, 1], and the
+ * displacements d_k of rt_set_motion (d[3 k + c]: half-extent of sphere k's motion during the exposure, scene-local):
+ *  1. Rays and lights.  Exactly rt_render_soft_dev rules 1-2: the lens point, the sub-pixel point and the light point
+ *     of the same (a, b).
+ *  2. Time of a sample.  Sample (a, b) has the time index n = a + S b and the time
+ *         sigma = F * u_n,   u_n = (double)(2 n + 1 - S S) / (double)(S S)
+ *     (an exact quotient; sigma is one multiplication): S S distinct times per pixel, symmetric about 0, |sigma| < 1.
+ *  3. Spheres of a sample.  Sphere k has the scene-local centre center[c] + (sigma * d_k[c]) per component: one
+ *     multiplication, then one addition.  Radii, board, meshes, lights (apart from rule 1), materials and the bounding
+ *     sphere are unchanged.
+ *  4. Value.  The colour and the counters of a sample are what rt_trace_rays_dev gives its ray after rt_set_scene of
+ *     the scene of rules 1 and 3 (which forms the world centre as that value + scene.position, one more addition).
+ *  5. Reduction and outputs follow rt_render_ss_dev rules 3-5 exactly.
+ *  6. Pins that follow, with NO shortcut in the implementation (all run the same kernel): F = 0 writes the images and
+ *     counters rt_render_soft_dev writes, for any A and R; so do all d = 0, and a context with no motion set.  With
+ *     R = 0 as well the output is rt_render_dof_dev's, with A = R = 0 rt_render_ss_dev's; S = 1 (sigma = 0) writes the
+ *     images rt_render_dev writes.  The pins assume that no sphere centre has a -0.0 component.
+ *  7. rt_set_motion copies the displacements and builds the device record the kernel reads (the swept spheres' filter
+ *     records and bounding proof).  n_spheres must equal the uploaded scene's, else RT_EINVAL; (NULL, 0) clears the
+ *     motion.  A CHANGED rt_set_scene also clears it; an identical scene (a no-op in rt_set_scene) keeps it.  It
+ *     follows rt_set_scene's ordering rule: a changed motion first waits for all work on the context's device.  It may
+ *     allocate, so it is not capturable.  The context's scene record is read, never written: every other call on the
+ *     context gives exactly what it gave before.
+ *  8. rt_render_motion_dev: full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host
+ *     synchronisation, so the call may be captured in a hipGraph.  No per-view state; it neither reads nor writes the
+ *     cone masks, the level masks or the tile order.
+ *  9. RT_EINVAL (rt_last_error names the argument) for `samples` outside {1, 2, 4, 8}, an `aperture` or a `light_size`
+ *     that is negative, NaN or infinite, a `shutter` that is negative, above 1, NaN or infinite, a non-finite
+ *     displacement, a wrong n_spheres, a bad frame size, and an int32 overflow of the sample-grid camera.  A rejected
+ *     call writes no pixel.
+ * 10. Not offered: moving meshes, board, lights or camera; curved or accelerated paths; jittered times; a pairing of
+ *     time with (a, b) other than rule 2.  A streak is therefore a sum of at most S S copies, the same in every pixel.
+ *     rt_render_multi, the packed and asynchronous host paths and the drop-in draw() stay frozen in time.
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, one sphere moving by |d| = 40, F = 1, A = R = 0, RGBA32F + RGBA8,
+ * tools/bench_motion.py): S = 2 139 us and S = 4 565 us per frame, 1.05 x and 1.06 x rt_render_soft_dev at the same S
+ * (the price of per-lane sphere centres and swept filter records), 1.9 x and 1.8 x rt_render_ss_dev, and 3.6 x and
+ * 2.9 x faster than S x S calls of rt_trace_rays_dev on pre-uploaded displaced scenes with the reduction in further
+ * passes (5.4 x and 4.6 x with the rt_set_scene uploads).  Other scenes, depths and motions: not measured. */
+int rt_set_motion(rt_ctx* ctx, const double* displacement, int n_spheres);
+/* Device pointers, each output nullable, width * height pixels. */
+int rt_render_motion_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples,
+                         double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                         double* rgb64f, uint32_t* raycount2, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_soft: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the frame.  *stats as rt_render_soft. */
+int rt_render_motion(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam, int width,
+                     int height, int depth, int samples, double aperture, double light_size, double shutter,
+                     float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
+
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.
  * GRAY formats hold the R channel only and are accepted only for an ACHROMATIC scene (rt_scene_achromatic):

@@ -190,6 +190,11 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_render_soft": (c_int, [c_void_p, _P(rt_scene), _P(rt_camera), c_int, c_int, c_int, c_int, c_double, c_double,
                                c_void_p, c_void_p, c_void_p, _P(rt_stats)]),
+    "rt_set_motion": (c_int, [c_void_p, _P(c_double), c_int]),
+    "rt_render_motion_dev": (c_int, [c_void_p, _P(rt_camera), c_int, c_int, c_int, c_int, c_double, c_double,
+                                     c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_render_motion": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int,
+                                 c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, _P(rt_stats)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

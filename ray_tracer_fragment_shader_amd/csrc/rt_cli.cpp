@@ -31,6 +31,11 @@
 //   rt_render --config c2 --samples 4 --light-size 40 [--aperture 8 [--focus 0.8]] --out c2_soft.ppm
 //                                                  soft shadows: every light a square panel of half-width 40 in the
 //                                                  world xz-plane, one of its S x S points per sample (rt_render_soft)
+//   rt_render --config c2 --samples 4 --shutter 1 --move 0:40,0,0 [--move K:DX,DY,DZ ...] [--light-size 40]
+//             [--aperture 8 [--focus 0.8]] --out c2_motion.ppm
+//                                                  motion blur: sphere 0 moves by +-(40, 0, 0) (scene-local) during the
+//                                                  exposure, of which the shutter is open for the share 1; each of the
+//                                                  S x S samples has its own time (rt_render_motion)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -67,6 +72,10 @@ struct Options {
     double focus_ratio = 1.0;
     bool soft = false;                       // --light-size R: rt_render_soft with panel half-width R (needs --samples)
     double light_size = 0.0;
+    bool motion = false;                     // --shutter F: rt_render_motion with the --move displacements (needs --samples)
+    double shutter = 0.0;
+    std::vector<int> move_k;                 // --move K:DX,DY,DZ (repeatable): sphere K's displacement
+    std::vector<double> move_d;
 };
 
 // A finite number that fills the whole argument, or a usage error.
@@ -78,6 +87,20 @@ double number_arg(const std::string& flag, const std::string& v) {
         std::exit(2);
     }
     return x;
+}
+
+// --move K:DX,DY,DZ: a sphere index and three finite numbers, or a usage error.
+void move_arg(const std::string& v, Options* o) {
+    int k = -1, used = 0;
+    double d[3];
+    if (std::sscanf(v.c_str(), "%d:%lf,%lf,%lf%n", &k, &d[0], &d[1], &d[2], &used) != 4 || used != (int)v.size() ||
+        k < 0 || !std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) {
+        std::fprintf(stderr, "rt_render: --move needs K:DX,DY,DZ (a sphere index and three numbers), got '%s'\n",
+                     v.c_str());
+        std::exit(2);
+    }
+    o->move_k.push_back(k);
+    o->move_d.insert(o->move_d.end(), d, d + 3);
 }
 
 [[noreturn]] void die(const std::string& what, int code) {
@@ -209,10 +232,12 @@ int main(int argc, char** argv) {
         else if (a == "--aperture") { o.dof = true; o.aperture = number_arg(a, next()); }
         else if (a == "--focus") { o.focus = true; o.focus_ratio = number_arg(a, next()); }
         else if (a == "--light-size") { o.soft = true; o.light_size = number_arg(a, next()); }
+        else if (a == "--shutter") { o.motion = true; o.shutter = number_arg(a, next()); }
+        else if (a == "--move") move_arg(next(), &o);
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
     }
@@ -237,6 +262,19 @@ int main(int argc, char** argv) {
     }
     if (o.soft && o.light_size < 0.0) {
         std::fprintf(stderr, "rt_render: --light-size must be >= 0\n");
+        return 2;
+    }
+    if (o.motion && (o.samples == 0 || o.adaptive || o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --shutter needs --samples, excludes --adaptive and applies to plain frames "
+                             "(not --faithful or --gpus)\n");
+        return 2;
+    }
+    if (o.motion && !(o.shutter >= 0.0 && o.shutter <= 1.0)) {
+        std::fprintf(stderr, "rt_render: --shutter must be in [0, 1]\n");
+        return 2;
+    }
+    if (!o.motion && !o.move_k.empty()) {
+        std::fprintf(stderr, "rt_render: --move needs --shutter\n");
         return 2;
     }
     if (o.focus && (!o.dof || !(o.focus_ratio > 0.0))) {
@@ -327,6 +365,15 @@ int main(int argc, char** argv) {
         pitch = o.pitch > 0 ? o.pitch : 500.0 / W;          // canonical framing
     }
 
+    std::vector<double> displacement((size_t)3 * (size_t)std::max(scene.n_spheres, 1), 0.0);
+    for (size_t m = 0; m < o.move_k.size(); ++m) {
+        if (o.move_k[m] >= scene.n_spheres) {
+            std::fprintf(stderr, "rt_render: --move %d: the scene has %d spheres\n", o.move_k[m], scene.n_spheres);
+            return 2;
+        }
+        for (int q = 0; q < 3; ++q) displacement[3 * (size_t)o.move_k[m] + q] = o.move_d[3 * m + q];
+    }
+
     rt_camera cam;
     check(rt_camera_init_reference(&cam, W, H, pitch), "rt_camera_init_reference");
     if (o.focus) check(rt_camera_focus(&cam, o.focus_ratio, &cam), "rt_camera_focus");
@@ -355,7 +402,10 @@ int main(int argc, char** argv) {
     uint64_t n_refined = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < o.repeat; ++k) {
-        if (o.soft)
+        if (o.motion)
+            check(rt_render_motion(ctx, &scene, displacement.data(), &cam, W, H, depth, o.samples, o.aperture,
+                                   o.light_size, o.shutter, nullptr, rgba8.data(), nullptr, &st), "rt_render_motion");
+        else if (o.soft)
             check(rt_render_soft(ctx, &scene, &cam, W, H, depth, o.samples, o.aperture, o.light_size, nullptr,
                                  rgba8.data(), nullptr, &st), "rt_render_soft");
         else if (o.dof)
@@ -379,7 +429,11 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.soft)
+    if (o.motion)
+        std::printf("rt_render: motion blur, shutter %g, %d moving spheres, light half-width %g, lens half-width %g: "
+                    "%d x %d shutter times per pixel, %llu primary rays\n", o.shutter, (int)o.move_k.size(),
+                    o.light_size, o.aperture, o.samples, o.samples, (unsigned long long)st.primary_rays);
+    else if (o.soft)
         std::printf("rt_render: soft shadows, light half-width %g, lens half-width %g: %d x %d light samples per "
                     "pixel, %llu primary rays\n", o.light_size, o.aperture, o.samples, o.samples,
                     (unsigned long long)st.primary_rays);

@@ -401,6 +401,28 @@ __device__ __forceinline__ void set_dir(Ray* r, d3 d, d3 u) {
     r->uz = (float)u.z;
 }
 
+// MOTION (motion blur, rt_render_motion_dev): this lane's sample has the time `sigma`, and sees sphere k at
+//     (cl_k + sigma * d_k) + pos
+// (one multiplication, then two additions per component: the scene-local centre displaced, then rt_set_scene's
+// "+ scene.position"), a per-lane value built from the wave-uniform records of the context's motion record M
+// (rt_layout.hpp DevMotion).  Radii, board, meshes, lights, materials and the bounding sphere are the scene record's.
+// Every use of a sphere centre on the generic path takes this value instead of DevSphere::c — the exact test
+// (sphere_hit_at), the self skip (origin_skip) and the normal (surface) — and the FP32 filter reads the records of the
+// SWEPT spheres (motion_filter), which reject a sphere only where every position it takes is missed.
+struct Motion {
+    double sigma;
+    const DevMotion* M;
+};
+
+__device__ __forceinline__ d3 motion_centre(const Motion& mo, int k) {
+    const DevMotionSphere& ms = reinterpret_cast<const DevMotionSphere*>(mo.M + 1)[k];
+    return add(add(ld3(ms.cl), scl(mo.sigma, ld3(ms.d))), ld3(mo.M->pos));
+}
+
+__device__ __forceinline__ const DevSphereF* motion_filter(const Motion& mo) {
+    return reinterpret_cast<const DevSphereF*>(reinterpret_cast<const DevMotionSphere*>(mo.M + 1) + mo.M->n_stride);
+}
+
 // ------------------------------------------------------------------------------------------------
 // g_scene bounding-sphere cull (:747-758): miss iff disc < 0 or |s| < eps.
 // Shortcut: if dd = |bc - p0|^2 < (R-1)^2 the cull passes.  Proof: m = R^2 - dd >= 2R - 1 > 0, so
@@ -561,12 +583,17 @@ __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p)
 //    |s| <= sqrt(|g| + E) + 2^-51 sqrt(dd + r2) < eps when |g| + E < eps^2 / 4 (self_eps2): the near root
 //    misses (:754, :767) — the reference never uses the far root.
 // NaN / inf operands fail the compares (no skip).  Returns -1 (no skip), 0 (board) or 1 + k (sphere k).
-__device__ __forceinline__ int origin_skip(const SceneView& V, int kind, d3 p0, d3 q) {
+// MOTION: C is the lane's own centre of sphere k (motion_centre), the centre q was found on and the one every ray
+// from q is tested against (sphere_hit_at, same operations): the argument above is about that C, whatever its value.
+template <bool MOTION = false>
+__device__ __forceinline__ int origin_skip(const SceneView& V, int kind, d3 p0, d3 q,
+                                           const Motion* mo = nullptr) {
     const DevScene* S = V.S;
     if (RT_BOARD_SKIP && kind == 0) return fabs(p0.y) <= S->board_skip_y ? 0 : -1;
     if (RT_SELF_SKIP && kind >= 1 && kind < kMeshKind) {
         const DevSphere& sp = V.sph[kind - 1];
-        const d3 dP = sub(ld3(sp.c), q);
+        d3 dP = sub(ld3(sp.c), q);
+        if constexpr (MOTION) dP = sub(motion_centre(*mo, kind - 1), q);
         const double dd = dot(dP, dP);
         return fabs(sp.r2 - dd) + 0x1p-49 * (dd + sp.r2) < S->self_eps2 ? kind : -1;
     }
@@ -710,6 +737,12 @@ __device__ __forceinline__ bool sphere_hit(const DevSphere& sp, d3 p0, d3 u, dou
     return sphere_hit_dp(dP, dot(dP, dP), sp.r2, p0, u, eps, p);
 }
 
+// The same test with the centre given (MOTION: the lane's own, motion_centre).
+__device__ __forceinline__ bool sphere_hit_at(d3 c, double r2, d3 p0, d3 u, double eps, d3* p) {
+    d3 dP = sub(c, p0);                                     // :740
+    return sphere_hit_dp(dP, dot(dP, dP), r2, p0, u, eps, p);
+}
+
 // Bits of the spheres a 64-bit mask may name: k < min(np, 64).
 __device__ __forceinline__ uint64_t sphere_bits(int np) { return np >= 64 ? ~0ull : ((1ull << np) - 1); }
 
@@ -751,8 +784,12 @@ __device__ __forceinline__ void take_closer(d3 p0, d3 q, int k, int* kind, doubl
 #ifndef RT_SEC_PREFETCH
 #define RT_SEC_PREFETCH 0
 #endif
+// MOTION: the filter records of the swept spheres, the exact test on the lane's centres (struct Motion).
+template <bool MOTION = false>
 __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const Ray& r, int k0, double eps,
-                                                     int* kind, double* best, d3* hp, int self = -1) {
+                                                     int* kind, double* best, d3* hp, int self = -1,
+                                                     const Motion* mo = nullptr) {
+    static_assert(!(MOTION && RT_SEC_PREFETCH), "the prefetched records hold the stored centres");
     uint32_t pass = 0;
 #if RT_SEC_PREFETCH
     // the batch's exact-test records requested with its filter records (one wait for all)
@@ -763,6 +800,11 @@ __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const R
 #endif
 #pragma unroll
     for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(V.sphf[k0 + j], r) ? 0u : 1u) << j;
+    if constexpr (MOTION) {                                 // (the static records' bits are dead code then)
+        pass = 0;
+#pragma unroll
+        for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(motion_filter(*mo)[k0 + j], r) ? 0u : 1u) << j;
+    }
     pass = drop_self(pass, self, k0);                       // r starts on sphere `self`: a certain miss
 #if RT_UNIFORM_SECONDARY
 #pragma unroll
@@ -782,6 +824,10 @@ __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const R
         pass &= pass - 1;
 #endif
         d3 q;
+        if constexpr (MOTION) {
+            if (sphere_hit_at(motion_centre(*mo, k), V.sph[k].r2, r.p0, r.u, eps, &q))
+                take_closer(r.p0, q, 1 + k, kind, best, hp);
+        } else
         if (sphere_hit(V.sph[k], r.p0, r.u, eps, &q)) take_closer(r.p0, q, 1 + k, kind, best, hp);   // :811-813
     }
 }
@@ -790,9 +836,11 @@ __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const R
 // first 64 are skipped.  Spheres are visited in increasing k either way.
 // skip = origin_skip of r's origin: 0 skips the board test, 1 + k sphere k's (certain misses).
 // from_hit: r starts at a hit point, which passes the cull when S->hits_inside (host-proven).
-template <bool FULL, bool CULL = false>
+// MOTION, mo: the lane's sphere centres (struct Motion); generic path only.
+template <bool FULL, bool CULL = false, bool MOTION = false>
 __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3* hp, uint64_t mask = ~0ull,
-                                           int skip = -1, bool from_hit = false) {
+                                           int skip = -1, bool from_hit = false, const Motion* mo = nullptr) {
+    static_assert(!(MOTION && CULL), "moving spheres take the generic path");
     const DevScene* S = V.S;
     if (!(RT_HITS_INSIDE && from_hit && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return -1;
     int kind = -1;
@@ -829,7 +877,7 @@ __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3*
         // (a batch none of whose spheres the mask keeps is missed by every ray of the wave: the cached masks of the
         // fast kernels, LevelMasks; ~0 otherwise)
         if (k0 < 64 && ((mask >> k0) & ((1ull << kChunk) - 1)) == 0) continue;
-        sphere_batch_closest(V, r, k0, eps, &kind, &best, hp, skip - 1);
+        sphere_batch_closest<MOTION>(V, r, k0, eps, &kind, &best, hp, skip - 1, mo);
     }
     if (FULL) meshes_closest(V, r, eps, &kind, &best, hp);
     return kind;
@@ -1272,7 +1320,10 @@ __device__ __forceinline__ bool occluded(const SceneView& V, const Ray& r, int l
 // What is kept argues from the ray's origin alone, which is still a hit point: the bounding-sphere shortcut
 // (hits_inside: a hit point lies inside the shortcut radius, so the cull passes for every direction, bound_pass_dp)
 // and `skip` (origin_skip: "any ray from q" misses the board / sphere q lies on).  Opaque scenes only (any hit blocks).
-__device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray& r, int skip = -1) {
+// MOTION, mo: the lane's sphere centres (struct Motion).
+template <bool MOTION = false>
+__device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray& r, int skip = -1,
+                                                  const Motion* mo = nullptr) {
     const DevScene* S = V.S;
     if (!(RT_HITS_INSIDE && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return false;
     const double eps = S->eps;
@@ -1285,11 +1336,17 @@ __device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray&
         uint32_t pass = 0;
 #pragma unroll
         for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(V.sphf[k0 + j], r) ? 0u : 1u) << j;
+        if constexpr (MOTION) {
+            pass = 0;
+#pragma unroll
+            for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(motion_filter(*mo)[k0 + j], r) ? 0u : 1u) << j;
+        }
         pass = blocked ? 0u : drop_self(pass, skip - 1, k0);
         while (pass) {
             const int k = k0 + __builtin_ctz(pass);
             d3 q;
             blocked = sphere_hit(V.sph[k], r.p0, r.u, eps, &q);
+            if constexpr (MOTION) blocked = sphere_hit_at(motion_centre(*mo, k), V.sph[k].r2, r.p0, r.u, eps, &q);
             pass = blocked ? 0u : pass & (pass - 1);
         }
     }
@@ -1320,9 +1377,11 @@ __device__ __forceinline__ int material_of(const SceneView& V, int kind, d3 p) {
 }
 
 // Shadow test when some material is transparent: the closest blocker decides (:1219-1221).
-__device__ __forceinline__ bool occluded_transparent(const SceneView& V, const Ray& r) {
+template <bool MOTION = false>
+__device__ __forceinline__ bool occluded_transparent(const SceneView& V, const Ray& r,
+                                                     const Motion* mo = nullptr) {
     d3 p;
-    int kind = closest_hit<true>(V, r, &p, ~0ull, -1, true);        // shadow rays start at hits
+    int kind = closest_hit<true, false, MOTION>(V, r, &p, ~0ull, -1, true, mo);   // shadow rays start at hits
     if (kind < 0) return false;
     return V.S->mat[material_of(V, kind, p)].transparent == 0;
 }
@@ -1345,8 +1404,10 @@ __device__ __forceinline__ d3 transmitted_end(const SceneView& V, int kind, int 
 #ifndef RT_CENTER_UNIFORM
 #define RT_CENTER_UNIFORM 0
 #endif
-template <bool MESH = true>
-__device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u, d3* n, int* mat, d3* pe) {
+template <bool MESH = true, bool MOTION = false>
+__device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u, d3* n, int* mat, d3* pe,
+                                        const Motion* mo = nullptr) {
+    static_assert(!(MOTION && RT_CENTER_UNIFORM), "the lane's centre is not wave-uniform");
     const DevScene* S = V.S;
     if (kind == 0) {
         *n = ld3(S->tri[0].n);
@@ -1371,6 +1432,7 @@ __device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u
 #else
         d3 c = ld3(V.sph[kind - 1].c);
 #endif
+        if constexpr (MOTION) c = motion_centre(*mo, kind - 1);   // the centre this lane's ray hit
         d3 dp = sub(p, c);                                  // directionP0 (:763)
         *n = unit(dp);                                      // :774-775
     }
@@ -1413,11 +1475,15 @@ __device__ __forceinline__ uint64_t* level_masks_out();
 struct LightShift {
     double x, z;
 };
-template <bool FULL, bool CULL, bool ACC = false, int SS = 256, bool ACHRO = false, bool AREA = false>
+// MOTION, mo (with AREA): the shadow tests run on the lane's sphere centres (struct Motion).
+template <bool FULL, bool CULL, bool ACC = false, int SS = 256, bool ACHRO = false, bool AREA = false,
+          bool MOTION = false>
 __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, int mat, double ks,
                                     int skip = -1, double* acc = nullptr, const LevelMasks* lm = nullptr,
-                                    int lslot = 0, LightShift ls = LightShift{0.0, 0.0}) {
+                                    int lslot = 0, LightShift ls = LightShift{0.0, 0.0},
+                                    const Motion* mo = nullptr) {
     static_assert(!(ACHRO && FULL), "achromatic shading is for opaque scenes");
+    static_assert(!MOTION || AREA, "moving spheres: no light-cone records, no masks (the AREA shadow tests)");
     static_assert(!(AREA && (CULL || ACHRO)), "area lights take the generic path");
     const DevScene* S = V.S;
     d3 color = mk(0.0, 0.0, 0.0);
@@ -1461,8 +1527,8 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         }
         bool lit = false;
         if (hit)
-            lit = !(FULL ? occluded_transparent(V, sr)
-                    : AREA ? occluded_anywhere(V, sr, skip)
+            lit = !(FULL ? occluded_transparent<MOTION>(V, sr, mo)
+                    : AREA ? occluded_anywhere<MOTION>(V, sr, skip, mo)
                            : occluded<false, CULL, RT_OCCL_FLAT && (ACHRO || !CULL)>(V, sr, i, m, skip));
         if (lit && ACHRO) {                                 // R only (same operations as below, channel x)
             const double a = S->att / (S->att + dl * dl);   // attenuation (:1181)
@@ -1668,11 +1734,15 @@ __device__ __forceinline__ bool cull_level(const SceneView& V, int lvl, bool fir
 }
 
 // AREA: every light displaced by `ls` for this lane (shade AREA); generic path only (no PRIMARY, no CULL, no masks).
-template <int B, bool PRIMARY, bool TRANSP, bool CULL, int SS = kSlotStride, bool ACHRO = false, bool AREA = false>
+// MOTION: every sphere at this lane's own centre (struct Motion); with AREA only.
+template <int B, bool PRIMARY, bool TRANSP, bool CULL, int SS = kSlotStride, bool ACHRO = false, bool AREA = false,
+          bool MOTION = false>
 __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t cone,
                                     uint32_t* seg, uint32_t* shadow, double* slot, int* mslot,
-                                    LevelMasks lm = LevelMasks{-1}, LightShift ls = LightShift{0.0, 0.0}) {
+                                    LevelMasks lm = LevelMasks{-1}, LightShift ls = LightShift{0.0, 0.0},
+                                    const Motion* mo = nullptr) {
     static_assert(!(AREA && (PRIMARY || CULL || ACHRO)), "area lights take the generic path");
+    static_assert(!MOTION || AREA, "moving spheres take the generic path, with the area lights' shadow tests");
     const DevScene* S = V.S;
     int levels = 0;
     Ray r;
@@ -1717,11 +1787,11 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
                         const uint64_t* in = level_masks_in();
                         if (in) rm = in[lm.tile + lvl - 1];
                     }
-                    kind = closest_hit<TRANSP>(V, r, &p, rm, TRANSP ? -1 : skip, lvl > 0);
+                    kind = closest_hit<TRANSP, false, MOTION>(V, r, &p, rm, TRANSP ? -1 : skip, lvl > 0, mo);
                 }
             }
             const bool hit = kind >= 0;
-            skip = kSkip ? origin_skip(V, kind, r.p0, p) : -1;   // this hit's rays start at p
+            skip = kSkip ? origin_skip<MOTION>(V, kind, r.p0, p, mo) : -1;   // this hit's rays start at p
             d3 nd = mk(0.0, 0.0, 0.0);
 #if RT_KEEP_NU || RT_PARK_NU
             d3 nu = nd;
@@ -1729,7 +1799,7 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
             if (hit) {
                 d3 n, pe;
                 int mat;
-                surface<TRANSP || !RT_MESH_STATIC>(V, kind, p, r.u, &n, &mat, &pe);
+                surface<TRANSP || !RT_MESH_STATIC, MOTION>(V, kind, p, r.u, &n, &mat, &pe, mo);
                 const d3 rd = sub(pe, p);                   // reflectedRay = Line(p, p + r)
                 const d3 rdir = unit(rd);                   // reflectedRay.direction()
                 const double ks = fabs(dot(r.u, rdir));     // |u . reflectedRay.direction()|
@@ -1758,8 +1828,8 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
                     ndsl[2 * SS] = nd.z;
                     asm volatile("" ::: "memory");          // keep it in LDS across the light loop
                 }
-                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA>(V, true, p, n, mat, ks, skip, psl, &lm,
-                                                                         B + lvl * V.nl, ls);
+                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA, MOTION>(V, true, p, n, mat, ks, skip, psl, &lm,
+                                                                                 B + lvl * V.nl, ls, mo);
                 if ((kPark || RT_PARK_NU) && lvl < B) {
                     asm volatile("" ::: "memory");
                     nd = mk(ndsl[0], ndsl[SS], ndsl[2 * SS]);
@@ -1810,23 +1880,25 @@ struct TreeNode {
 };
 
 // Trace Line(a, a + d) as node k: closest hit, local colour; false on a miss.  AREA, ls: shade's.
-template <bool AREA = false>
+template <bool AREA = false, bool MOTION = false>
 __device__ __forceinline__ bool tree_eval(const SceneView& V, d3 a, d3 d, TreeNode* node, uint32_t* nseg,
-                                          uint32_t* nsh, LightShift ls = LightShift{0.0, 0.0}) {
+                                          uint32_t* nsh, LightShift ls = LightShift{0.0, 0.0},
+                                          const Motion* mo = nullptr) {
     Ray r;
     r.p0 = a;
     set_dir(&r, d, unit(d));
     set_origin_f32(V.S, &r);
     ++*nseg;
     d3 p;
-    const int kind = closest_hit<true>(V, r, &p);
+    const int kind = closest_hit<true, false, MOTION>(V, r, &p, ~0ull, -1, false, mo);
     if (kind < 0) return false;
     d3 n, pe;
     int mat;
-    surface(V, kind, p, r.u, &n, &mat, &pe);
+    surface<true, MOTION>(V, kind, p, r.u, &n, &mat, &pe, mo);
     const d3 rd = sub(pe, p);                               // reflectedRay = Line(p, p + r)
     const double ks = fabs(dot(r.u, unit(rd)));             // |u . reflectedRay.direction()|
-    node->acc = shade<true, false, false, 256, false, AREA>(V, true, p, n, mat, ks, -1, nullptr, nullptr, 0, ls);
+    node->acc = shade<true, false, false, 256, false, AREA, MOTION>(V, true, p, n, mat, ks, -1, nullptr, nullptr, 0, ls,
+                                                                    mo);
     *nsh += V.nl;
     node->p = p;
     node->rd = rd;
@@ -1836,13 +1908,13 @@ __device__ __forceinline__ bool tree_eval(const SceneView& V, d3 a, d3 d, TreeNo
     return true;
 }
 
-template <int B, bool AREA = false>
+template <int B, bool AREA = false, bool MOTION = false>
 __device__ __forceinline__ d3 trace_tree(const SceneView& V, d3 p0, d3 p1, uint32_t* seg, uint32_t* shadow,
-                                         LightShift ls = LightShift{0.0, 0.0}) {
+                                         LightShift ls = LightShift{0.0, 0.0}, const Motion* mo = nullptr) {
     TreeNode st[B + 1];
     uint32_t nseg = 0, nsh = 0;
     d3 col = mk(0.0, 0.0, 0.0);
-    if (tree_eval<AREA>(V, p0, sub(p1, p0), &st[0], &nseg, &nsh, ls)) {
+    if (tree_eval<AREA, MOTION>(V, p0, sub(p1, p0), &st[0], &nseg, &nsh, ls, mo)) {
         int k = 0;
         for (;;) {
             TreeNode& f = st[k];
@@ -1850,14 +1922,14 @@ __device__ __forceinline__ d3 trace_tree(const SceneView& V, d3 p0, d3 p1, uint3
                 const DevMat& M = V.S->mat[f.mat];
                 if (f.state == 0) {
                     f.state = 1;
-                    if (M.transmit && tree_eval<AREA>(V, f.p, f.td, &st[k + 1], &nseg, &nsh, ls)) {
+                    if (M.transmit && tree_eval<AREA, MOTION>(V, f.p, f.td, &st[k + 1], &nseg, &nsh, ls, mo)) {
                         ++k;
                         continue;
                     }
                 }
                 if (f.state == 1) {
                     f.state = 2;
-                    if (M.reflect && tree_eval<AREA>(V, f.p, f.rd, &st[k + 1], &nseg, &nsh, ls)) {
+                    if (M.reflect && tree_eval<AREA, MOTION>(V, f.p, f.rd, &st[k + 1], &nseg, &nsh, ls, mo)) {
                         ++k;
                         continue;
                     }

@@ -672,6 +672,89 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
     return RT_OK;
 }
 
+// The motion record of rt_set_motion (rt_layout.hpp DevMotion) for the flattened scene `blob`, the scene-local sphere
+// centres cl[3 n] that scene was built from and the displacements disp[3 n] (null: none).  For sphere k with the
+// stored world centre c0 = cl + bc, every sample's centre c = (cl + sigma d) + bc, |sigma| < 1, lies within
+//     rho - r,   rho = (r + |d|) (1 + 2^-30) + 2^-40 max_i(|cl_i| + |d_i| + |bc_i|)
+// of c0: |sigma d| < |d|, and the three roundings of c and the one of c0 move a component by at most
+// 2^-51 (|cl_i| + |d_i| + |bc_i|).  So the sample's sphere lies inside the SWEPT sphere (c0, rho), and
+//  * the FP32 filter record of sphere k is DevSphereF's formula on (c0, rho): the filter rejects a ray only when its
+//    line misses the swept sphere, by the margin that DESIGN.md 5h turns into "the exact test on c computes disc < 0";
+//  * hits_inside / hits_lim2 are rt_build_dev_scene's proof with every sphere's extent |c0 - bc| + rho: a hit point of
+//    a sample lies on a sphere inside the swept one.  The other extents (board corners, meshes' bounding spheres) are
+//    read back from the record; the flag is only ever set where the scene's own is.
+int rt_build_motion(const std::vector<unsigned char>& blob, const double* cl, const double* disp, int n,
+                    std::vector<unsigned char>* out) {
+    const rt::DevScene* d = reinterpret_cast<const rt::DevScene*>(blob.data());
+    if (n != d->n_spheres) return rt_fail(RT_EINVAL, "rt_set_motion: n_spheres is not the uploaded scene's");
+    const int ns = d->n_stride;
+    const rt::DevSphere* sph = reinterpret_cast<const rt::DevSphere*>(d + 1);
+    out->assign(sizeof(rt::DevMotion) + (sizeof(rt::DevMotionSphere) + sizeof(rt::DevSphereF)) * (size_t)ns, 0);
+    rt::DevMotion* M = reinterpret_cast<rt::DevMotion*>(out->data());
+    rt::DevMotionSphere* ms = reinterpret_cast<rt::DevMotionSphere*>(M + 1);
+    rt::DevSphereF* sphf = reinterpret_cast<rt::DevSphereF*>(ms + ns);
+    const HP bc = hp(d->bc);
+    put(M->pos, bc);
+    M->n_stride = ns;
+    M->hits_inside = 0;
+    M->hits_lim2 = -1.0;
+    const double K = (double)rt::kFilterK, finf = std::numeric_limits<float>::infinity();
+    double far = 0.0, rmin = std::numeric_limits<double>::infinity();
+    for (int k = 0; k < n; ++k) {
+        const HP c = hp(cl + 3 * k), dk = disp ? hp(disp + 3 * k) : hp(0.0, 0.0, 0.0);
+        put(ms[k].cl, c);
+        put(ms[k].d, dk);
+        const double r = std::sqrt(sph[k].r2) * (1.0 + 0x1p-50);                // >= |radius|
+        const double m = std::max(std::fabs(c.x) + std::fabs(dk.x) + std::fabs(bc.x),
+                                  std::max(std::fabs(c.y) + std::fabs(dk.y) + std::fabs(bc.y),
+                                           std::fabs(c.z) + std::fabs(dk.z) + std::fabs(bc.z)));
+        const double rho = (r + length(dk)) * (1.0 + 0x1p-30) + 0x1p-40 * m;
+        const HP rel = hp(sph[k].c) - bc;
+        const double sC = std::max(std::fabs(rel.x), std::max(std::fabs(rel.y), std::fabs(rel.z)));
+        const double rm = rho * rho + 4 * K * sC * sC + K * rho * rho;
+        sphf[k].cx = (float)rel.x;
+        sphf[k].cy = (float)rel.y;
+        sphf[k].cz = (float)rel.z;
+        float rmf = (float)rm;
+        if ((double)rmf < rm) rmf = std::nextafter(rmf, (float)finf);
+        sphf[k].rm = rmf;
+        far = std::max(far, length(rel) + rho);
+        rmin = std::min(rmin, std::sqrt(sph[k].r2));
+    }
+    for (int k = n; k < ns; ++k) sphf[k].rm = -(float)finf;                     // padding: never a hit (cl = d = 0)
+    if (d->hits_inside && d->bound_on && d->inner2 > 0) {
+        if (d->has_board) {
+            const HP p1 = hp(d->tri[0].v0);
+            const HP corner[4] = {p1, p1 + hp(d->tri[0].u), p1 + hp(d->tri[0].v), p1 + hp(d->tri[1].v)};
+            for (const HP& p : corner) far = std::max(far, length(p - bc));
+        }
+        const rt::DevMesh* mesh = reinterpret_cast<const rt::DevMesh*>(
+            reinterpret_cast<const rt::DevSphereLightF*>(
+                reinterpret_cast<const rt::DevSphereCone*>(
+                    reinterpret_cast<const rt::DevSpherePrimF*>(
+                        reinterpret_cast<const rt::DevSphereF*>(reinterpret_cast<const rt::DevSpherePrim*>(sph + ns) + ns) +
+                        ns) +
+                    ns) +
+                ns) +
+            (size_t)d->n_lights * ns);
+        for (int m = 0; m < d->n_meshes; ++m) far = std::max(far, length(hp(mesh[m].bc) - bc) + std::sqrt(mesh[m].br2));
+        // (rt_build_dev_scene's bound, with the swept `far`)
+        const double Rin = std::sqrt(d->inner2) * (1.0 - 1e-9);
+        const double slack = Rin - far - 1e-6 * (1.0 + far);
+        const double absbc = length(bc);
+        const double e = 0x1p-44, a = rmin > 0 ? e / rmin : std::numeric_limits<double>::infinity();
+        const double c = e * (absbc + far + 1.0) - slack / 2;
+        double dlim = -1.0;
+        if (std::isfinite(far) && std::isfinite(absbc) && slack > 0 && c < 0)
+            dlim = std::isfinite(a) ? (-e + std::sqrt(e * e - 4 * a * c)) / (2 * a) : -c / e;
+        if (dlim >= Rin) {
+            M->hits_inside = 1;
+            M->hits_lim2 = std::min(d->hits_lim2, dlim * dlim * (1.0 - 1e-9));
+        }
+    }
+    return RT_OK;
+}
+
 // R = G = B bit for bit in every frame of the scene: rayTraceRay's colour (:1213-1247) is built from the
 // light colours, the material terms and scalar factors by component-wise products and sums only, and every
 // decision (hits, shadows, which continuations, :1221, :1230-1247) is the same for the three channels (it

@@ -19,6 +19,11 @@ uint64_t rt_blob_fingerprint(const std::vector<unsigned char>& blob);
 // precomputing every derived quantity with the reference's operation order.
 int rt_build_dev_scene(const rt_scene* scene, std::vector<unsigned char>* blob);
 
+// The motion record (rt::DevMotion, rt_layout.hpp) of the flattened scene `blob`: scene-local sphere centres cl[3 n]
+// (what the scene was built from), displacements disp[3 n] (null: no motion); n must be the scene's sphere count.
+int rt_build_motion(const std::vector<unsigned char>& blob, const double* cl, const double* disp, int n,
+                    std::vector<unsigned char>* out);
+
 // rayTraceScreen basis (MySdlApplication.cpp:1270-1277): right = normalize(LD x up),
 // up' = normalize(right x LD), LD = look_at - eye.
 void rt_camera_basis(const rt_camera* cam, double right[3], double upp[3]);

@@ -543,6 +543,12 @@ struct rt_ctx {
                                                // the per-eye data, so every later render re-prepares it
     double eye[3] = {0, 0, 0};
     std::vector<unsigned char> blob;           // host image of d_scene (rt_set_scene skips an unchanged scene)
+    // Motion blur (rt_set_motion, rt_render_motion_dev): the record d_motion (rt_layout.hpp DevMotion) always describes
+    // the uploaded scene — rt_set_scene builds it with no motion — from the scene-local centres the scene was set with.
+    rt::DevMotion* d_motion = nullptr;
+    size_t motion_cap = 0;
+    std::vector<double> local_c;               // rt_sphere::center of the uploaded scene, 3 per sphere
+    std::vector<double> disp;                  // the displacements in force, 3 per sphere (all 0: no motion)
     int min_waves = 5;                         // >= 5: the RT_MINW / RT_MINW_CULL launch bounds for depth <= 3 (measured faster
                                                // than no bound: tools/ab.py); RT_MIN_WAVES=0 disables
     int use_lds = 0;                           // RT_SCENE_IN_LDS=1: header + exact records in LDS (A/B: tools/ab.py)
@@ -772,6 +778,7 @@ extern "C" int rt_ctx_destroy(rt_ctx* c) {
     if (c->rs) (void)hipStreamSynchronize(c->rs);
     if (c->cs) (void)hipStreamSynchronize(c->cs);
     if (c->d_scene) (void)hipFree(c->d_scene);
+    if (c->d_motion) (void)hipFree(c->d_motion);
     if (c->d_tile_rows) (void)hipFree(c->d_tile_rows);
     if (c->d_row_cost) (void)hipFree(c->d_row_cost);
     rt_free_view_bufs(c);
@@ -859,6 +866,34 @@ void rt_ctx_scene_id(const rt_ctx* c, uint64_t* gen, uint64_t* fingerprint) {
     *fingerprint = c && c->scene_set ? c->scene_hash : 0;
 }
 
+// Builds the motion record of the uploaded scene for the displacements `disp` (3 per sphere) and uploads it.  The
+// record changes, so work in flight on the device is waited for first (rt_set_scene's ordering rule).
+static int motion_upload(rt_ctx* c, std::vector<double> disp) {
+    std::vector<unsigned char> rec;
+    const int n = (int)(c->local_c.size() / 3);
+    int rc = rt_build_motion(c->blob, c->local_c.data(), disp.data(), n, &rec);
+    if (rc) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipDeviceSynchronize());
+    if (rec.size() > c->motion_cap) {
+        if (c->d_motion) RT_HIP(hipFree(c->d_motion));
+        c->d_motion = nullptr;
+        c->motion_cap = 0;
+        if (hipMalloc(&c->d_motion, rec.size()) != hipSuccess) return rt_fail(RT_ENOMEM, "rt_set_motion: hipMalloc failed");
+        c->motion_cap = rec.size();
+    }
+    RT_HIP(hipMemcpy(c->d_motion, rec.data(), rec.size(), hipMemcpyHostToDevice));
+    c->disp.swap(disp);
+    return RT_OK;
+}
+
+static std::vector<double> scene_local_centres(const rt_scene* scene) {
+    std::vector<double> v((size_t)3 * (size_t)scene->n_spheres);
+    for (int k = 0; k < scene->n_spheres; ++k)
+        for (int q = 0; q < 3; ++q) v[3 * k + q] = scene->spheres[k].center[q];
+    return v;
+}
+
 extern "C" int rt_set_scene(rt_ctx* c, const rt_scene* scene) {
     if (!c) return rt_fail(RT_EINVAL, "rt_set_scene: null context");
     std::vector<unsigned char> blob;
@@ -866,7 +901,14 @@ extern "C" int rt_set_scene(rt_ctx* c, const rt_scene* scene) {
     if (rc) return rc;
     // An unchanged scene (same flattened record, byte for byte) keeps the device copy, the per-eye data
     // and the tile-row order: rt_render calls this every frame.
-    if (c->scene_set && blob == c->blob) return RT_OK;
+    if (c->scene_set && blob == c->blob) {
+        // (the motion record is built from the scene-local centres: other centres that round to the same world centres
+        // are a changed scene to it, and clear the motion as one)
+        std::vector<double> lc = scene_local_centres(scene);
+        if (memcmp(lc.data(), c->local_c.data(), lc.size() * sizeof(double)) == 0) return RT_OK;
+        c->local_c.swap(lc);
+        return motion_upload(c, std::vector<double>(c->local_c.size(), 0.0));
+    }
     int achromatic = 0;
     rc = rt_scene_achromatic(scene, &achromatic);
     if (rc) return rc;
@@ -901,7 +943,8 @@ extern "C" int rt_set_scene(rt_ctx* c, const rt_scene* scene) {
     c->blob.swap(blob);
     c->scene_hash = rt_blob_fingerprint(c->blob);
     ++c->scene_gen;
-    return RT_OK;
+    c->local_c = scene_local_centres(scene);
+    return motion_upload(c, std::vector<double>(c->local_c.size(), 0.0));   // a changed scene clears the motion
 }
 
 static int render_params(const rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
@@ -1695,6 +1738,80 @@ extern "C" int rt_render_soft(rt_ctx* c, const rt_scene* scene, const rt_camera*
         [&](void* const* d) {
             return rt_render_soft_dev(c, cam, W, H, depth, samples, aperture, light_size, (float*)d[0], (uint8_t*)d[1],
                                       (double*)d[2], (uint32_t*)d[3], c->rs);
+        },
+        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
+}
+
+// ---- motion blur (include/rt_api.h, ABI 10: new symbols only) ------------------------------------------------------
+extern "C" int rt_set_motion(rt_ctx* c, const double* displacement, int n_spheres) {
+    if (!c) return rt_fail(RT_EINVAL, "rt_set_motion: null context");
+    if (!c->scene_set) return rt_fail(RT_EINVAL, "rt_set_motion: no scene set");
+    const int n = (int)(c->local_c.size() / 3);
+    std::vector<double> disp(c->local_c.size(), 0.0);
+    if (displacement || n_spheres != 0) {                   // (NULL, 0) clears the motion
+        if (!displacement) return rt_fail(RT_EINVAL, "rt_set_motion: null displacement");
+        if (n_spheres != n) return rt_fail(RT_EINVAL, "rt_set_motion: n_spheres is not the uploaded scene's");
+        for (size_t k = 0; k < disp.size(); ++k) {
+            if (!std::isfinite(displacement[k])) return rt_fail(RT_EINVAL, "rt_set_motion: displacement must be finite");
+            disp[k] = displacement[k];
+        }
+    }
+    if (c->d_motion && memcmp(disp.data(), c->disp.data(), disp.size() * sizeof(double)) == 0) return RT_OK;
+    return motion_upload(c, std::move(disp));
+}
+
+static int motion_arg_checks(const char* who, double aperture, double light_size, double shutter) {
+    int rc = soft_arg_checks(who, aperture, light_size);
+    if (rc) return rc;
+    if (!(shutter >= 0.0 && shutter <= 1.0)) return rt_fail(RT_EINVAL, std::string(who) + ": shutter must be in [0, 1]");
+    return RT_OK;
+}
+
+// One launch of rt_motion_kernel (rt_sampled.hpp) on `stream`: rt_render_soft_dev's rays and lights, sample (a, b) at
+// its own shutter time.  The displaced centres are formed in the kernel from the context's motion record; the scene
+// record is read, never written, and nothing per view is kept.  No shortcut for shutter 0 or an unset motion.
+extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                    double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                                    double* rgb64f, uint32_t* raycount2, void* stream) {
+    int s, rc = motion_arg_checks("rt_render_motion_dev", aperture, light_size, shutter);
+    if (rc) return rc;
+    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
+    if (!c->d_motion) return rt_fail(RT_EINVAL, "rt_render_motion_dev: no scene set");
+    L.variant = trace_variant(c->tree, c->transparent);
+    L.stream = (hipStream_t)stream;
+    L.scene = c->d_scene;
+    L.motion = c->d_motion;
+    L.aperture = aperture;
+    L.light_size = light_size;
+    L.shutter = shutter;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    const hipError_t e = with_depth(depth, [&](auto B) { return launch_motion<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_motion_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// rt_render for a motion-blurred frame (rt_set_scene, rt_set_motion, rt_render_motion_dev into the context's device
+// buffers, then the copies back).  displacement = nullptr: no motion.
+extern "C" int rt_render_motion(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                                int W, int H, int depth, int samples, double aperture, double light_size,
+                                double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
+    int rc = sampled_host_checks("rt_render_motion", c, W, H, samples);
+    if (rc || (rc = motion_arg_checks("rt_render_motion", aperture, light_size, shutter))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor the motion
+    const size_t npx = (size_t)W * H;
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return rt_render_motion_dev(c, cam, W, H, depth, samples, aperture, light_size, shutter, (float*)d[0],
+                                        (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3], c->rs);
         },
         [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }

@@ -161,6 +161,24 @@ struct alignas(16) DevScene {
     DevBoardEdge edge[4];              // per eye: the board's four edges seen from the camera `eye` (rt_prepare_kernel)
 };
 
+// The motion record of a context (rt_set_motion, rt_render_motion_dev): an allocation of its own beside the scene
+// record, which stays as it is.  DevMotion header, DevMotionSphere[ns], then DevSphereF[ns]: the FP32 filter image of
+// each sphere's SWEPT sphere (every position it takes during the exposure), with the scene record's stride ns.
+struct alignas(16) DevMotionSphere {   // sample centre = (cl + sigma * d) + DevMotion::pos, one IEEE operation each
+    double cl[3];                      // scene-local centre (rt_sphere::center)
+    double pad0;
+    double d[3];                       // half-extent of the motion (0 for the padding spheres)
+    double pad1;
+};
+
+struct alignas(16) DevMotion {
+    double pos[3];                     // rt_scene::position (what rt_set_scene adds to a scene-local centre)
+    double hits_lim2;                  // DevScene::hits_lim2 for the swept extents
+    int32_t hits_inside;               // DevScene::hits_inside for the swept extents
+    int32_t n_stride;                  // ns of the scene record the arrays were built for
+    int32_t pad[2];
+};
+
 inline constexpr int padded_spheres(int n) { return (n + kChunk - 1) / kChunk * kChunk; }
 
 inline constexpr int lds_bytes_for(int n) {

@@ -365,15 +365,15 @@ __device__ __forceinline__ void store_sampled(const RenderParams& P, size_t k, d
 
 // rayTraceRay on Line(p0, p1) through the generic path: no per-tile cone or level masks, V.hits_ok as the caller set
 // it.  lds: the workgroup's trace() slots (slot_bytes(B, TRANSP, WG); unused by ray trees).  AREA, ls: shade()'s (the
-// lane's lights displaced).  (rt_trace_rays_kernel spells the call itself: through this its depth-3 FULL code differed.)
-template <int B, bool TRANSP, bool TREE, int WG, bool AREA = false>
+// lane's lights, MOTION, mo: its sphere centres).  (rt_trace_rays_kernel spells the call itself: its depth-3 FULL code differed.)
+template <int B, bool TRANSP, bool TREE, int WG, bool AREA = false, bool MOTION = false>
 __device__ __forceinline__ d3 trace_generic(const SceneView& V, d3 p0, d3 p1, char* lds, uint32_t* seg, uint32_t* sh,
-                                            LightShift ls = LightShift{0.0, 0.0}) {
-    if constexpr (TREE) return trace_tree<B, AREA>(V, p0, p1, seg, sh, ls);
+                                            LightShift ls = LightShift{0.0, 0.0}, const Motion* mo = nullptr) {
+    if constexpr (TREE) return trace_tree<B, AREA, MOTION>(V, p0, p1, seg, sh, ls, mo);
     else {
         double* slot = reinterpret_cast<double*>(lds) + threadIdx.x;
         int* mslot = reinterpret_cast<int*>(lds + 3 * 8 * colour_slots(B, TRANSP) * WG) + threadIdx.x;
-        return trace<B, false, TRANSP, false, WG, false, AREA>(V, p0, p1, ~0ull, seg, sh, slot, mslot, {-1}, ls);
+        return trace<B, false, TRANSP, false, WG, false, AREA, MOTION>(V, p0, p1, ~0ull, seg, sh, slot, mslot, {-1}, ls, mo);
     }
 }
 

@@ -4,16 +4,16 @@
 //                                      of the pixels on a compacted work list.
 //   rt_dof_kernel<B, TRANSP, TREE>     depth of field (rt_render_dof_dev): thin-lens rays over the whole frame.
 //   rt_soft_kernel<B, TRANSP, TREE>    soft shadows (rt_render_soft_dev): those rays, each lit by its own light points.
+//   rt_motion_kernel<B, TRANSP, TREE>  motion blur (rt_render_motion_dev): those samples, each at its own shutter time.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
 // the reduced pixel.  None has a tile of neighbouring rays from one origin, so there are no cone or level masks:
 // the rays take the generic path (trace_generic, as rt_trace_rays_kernel) with hits_ok_from of their start.  trace()
-// reduces over the whole wave, so every lane stays active: lanes without a sample of their own trace a clamped one
-// and store nothing.
+// reduces over the whole wave: every lane stays active, lanes without a sample trace a clamped one and store nothing.
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
-// rt_adaptive.hip (rt_adaptive_b<B>.o), rt_dof.hip (rt_dof_b<B>.o) and rt_soft.hip (rt_soft_b<B>.o).
+// rt_adaptive.hip (rt_adaptive_b<B>.o), rt_dof.hip (rt_dof_b<B>.o), rt_soft.hip (.._soft_b<B>.o), rt_motion.hip.
 #pragma once
 
 #include "rt_render.hpp"
@@ -130,6 +130,47 @@ __global__ __launch_bounds__(64) void rt_soft_kernel(const DevScene* __restrict_
     }
 }
 
+// Motion blur: rt_soft_kernel's wave layout, rays, lights and store path, and sample (a, b) of a pixel also has the time
+//     sigma = F u_n,   n = a + S b,   u_n = (2 n + 1 - S^2) / S^2
+// (an exact quotient: S^2 is a power of two), F = shutter, at which sphere k is centred at (cl_k + sigma d_k) + pos
+// (rt_device.hpp Motion: the displacement d_k and the swept-sphere filter records come from the context's motion
+// record M, rt_set_motion).  hits_ok is hits_ok_from with the motion record's flag and limit, which the host proves
+// for the swept extents.  F = 0, d = 0, R = 0, A = 0 and S = 1 run this same code.  A sibling kernel, as rt_soft_kernel.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_motion_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                       RenderParams P, double aperture, double light_size,
+                                                       double shutter, int tile_rows, void* o32, void* o8, double* o64,
+                                                       uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const d3 sp = screen_point(P, ic, j, right, upp);
+    const double inv_s = ldexp(1.0, -s);                    // t = (2 a + 1 - S) / S, exact (as rt_dof_kernel)
+    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    const int n = (x & S1) + ((y & S1) << s);               // time index a + S b; u_n exact as t is
+    const double sigma = shutter * ((double)(2 * n + 1 - (1 << 2 * s)) * ldexp(1.0, -2 * s));
+    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+    const Motion mo{sigma, M};
+    uint32_t seg = 0, sh = 0;
+    d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                            LightShift{light_size * ta, light_size * tb}, &mo);
+    reduce_samples(s, 8, col, seg, sh);
+    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -149,23 +190,30 @@ struct SampledLaunch {
     double aperture;                           // half-width of the lens
     // rt_soft_kernel
     double light_size;                         // half-width of the lights' panels
+    // rt_motion_kernel
+    double shutter;                            // share of the displacements the exposure covers
+    const DevMotion* motion;                   // the context's motion record (rt_set_motion)
 };
 
-// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), rt_dof_b<B>.o (rt_dof.hip) and rt_soft_b<B>.o
-// (rt_soft.hip).
+// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), rt_dof_b<B>.o (rt_dof.hip), rt_soft_b<B>.o
+// (rt_soft.hip) and rt_motion_b<B>.o (rt_motion.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
 hipError_t launch_dof(const SampledLaunch& L);
 template <int B>
 hipError_t launch_soft(const SampledLaunch& L);
+template <int B>
+hipError_t launch_motion(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                           \
     template <>                                         \
     hipError_t launch_refine<B>(const SampledLaunch& L); \
     template <>                                         \
     hipError_t launch_dof<B>(const SampledLaunch& L);    \
     template <>                                         \
-    hipError_t launch_soft<B>(const SampledLaunch& L);
+    hipError_t launch_soft<B>(const SampledLaunch& L);   \
+    template <>                                         \
+    hipError_t launch_motion<B>(const SampledLaunch& L);
 RT_DECLARE_SAMPLED(0) RT_DECLARE_SAMPLED(1) RT_DECLARE_SAMPLED(2) RT_DECLARE_SAMPLED(3)
 RT_DECLARE_SAMPLED(4) RT_DECLARE_SAMPLED(5) RT_DECLARE_SAMPLED(6) RT_DECLARE_SAMPLED(7)
 #undef RT_DECLARE_SAMPLED
@@ -192,7 +240,7 @@ hipError_t launch_refine_impl(const SampledLaunch& L) {
     });
 }
 
-// The grid of rt_dof_kernel and rt_soft_kernel: one wave per 8 x 8 tile of the sample grid.
+// The grid of rt_dof_kernel, rt_soft_kernel and rt_motion_kernel: one wave per 8 x 8 tile of the sample grid.
 inline dim3 lens_grid(const RenderParams& P, int* tile_rows) {
     const int tiles_x = (P.width + 7) / 8;
     *tile_rows = (P.height + 7) / 8;
@@ -217,6 +265,17 @@ hipError_t launch_soft_impl(const SampledLaunch& L) {
     return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
         hipLaunchKernelGGL((rt_soft_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
                            L.stream, L.scene, L.P, L.aperture, L.light_size, tile_rows, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_motion_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_motion_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter, tile_rows, L.o32,
+                           L.o8, L.o64, L.orc2);
     });
 }
 

@@ -178,6 +178,40 @@ class Tracer:
         bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
         return self.render_soft_into(cam, width, height, depth, samples, aperture, light_size, bufs, stream)
 
+    # ---------------------------------------------------------------------------------------- motion blur
+    def set_motion(self, displacement=None):
+        """rt_set_motion: `displacement` (n_spheres, 3), the half-extent of each sphere's motion during the exposure
+        in scene-local coordinates; None clears the motion.  A changed set_scene() clears it too."""
+        if displacement is None:
+            abi.check(abi.lib().rt_set_motion(self._ctx, None, 0), "rt_set_motion")
+            return
+        flat = [float(v) for row in displacement for v in row]
+        if len(flat) % 3:
+            raise ValueError("set_motion: three components per sphere")
+        d = (ctypes.c_double * max(len(flat), 1))(*flat)
+        abi.check(abi.lib().rt_set_motion(self._ctx, d, len(flat) // 3), "rt_set_motion")
+
+    def render_motion_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int,
+                           aperture: float, light_size: float, shutter: float, bufs: dict,
+                           stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_motion_dev into alloc_ss() buffers (full frames): the rays and lights of render_soft_into(),
+        sample (a, b) at shutter time shutter * (2 (a + S b) + 1 - S S) / (S S) of the motion set_motion() gave;
+        asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_motion_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
+                                                 float(aperture), float(light_size), float(shutter),
+                                                 _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
+                                                 _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
+                                                 ctypes.c_void_p(st.cuda_stream)), "rt_render_motion_dev")
+        return bufs
+
+    def render_motion(self, cam, width, height, depth, samples, aperture, light_size, shutter, rgba32f=True,
+                      rgba8=False, rgb64f=False, raycount=False, stream=None):
+        """-> the buffers of alloc_ss() (the keys of render_ss())."""
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_motion_into(cam, width, height, depth, samples, aperture, light_size, shutter, bufs,
+                                       stream)
+
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):
         """rt_render_dev_packed: the float image in float_format (RT_PIXEL_RGBA32F / GRAY32F) and the byte
