@@ -1641,108 +1641,7 @@ extern "C" int rt_render_adaptive(rt_ctx* c, const rt_scene* scene, const rt_cam
         });
 }
 
-// ---- depth of field (include/rt_api.h, ABI 10) --------------------------------------------------------------------
-// One launch of rt_dof_kernel (rt_sampled.hpp) on `stream`: S x S lens samples per pixel through the generic trace
-// path.  Nothing per view: no rt_prepare_kernel, no calibration, no dispatch table, and no field of the context is
-// written, so the context's cone and level masks and its tile order stay what the last rt_render_dev left.  No
-// shortcut for aperture 0 or samples 1.
-extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
-                                 double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                                 uint32_t* raycount2, void* stream) {
-    if (!(aperture >= 0.0) || !std::isfinite(aperture))
-        return rt_fail(RT_EINVAL, "rt_render_dof_dev: aperture must be finite and >= 0");
-    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
-    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
-    if (rc) return rc;
-    L.variant = trace_variant(c->tree, c->transparent);
-    L.stream = (hipStream_t)stream;
-    L.scene = c->d_scene;
-    L.aperture = aperture;
-    L.o32 = rgba32f;
-    L.o8 = rgba8;
-    L.o64 = rgb64f;
-    L.orc2 = raycount2;
-    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
-    RT_HIP(hipSetDevice(c->device));
-    const hipError_t e = with_depth(depth, [&](auto B) { return launch_dof<decltype(B)::value>(L); });
-    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_dof_kernel: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
-// rt_render for a depth-of-field frame (rt_render_dof_dev into the context's device buffers, then the copies back).
-extern "C" int rt_render_dof(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
-                             int samples, double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                             rt_stats* stats) {
-    int rc = sampled_host_checks("rt_render_dof", c, W, H, samples);
-    if (rc) return rc;
-    if (!(aperture >= 0.0) || !std::isfinite(aperture))
-        return rt_fail(RT_EINVAL, "rt_render_dof: aperture must be finite and >= 0");
-    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
-    const size_t npx = (size_t)W * H;
-    return host_render(
-        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
-        [&](void* const* d) {
-            return rt_render_dof_dev(c, cam, W, H, depth, samples, aperture, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
-                                     (uint32_t*)d[3], c->rs);
-        },
-        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
-}
-
-// ---- soft shadows (include/rt_api.h, ABI 10: new symbols only) ----------------------------------------------------
-// One launch of rt_soft_kernel (rt_sampled.hpp) on `stream`: the lens kernel's rays, sample (a, b) lit by point (a, b)
-// of every light's square panel.  The displacement is formed in the kernel from light_size: the context's scene record
-// is read, never written or re-uploaded, and nothing per view is kept, as rt_render_dof_dev.  No shortcut for
-// light_size 0, aperture 0 or samples 1.
-static int soft_arg_checks(const char* who, double aperture, double light_size) {
-    if (!(aperture >= 0.0) || !std::isfinite(aperture))
-        return rt_fail(RT_EINVAL, std::string(who) + ": aperture must be finite and >= 0");
-    if (!(light_size >= 0.0) || !std::isfinite(light_size))
-        return rt_fail(RT_EINVAL, std::string(who) + ": light_size must be finite and >= 0");
-    return RT_OK;
-}
-
-extern "C" int rt_render_soft_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
-                                  double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                                  uint32_t* raycount2, void* stream) {
-    int s, rc = soft_arg_checks("rt_render_soft_dev", aperture, light_size);
-    if (rc) return rc;
-    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
-    rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
-    if (rc) return rc;
-    L.variant = trace_variant(c->tree, c->transparent);
-    L.stream = (hipStream_t)stream;
-    L.scene = c->d_scene;
-    L.aperture = aperture;
-    L.light_size = light_size;
-    L.o32 = rgba32f;
-    L.o8 = rgba8;
-    L.o64 = rgb64f;
-    L.orc2 = raycount2;
-    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
-    RT_HIP(hipSetDevice(c->device));
-    const hipError_t e = with_depth(depth, [&](auto B) { return launch_soft<decltype(B)::value>(L); });
-    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_soft_kernel: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
-// rt_render for a soft-shadow frame (rt_render_soft_dev into the context's device buffers, then the copies back).
-extern "C" int rt_render_soft(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
-                              int samples, double aperture, double light_size, float* rgba32f, uint8_t* rgba8,
-                              double* rgb64f, rt_stats* stats) {
-    int rc = sampled_host_checks("rt_render_soft", c, W, H, samples);
-    if (rc || (rc = soft_arg_checks("rt_render_soft", aperture, light_size))) return rc;
-    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
-    const size_t npx = (size_t)W * H;
-    return host_render(
-        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
-        [&](void* const* d) {
-            return rt_render_soft_dev(c, cam, W, H, depth, samples, aperture, light_size, (float*)d[0], (uint8_t*)d[1],
-                                      (double*)d[2], (uint32_t*)d[3], c->rs);
-        },
-        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
-}
-
-// ---- motion blur (include/rt_api.h, ABI 10: new symbols only) ------------------------------------------------------
+// ---- motion of the spheres (include/rt_api.h, ABI 10: new symbols only) ------------------------------------------
 extern "C" int rt_set_motion(rt_ctx* c, const double* displacement, int n_spheres) {
     if (!c) return rt_fail(RT_EINVAL, "rt_set_motion: null context");
     if (!c->scene_set) return rt_fail(RT_EINVAL, "rt_set_motion: no scene set");
@@ -1760,60 +1659,125 @@ extern "C" int rt_set_motion(rt_ctx* c, const double* displacement, int n_sphere
     return motion_upload(c, std::move(disp));
 }
 
-static int motion_arg_checks(const char* who, double aperture, double light_size, double shutter) {
-    int rc = soft_arg_checks(who, aperture, light_size);
-    if (rc) return rc;
-    if (!(shutter >= 0.0 && shutter <= 1.0)) return rt_fail(RT_EINVAL, std::string(who) + ": shutter must be in [0, 1]");
+// ---- the lens family: depth of field, soft shadows, motion blur (include/rt_api.h, ABI 10) -------------------------
+// rt_render_motion_dev with shutter 0 is rt_render_soft_dev, and that with light_size 0 is rt_render_dof_dev: one
+// kernel (rt_lens_kernel<.., AREA, MOTION>, rt_sampled.hpp) in three kinds behind the three pairs of entry points.
+enum LensKind { kLensDof = 0, kLensSoft = 1, kLensMotion = 2 };
+
+// The arguments a kind reads, in the order aperture, light_size, shutter.
+static int lens_arg_checks(LensKind kind, const char* who, double aperture, double light_size, double shutter) {
+    if (!(aperture >= 0.0) || !std::isfinite(aperture))
+        return rt_fail(RT_EINVAL, std::string(who) + ": aperture must be finite and >= 0");
+    if (kind >= kLensSoft && (!(light_size >= 0.0) || !std::isfinite(light_size)))
+        return rt_fail(RT_EINVAL, std::string(who) + ": light_size must be finite and >= 0");
+    if (kind >= kLensMotion && !(shutter >= 0.0 && shutter <= 1.0))
+        return rt_fail(RT_EINVAL, std::string(who) + ": shutter must be in [0, 1]");
     return RT_OK;
 }
 
-// One launch of rt_motion_kernel (rt_sampled.hpp) on `stream`: rt_render_soft_dev's rays and lights, sample (a, b) at
-// its own shutter time.  The displaced centres are formed in the kernel from the context's motion record; the scene
-// record is read, never written, and nothing per view is kept.  No shortcut for shutter 0 or an unset motion.
-extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
-                                    double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
-                                    double* rgb64f, uint32_t* raycount2, void* stream) {
-    int s, rc = motion_arg_checks("rt_render_motion_dev", aperture, light_size, shutter);
+// One launch of the kind's rt_lens_kernel on `stream`: S x S lens samples per pixel through the generic trace path;
+// soft: sample (a, b) lit by point (a, b) of every light's square panel; motion: sample (a, b) also at its own shutter
+// time.  The light shift and the displaced centres are formed in the kernel, from light_size and from the context's
+// motion record: the scene record is read, never written or re-uploaded.  Nothing per view: no rt_prepare_kernel, no
+// calibration, no dispatch table, and no field of the context is written, so the context's cone and level masks and
+// its tile order stay what the last rt_render_dev left.  No shortcut for shutter 0, an unset motion, light_size 0,
+// aperture 0 or samples 1.  `who` is the entry point, the prefix of its messages.
+static int lens_render_dev(LensKind kind, const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth,
+                           int samples, double aperture, double light_size, double shutter, float* rgba32f,
+                           uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream) {
+    int s, rc = lens_arg_checks(kind, who, aperture, light_size, shutter);
     if (rc) return rc;
     SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
     rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
     if (rc) return rc;
-    if (!c->d_motion) return rt_fail(RT_EINVAL, "rt_render_motion_dev: no scene set");
+    if (kind == kLensMotion && !c->d_motion) return rt_fail(RT_EINVAL, std::string(who) + ": no scene set");
     L.variant = trace_variant(c->tree, c->transparent);
     L.stream = (hipStream_t)stream;
     L.scene = c->d_scene;
-    L.motion = c->d_motion;
     L.aperture = aperture;
-    L.light_size = light_size;
+    L.light_size = light_size;                              // 0 from the kinds without it
     L.shutter = shutter;
+    if (kind == kLensMotion) L.motion = c->d_motion;
     L.o32 = rgba32f;
     L.o8 = rgba8;
     L.o64 = rgb64f;
     L.orc2 = raycount2;
     if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
-    const hipError_t e = with_depth(depth, [&](auto B) { return launch_motion<decltype(B)::value>(L); });
-    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_motion_kernel: ") + hipGetErrorString(e));
+    const hipError_t e = with_depth(depth, [&](auto B) {
+        constexpr int b = decltype(B)::value;
+        return kind == kLensMotion ? launch_lens<b, true, true>(L)
+               : kind == kLensSoft ? launch_lens<b, true, false>(L)
+                                   : launch_lens<b, false, false>(L);
+    });
+    // the names the kinds' kernels had as kernels of their own: the messages keep them
+    static const char* const kKernel[] = {"rt_dof_kernel: ", "rt_soft_kernel: ", "rt_motion_kernel: "};
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string(kKernel[kind]) + hipGetErrorString(e));
     return RT_OK;
 }
 
-// rt_render for a motion-blurred frame (rt_set_scene, rt_set_motion, rt_render_motion_dev into the context's device
-// buffers, then the copies back).  displacement = nullptr: no motion.
-extern "C" int rt_render_motion(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
-                                int W, int H, int depth, int samples, double aperture, double light_size,
-                                double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
-    int rc = sampled_host_checks("rt_render_motion", c, W, H, samples);
-    if (rc || (rc = motion_arg_checks("rt_render_motion", aperture, light_size, shutter))) return rc;
+// rt_render for a frame of the kind: lens_render_dev (as `who`_dev) into the context's device buffers, then the copies
+// back.  Motion: rt_set_motion after rt_set_scene; displacement = nullptr: no motion.
+static int lens_render_host(LensKind kind, const char* who, rt_ctx* c, const rt_scene* scene,
+                            const double* displacement, const rt_camera* cam, int W, int H, int depth, int samples,
+                            double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                            double* rgb64f, rt_stats* stats) {
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc || (rc = lens_arg_checks(kind, who, aperture, light_size, shutter))) return rc;
     if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
-    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor the motion
+    if (kind == kLensMotion && (rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0)))
+        return rc;                                          // nor when the motion is
     const size_t npx = (size_t)W * H;
+    const std::string dev = std::string(who) + "_dev";
     return host_render(
         c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
         [&](void* const* d) {
-            return rt_render_motion_dev(c, cam, W, H, depth, samples, aperture, light_size, shutter, (float*)d[0],
-                                        (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3], c->rs);
+            return lens_render_dev(kind, dev.c_str(), c, cam, W, H, depth, samples, aperture, light_size, shutter,
+                                   (float*)d[0], (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3], c->rs);
         },
         [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
+}
+
+extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                 double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                 uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensDof, "rt_render_dof_dev", c, cam, W, H, depth, samples, aperture, 0.0, 0.0, rgba32f,
+                           rgba8, rgb64f, raycount2, stream);
+}
+
+extern "C" int rt_render_dof(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                             int samples, double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                             rt_stats* stats) {
+    return lens_render_host(kLensDof, "rt_render_dof", c, scene, nullptr, cam, W, H, depth, samples, aperture, 0.0, 0.0,
+                            rgba32f, rgba8, rgb64f, stats);
+}
+
+extern "C" int rt_render_soft_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                  double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                  uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensSoft, "rt_render_soft_dev", c, cam, W, H, depth, samples, aperture, light_size, 0.0,
+                           rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+extern "C" int rt_render_soft(rt_ctx* c, const rt_scene* scene, const rt_camera* cam, int W, int H, int depth,
+                              int samples, double aperture, double light_size, float* rgba32f, uint8_t* rgba8,
+                              double* rgb64f, rt_stats* stats) {
+    return lens_render_host(kLensSoft, "rt_render_soft", c, scene, nullptr, cam, W, H, depth, samples, aperture,
+                            light_size, 0.0, rgba32f, rgba8, rgb64f, stats);
+}
+
+extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                    double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                                    double* rgb64f, uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensMotion, "rt_render_motion_dev", c, cam, W, H, depth, samples, aperture, light_size,
+                           shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+extern "C" int rt_render_motion(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                                int W, int H, int depth, int samples, double aperture, double light_size,
+                                double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
+    return lens_render_host(kLensMotion, "rt_render_motion", c, scene, displacement, cam, W, H, depth, samples,
+                            aperture, light_size, shutter, rgba32f, rgba8, rgb64f, stats);
 }
 
 // ---- copy_mode 3: device-to-host frames on an SDMA engine (HSA runtime, hsa_amd_memory_async_copy_on_engine) ----

@@ -322,7 +322,7 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 
 }
 
 // ---- The sample-grid contract of include/rt_api.h (rt_render_ss_dev), spelled once for render_body's supersampled
-// instances and the two list-free sampled kernels of rt_sampled.hpp (rt_refine_kernel, rt_dof_kernel). ----
+// instances and the two list-free sampled kernels of rt_sampled.hpp (rt_refine_kernel, rt_lens_kernel). ----
 
 // Screen point of pixel (ic, j) of the frame P describes (for a sampled render: the sample grid),
 //     sp = (look + (pitch (ic + bottom_x)) right) + (pitch (j + bottom_y)) up',

@@ -2,9 +2,10 @@
 //
 //   rt_refine_kernel<B, TRANSP, TREE>  adaptive supersampling (rt_render_adaptive_dev, include/rt_api.h): the samples
 //                                      of the pixels on a compacted work list.
-//   rt_dof_kernel<B, TRANSP, TREE>     depth of field (rt_render_dof_dev): thin-lens rays over the whole frame.
-//   rt_soft_kernel<B, TRANSP, TREE>    soft shadows (rt_render_soft_dev): those rays, each lit by its own light points.
-//   rt_motion_kernel<B, TRANSP, TREE>  motion blur (rt_render_motion_dev): those samples, each at its own shutter time.
+//   rt_lens_kernel<B, TRANSP, TREE, AREA, MOTION>  thin-lens rays over the whole frame, in three kinds:
+//                                      depth of field (rt_render_dof_dev), AREA: soft shadows (rt_render_soft_dev), each
+//                                      ray lit by its own light points, and AREA, MOTION: motion blur
+//                                      (rt_render_motion_dev), each sample at its own shutter time.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -13,7 +14,7 @@
 // reduces over the whole wave: every lane stays active, lanes without a sample trace a clamped one and store nothing.
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
-// rt_adaptive.hip (rt_adaptive_b<B>.o), rt_dof.hip (rt_dof_b<B>.o), rt_soft.hip (.._soft_b<B>.o), rt_motion.hip.
+// rt_adaptive.hip (rt_adaptive_b<B>.o) and, once per depth and kind, rt_lens.hip (rt_lens_k<kind>_b<B>.o).
 #pragma once
 
 #include "rt_render.hpp"
@@ -63,9 +64,30 @@ constexpr int kDofGridY = 32768;               // tile rows per grid.z slice (gr
 // one IEEE operation per parenthesis and component, in this order; hits_ok_from(e) per lane.  A = 0 and S = 1 run this
 // same code.  The sample frame is S times the output, and S divides 8, so an S x S block lies wholly inside the sample
 // frame or wholly outside it; lanes outside (and the padding tile rows of the last grid.z slice) store nothing.
-template <int B, bool TRANSP, bool TREE>
-__global__ __launch_bounds__(64) void rt_dof_kernel(const DevScene* __restrict__ S, RenderParams P, double aperture,
-                                                    int tile_rows, void* o32, void* o8, double* o64, uint32_t* orc2) {
+//
+// AREA (soft shadows): sample (a, b) also sees every light of the scene displaced to
+//     (L.x + (R t_a), L.y, L.z + (R t_b)),
+// point (a, b) of a square panel of half-width R = light_size in the world xz-plane, paired with the lens point and the
+// sub-pixel point of the same (a, b).  The shift reaches shade() through trace_generic<.., AREA = true> (rt_device.hpp:
+// no light-cone records and no masks for the displaced shadow rays).  R = 0, A = 0 and S = 1 run this same code.
+//
+// MOTION (motion blur, on AREA): sample (a, b) of a pixel also has the time
+//     sigma = F u_n,   n = a + S b,   u_n = (2 n + 1 - S^2) / S^2
+// (an exact quotient: S^2 is a power of two), F = shutter, at which sphere k is centred at (cl_k + sigma d_k) + pos
+// (rt_device.hpp Motion: the displacement d_k and the swept-sphere filter records come from the context's motion
+// record M, rt_set_motion).  hits_ok is hits_ok_from with the motion record's flag and limit, which the host proves
+// for the swept extents.  F = 0, d = 0, R = 0, A = 0 and S = 1 run this same code.
+//
+// One __global__ template for the three kinds, with one parameter list (light_size, shutter and M are passed to all
+// and read under their flag only: M may be nullptr without MOTION).  The parts of a kind sit under if constexpr, so an
+// instance compiles to the code its own kernel had (profiles/lens/isa_compare.md); a shared __device__ body called
+// from three kernels did not: the lens kernel's instances came out with another register allocation.
+template <int B, bool TRANSP, bool TREE, bool AREA, bool MOTION>
+__global__ __launch_bounds__(64) void rt_lens_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                     RenderParams P, double aperture, double light_size,
+                                                     double shutter, int tile_rows, void* o32, void* o8, double* o64,
+                                                     uint32_t* orc2) {
+    static_assert(AREA || !MOTION, "the motion instances are area-light instances");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x;
     const int s = P.ss_log2, S1 = (1 << s) - 1;
@@ -82,88 +104,24 @@ __global__ __launch_bounds__(64) void rt_dof_kernel(const DevScene* __restrict__
     const double inv_s = ldexp(1.0, -s);
     const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
     const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
-    V.hits_ok = hits_ok_from(S, e);
     uint32_t seg = 0, sh = 0;
-    d3 col = trace_generic<B, TRANSP, TREE, 64>(V, e, sp, smem, &seg, &sh);
-    reduce_samples(s, 8, col, seg, sh);
-    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
-        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
-        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    d3 col;
+    if constexpr (MOTION) {
+        const int n = (x & S1) + ((y & S1) << s);           // time index a + S b; u_n exact as t is
+        const double sigma = shutter * ((double)(2 * n + 1 - (1 << 2 * s)) * ldexp(1.0, -2 * s));
+        const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+        V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+        const Motion mo{sigma, M};
+        col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                             LightShift{light_size * ta, light_size * tb}, &mo);
+    } else if constexpr (AREA) {
+        V.hits_ok = hits_ok_from(S, e);
+        col = trace_generic<B, TRANSP, TREE, 64, true>(V, e, sp, smem, &seg, &sh,
+                                                       LightShift{light_size * ta, light_size * tb});
+    } else {
+        V.hits_ok = hits_ok_from(S, e);
+        col = trace_generic<B, TRANSP, TREE, 64>(V, e, sp, smem, &seg, &sh);
     }
-}
-
-// Soft shadows: rt_dof_kernel's wave layout, rays and store path, and sample (a, b) also sees every light of the scene
-// displaced to
-//     (L.x + (R t_a), L.y, L.z + (R t_b)),
-// point (a, b) of a square panel of half-width R = light_size in the world xz-plane, paired with the lens point and the
-// sub-pixel point of the same (a, b).  The shift reaches shade() through trace_generic<.., AREA = true> (rt_device.hpp:
-// no light-cone records and no masks for the displaced shadow rays).  R = 0, A = 0 and S = 1 run this same code.
-// A sibling of rt_dof_kernel, not an instance of a shared body: called through one, the lens kernel's instances came
-// out with another register allocation, and they are required to compile to the code they had.
-template <int B, bool TRANSP, bool TREE>
-__global__ __launch_bounds__(64) void rt_soft_kernel(const DevScene* __restrict__ S, RenderParams P, double aperture,
-                                                     double light_size, int tile_rows, void* o32, void* o8,
-                                                     double* o64, uint32_t* orc2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x;
-    const int s = P.ss_log2, S1 = (1 << s) - 1;
-    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
-    const int x = lane & 7, y = lane >> 3;
-    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
-    const bool pad = ty_raw >= tile_rows;
-    const int ty = pad ? tile_rows - 1 : ty_raw;
-    const int i = tx * 8 + x, lr = ty * 8 + y;
-    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
-    const d3 right = ld3(P.right), upp = ld3(P.upp);
-    const d3 sp = screen_point(P, ic, j, right, upp);
-    const double inv_s = ldexp(1.0, -s);                    // t = (2 a + 1 - S) / S, exact (as rt_dof_kernel)
-    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
-    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
-    V.hits_ok = hits_ok_from(S, e);
-    uint32_t seg = 0, sh = 0;
-    d3 col = trace_generic<B, TRANSP, TREE, 64, true>(V, e, sp, smem, &seg, &sh,
-                                                      LightShift{light_size * ta, light_size * tb});
-    reduce_samples(s, 8, col, seg, sh);
-    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
-        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
-        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
-    }
-}
-
-// Motion blur: rt_soft_kernel's wave layout, rays, lights and store path, and sample (a, b) of a pixel also has the time
-//     sigma = F u_n,   n = a + S b,   u_n = (2 n + 1 - S^2) / S^2
-// (an exact quotient: S^2 is a power of two), F = shutter, at which sphere k is centred at (cl_k + sigma d_k) + pos
-// (rt_device.hpp Motion: the displacement d_k and the swept-sphere filter records come from the context's motion
-// record M, rt_set_motion).  hits_ok is hits_ok_from with the motion record's flag and limit, which the host proves
-// for the swept extents.  F = 0, d = 0, R = 0, A = 0 and S = 1 run this same code.  A sibling kernel, as rt_soft_kernel.
-template <int B, bool TRANSP, bool TREE>
-__global__ __launch_bounds__(64) void rt_motion_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
-                                                       RenderParams P, double aperture, double light_size,
-                                                       double shutter, int tile_rows, void* o32, void* o8, double* o64,
-                                                       uint32_t* orc2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x;
-    const int s = P.ss_log2, S1 = (1 << s) - 1;
-    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
-    const int x = lane & 7, y = lane >> 3;
-    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
-    const bool pad = ty_raw >= tile_rows;
-    const int ty = pad ? tile_rows - 1 : ty_raw;
-    const int i = tx * 8 + x, lr = ty * 8 + y;
-    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
-    const d3 right = ld3(P.right), upp = ld3(P.upp);
-    const d3 sp = screen_point(P, ic, j, right, upp);
-    const double inv_s = ldexp(1.0, -s);                    // t = (2 a + 1 - S) / S, exact (as rt_dof_kernel)
-    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
-    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
-    const int n = (x & S1) + ((y & S1) << s);               // time index a + S b; u_n exact as t is
-    const double sigma = shutter * ((double)(2 * n + 1 - (1 << 2 * s)) * ldexp(1.0, -2 * s));
-    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
-    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
-    const Motion mo{sigma, M};
-    uint32_t seg = 0, sh = 0;
-    d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
-                                                            LightShift{light_size * ta, light_size * tb}, &mo);
     reduce_samples(s, 8, col, seg, sh);
     if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
         const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
@@ -186,34 +144,28 @@ struct SampledLaunch {
     int out_w;
     const uint32_t* count;
     const uint32_t* list;
-    // rt_dof_kernel, rt_soft_kernel
+    // rt_lens_kernel (a kind leaves what it does not read at zero)
     double aperture;                           // half-width of the lens
-    // rt_soft_kernel
-    double light_size;                         // half-width of the lights' panels
-    // rt_motion_kernel
-    double shutter;                            // share of the displacements the exposure covers
-    const DevMotion* motion;                   // the context's motion record (rt_set_motion)
+    double light_size;                         // AREA: half-width of the lights' panels
+    double shutter;                            // MOTION: share of the displacements the exposure covers
+    const DevMotion* motion;                   // MOTION: the context's motion record (rt_set_motion)
 };
 
-// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), rt_dof_b<B>.o (rt_dof.hip), rt_soft_b<B>.o
-// (rt_soft.hip) and rt_motion_b<B>.o (rt_motion.hip).
+// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip) and, per kind, in rt_lens_k<kind>_b<B>.o
+// (rt_lens.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
-template <int B>
-hipError_t launch_dof(const SampledLaunch& L);
-template <int B>
-hipError_t launch_soft(const SampledLaunch& L);
-template <int B>
-hipError_t launch_motion(const SampledLaunch& L);
-#define RT_DECLARE_SAMPLED(B)                           \
-    template <>                                         \
-    hipError_t launch_refine<B>(const SampledLaunch& L); \
-    template <>                                         \
-    hipError_t launch_dof<B>(const SampledLaunch& L);    \
-    template <>                                         \
-    hipError_t launch_soft<B>(const SampledLaunch& L);   \
-    template <>                                         \
-    hipError_t launch_motion<B>(const SampledLaunch& L);
+template <int B, bool AREA, bool MOTION>
+hipError_t launch_lens(const SampledLaunch& L);
+#define RT_DECLARE_SAMPLED(B)                                         \
+    template <>                                                       \
+    hipError_t launch_refine<B>(const SampledLaunch& L);              \
+    template <>                                                       \
+    hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
+    template <>                                                       \
+    hipError_t launch_lens<B, true, false>(const SampledLaunch& L);   \
+    template <>                                                       \
+    hipError_t launch_lens<B, true, true>(const SampledLaunch& L);
 RT_DECLARE_SAMPLED(0) RT_DECLARE_SAMPLED(1) RT_DECLARE_SAMPLED(2) RT_DECLARE_SAMPLED(3)
 RT_DECLARE_SAMPLED(4) RT_DECLARE_SAMPLED(5) RT_DECLARE_SAMPLED(6) RT_DECLARE_SAMPLED(7)
 #undef RT_DECLARE_SAMPLED
@@ -240,7 +192,7 @@ hipError_t launch_refine_impl(const SampledLaunch& L) {
     });
 }
 
-// The grid of rt_dof_kernel, rt_soft_kernel and rt_motion_kernel: one wave per 8 x 8 tile of the sample grid.
+// The grid of rt_lens_kernel: one wave per 8 x 8 tile of the sample grid.
 inline dim3 lens_grid(const RenderParams& P, int* tile_rows) {
     const int tiles_x = (P.width + 7) / 8;
     *tile_rows = (P.height + 7) / 8;
@@ -248,34 +200,14 @@ inline dim3 lens_grid(const RenderParams& P, int* tile_rows) {
                 (unsigned)((*tile_rows + kDofGridY - 1) / kDofGridY));
 }
 
-template <int B>
-hipError_t launch_dof_impl(const SampledLaunch& L) {
+template <int B, bool AREA, bool MOTION>
+hipError_t launch_lens_impl(const SampledLaunch& L) {
     int tile_rows;
     const dim3 g = lens_grid(L.P, &tile_rows);
     return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
-        hipLaunchKernelGGL((rt_dof_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
-                           L.stream, L.scene, L.P, L.aperture, tile_rows, L.o32, L.o8, L.o64, L.orc2);
-    });
-}
-
-template <int B>
-hipError_t launch_soft_impl(const SampledLaunch& L) {
-    int tile_rows;
-    const dim3 g = lens_grid(L.P, &tile_rows);
-    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
-        hipLaunchKernelGGL((rt_soft_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
-                           L.stream, L.scene, L.P, L.aperture, L.light_size, tile_rows, L.o32, L.o8, L.o64, L.orc2);
-    });
-}
-
-template <int B>
-hipError_t launch_motion_impl(const SampledLaunch& L) {
-    int tile_rows;
-    const dim3 g = lens_grid(L.P, &tile_rows);
-    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
-        hipLaunchKernelGGL((rt_motion_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
-                           L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter, tile_rows, L.o32,
-                           L.o8, L.o64, L.orc2);
+        hipLaunchKernelGGL((rt_lens_kernel<B, decltype(transp)::value, decltype(tree)::value, AREA, MOTION>), g,
+                           dim3(64), lds, L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter,
+                           tile_rows, L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

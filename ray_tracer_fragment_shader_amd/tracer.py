@@ -138,47 +138,50 @@ class Tracer:
         bufs = self.alloc_adaptive(width, height, samples, rgba32f, rgba8, rgb64f, raycount)
         return self.render_adaptive_into(cam, width, height, depth, samples, threshold, bufs, stream)
 
-    # ------------------------------------------------------------------------------------- depth of field
+    # ------------------------------------------------- the lens family: depth of field, soft shadows, motion blur
+    def _render_lens_into(self, symbol: str, extra_floats, cam: abi.rt_camera, width: int, height: int, depth: int,
+                          samples: int, bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """`symbol` (rt_render_dof_dev, rt_render_soft_dev or rt_render_motion_dev) into alloc_ss() buffers (full
+        frames), `extra_floats` its doubles after `samples`; asynchronous on `stream` (default: torch's current
+        stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(getattr(abi.lib(), symbol)(self._ctx, ctypes.byref(cam), width, height, depth, samples,
+                                             *(float(v) for v in extra_floats), _ptr(bufs.get("rgba32f")),
+                                             _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")),
+                                             _ptr(bufs.get("raycount")), ctypes.c_void_p(st.cuda_stream)), symbol)
+        return bufs
+
     def render_dof_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int,
                         aperture: float, bufs: dict, stream: Optional[torch.cuda.Stream] = None):
         """rt_render_dof_dev into alloc_ss() buffers (full frames): samples x samples rays per pixel from a square
         lens of half-width `aperture` around the eye, focused on the plane through cam.look_at
         (scenes.focus_camera moves it); asynchronous on `stream` (default: torch's current stream)."""
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        abi.check(abi.lib().rt_render_dof_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
-                                              float(aperture), _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
-                                              _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
-                                              ctypes.c_void_p(st.cuda_stream)), "rt_render_dof_dev")
-        return bufs
+        return self._render_lens_into("rt_render_dof_dev", (aperture,), cam, width, height, depth, samples, bufs,
+                                      stream)
 
     def render_dof(self, cam, width, height, depth, samples, aperture, rgba32f=True, rgba8=False, rgb64f=False,
                    raycount=False, stream=None):
         """-> the buffers of alloc_ss() (the keys of render_ss())."""
         bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
-        return self.render_dof_into(cam, width, height, depth, samples, aperture, bufs, stream)
+        return self._render_lens_into("rt_render_dof_dev", (aperture,), cam, width, height, depth, samples, bufs,
+                                      stream)
 
-    # --------------------------------------------------------------------------------------- soft shadows
     def render_soft_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int,
                          aperture: float, light_size: float, bufs: dict,
                          stream: Optional[torch.cuda.Stream] = None):
         """rt_render_soft_dev into alloc_ss() buffers (full frames): the rays of render_dof_into(), sample (a, b)
         lit by point (a, b) of every light's square panel of half-width `light_size` in the world xz-plane;
         asynchronous on `stream` (default: torch's current stream)."""
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        abi.check(abi.lib().rt_render_soft_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
-                                               float(aperture), float(light_size), _ptr(bufs.get("rgba32f")),
-                                               _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")),
-                                               _ptr(bufs.get("raycount")), ctypes.c_void_p(st.cuda_stream)),
-                  "rt_render_soft_dev")
-        return bufs
+        return self._render_lens_into("rt_render_soft_dev", (aperture, light_size), cam, width, height, depth, samples,
+                                      bufs, stream)
 
     def render_soft(self, cam, width, height, depth, samples, aperture, light_size, rgba32f=True, rgba8=False,
                     rgb64f=False, raycount=False, stream=None):
         """-> the buffers of alloc_ss() (the keys of render_ss())."""
         bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
-        return self.render_soft_into(cam, width, height, depth, samples, aperture, light_size, bufs, stream)
+        return self._render_lens_into("rt_render_soft_dev", (aperture, light_size), cam, width, height, depth, samples,
+                                      bufs, stream)
 
-    # ---------------------------------------------------------------------------------------- motion blur
     def set_motion(self, displacement=None):
         """rt_set_motion: `displacement` (n_spheres, 3), the half-extent of each sphere's motion during the exposure
         in scene-local coordinates; None clears the motion.  A changed set_scene() clears it too."""
@@ -197,20 +200,15 @@ class Tracer:
         """rt_render_motion_dev into alloc_ss() buffers (full frames): the rays and lights of render_soft_into(),
         sample (a, b) at shutter time shutter * (2 (a + S b) + 1 - S S) / (S S) of the motion set_motion() gave;
         asynchronous on `stream` (default: torch's current stream)."""
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        abi.check(abi.lib().rt_render_motion_dev(self._ctx, ctypes.byref(cam), width, height, depth, samples,
-                                                 float(aperture), float(light_size), float(shutter),
-                                                 _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
-                                                 _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
-                                                 ctypes.c_void_p(st.cuda_stream)), "rt_render_motion_dev")
-        return bufs
+        return self._render_lens_into("rt_render_motion_dev", (aperture, light_size, shutter), cam, width, height,
+                                      depth, samples, bufs, stream)
 
     def render_motion(self, cam, width, height, depth, samples, aperture, light_size, shutter, rgba32f=True,
                       rgba8=False, rgb64f=False, raycount=False, stream=None):
         """-> the buffers of alloc_ss() (the keys of render_ss())."""
         bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
-        return self.render_motion_into(cam, width, height, depth, samples, aperture, light_size, shutter, bufs,
-                                       stream)
+        return self._render_lens_into("rt_render_motion_dev", (aperture, light_size, shutter), cam, width, height,
+                                      depth, samples, bufs, stream)
 
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):

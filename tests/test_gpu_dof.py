@@ -17,55 +17,20 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from oracle import pyoracle as po  # noqa: E402
 from ray_tracer_fragment_shader_amd import abi, scenes  # noqa: E402
-from ray_tracer_fragment_shader_amd.tracer import Tracer  # noqa: E402
 
 from . import dof_common as dc  # noqa: E402
+from . import lens_gpu_common as lg  # noqa: E402
 from . import ssaa_common as sc  # noqa: E402
+from .lens_gpu_common import H, W, _check_all, _host, _read_ppm, fresh, tr  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
-W, H, A = 37, 21, 8.0
-
-
-@pytest.fixture(scope="module")
-def tr():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a HIP device")
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-@pytest.fixture()
-def fresh():
-    """A context of its own: the tests of the per-view state."""
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a HIP device")
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def _host(bufs):
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in bufs.items() if v is not None}
-    if "raycount" in out:
-        out["raycount"] = out["raycount"].view(np.uint32)
-    return out
+A = 8.0
 
 
 def _render(t, cam, w, h, depth, S, aperture):
     return _host(t.render_dof(cam, w, h, depth, S, aperture, rgba32f=True, rgba8=True, rgb64f=True, raycount=True))
-
-
-def _check_all(got, rgb, rc2, what):
-    """Every output of a depth-of-field render against the expected float64 frame and counters."""
-    sc.assert_same_bits(got["rgb64f"], rgb, what + " rgb64f")
-    sc.assert_same_bits(got["rgba32f"], sc.to_rgba32f(rgb), what + " rgba32f")
-    assert np.array_equal(got["rgba8"], sc.to_rgba8(rgb)), what + " rgba8"
-    assert got["raycount"].shape == rc2.shape and np.array_equal(got["raycount"], rc2), what + " raycount"
 
 
 # 1. every instance -------------------------------------------------------------------------------------------
@@ -107,16 +72,7 @@ def test_aperture_zero_is_the_ssaa_fixture(tr, name, S):
 # 3. S = 1 ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["c2", "demo"])
 def test_one_sample_is_the_plain_render(tr, name):
-    scene, depth = sc.scene_of(name)
-    tr.set_scene(scene)
-    cam = scenes.make_camera(W, H, 500.0 / W)
-    want, want_rc = po.render(scene.to_abi(), cam, W, H, depth)
-    plain = _host(tr.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True))
-    assert plain["rgb64f"].tobytes() == want.tobytes()
-    got = _render(tr, cam, W, H, depth, 1, A)
-    for k in ("rgba32f", "rgba8", "rgb64f"):
-        assert got[k].tobytes() == plain[k].tobytes(), k
-    assert np.array_equal(got["raycount"], sc.reduce_counts(want_rc, 1))
+    lg.check_one_sample_is_the_plain_render(tr, name, lambda cam, depth: _render(tr, cam, W, H, depth, 1, A))
 
 
 # 4. NaN frames -----------------------------------------------------------------------------------------------
@@ -128,10 +84,7 @@ def test_nan_frames(tr, S):
     scene, depth = sc.scene_of("tree_c2")
     assert depth == 3
     tr.set_scene(scene)
-    got = _render(tr, e["cam"], W, H, depth, S, A)
-    assert np.array_equal(np.isnan(got["rgb64f"]), np.isnan(e["rgb"]))
-    _check_all(got, e["rgb"], e["rc2"], f"tree_c2 S={S}")
-    assert (got["rgba8"][..., :3][np.isnan(e["rgb"])] == 0).all()
+    lg.check_nan_frame(_render(tr, e["cam"], W, H, depth, S, A), e, S)
 
 
 # 5. focus ----------------------------------------------------------------------------------------------------
@@ -161,28 +114,17 @@ def test_small_frames(tr, w, h, S):
 
 
 # 7. each output alone ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("only", ["rgba32f", "rgba8", "rgb64f", "raycount"])
+@pytest.mark.parametrize("only", lg.OUTS)
 def test_nullable_outputs(tr, only):
     S = 2
     e = dc.expected("c2", W, H, S, A)
     scene, depth = sc.scene_of("c2")
     tr.set_scene(scene)
-    got = _host(tr.render_dof(e["cam"], W, H, depth, S, A, **{k: k == only for k in
-                                                              ("rgba32f", "rgba8", "rgb64f", "raycount")}))
-    assert list(got) == [only]
-    want = {"rgba32f": sc.to_rgba32f(e["rgb"]), "rgba8": sc.to_rgba8(e["rgb"]), "rgb64f": e["rgb"],
-            "raycount": e["rc2"]}[only]
-    assert got[only].shape == want.shape and got[only].tobytes() == want.tobytes()
+    lg.check_nullable_output(only, e, lambda **flags: tr.render_dof(e["cam"], W, H, depth, S, A, **flags))
 
 
 def test_no_outputs_is_a_no_op(tr):
-    scene, depth = sc.scene_of("c2")
-    tr.set_scene(scene)
-    cam = scenes.make_camera(W, H, 500.0 / W)
-    rc = abi.lib().rt_render_dof_dev(tr._ctx, ctypes.byref(cam), W, H, depth, 2, A, None, None, None, None,
-                                     ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == abi.RT_OK
-    torch.cuda.synchronize()
+    lg.check_no_outputs_is_a_no_op(tr, "rt_render_dof_dev", A)
 
 
 # 8. no per-view side effect ----------------------------------------------------------------------------------
@@ -192,21 +134,15 @@ def test_no_per_view_side_effect(fresh):
     scene, depth = sc.scene_of("c2")
     fresh.set_scene(scene)
     cam = scenes.make_camera(W, H, 500.0 / W)
-    want, want_rc = po.render(scene.to_abi(), cam, W, H, depth)
-    frames = [_host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True, raycount=True))
-              for _ in range(3)]
-    assert frames[0]["rgb64f"].tobytes() == want.tobytes()
-    assert np.array_equal(frames[0]["raycount"], want_rc)
+    frames = lg.view_frames(fresh, scene, cam, depth)
     other = scenes.make_camera(W, H, 500.0 / W)
     other.eye[0] += 40.0
     other.eye[1] += 25.0
     for c, S, ap in ((cam, 2, 3.0), (other, 4, A), (other, 2, 0.0)):
         e = dc.render(scene, c, W, H, depth, S, ap)
         _check_all(_render(fresh, c, W, H, depth, S, ap), e["rgb"], e["rc2"], f"S={S} A={ap}")
-    frames.append(_host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True, raycount=True)))
-    for k, f in enumerate(frames[1:]):
-        for key in ("rgba32f", "rgba8", "rgb64f", "raycount"):
-            assert f[key].tobytes() == frames[0][key].tobytes(), (k + 1, key)
+    lg.check_view_unchanged(frames, _host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True,
+                                                       raycount=True)))
 
 
 # 9. hipGraph capture -----------------------------------------------------------------------------------------
@@ -215,23 +151,8 @@ def test_graph_capture(fresh):
     e = dc.expected("c2", W, H, S, A)
     scene, depth = sc.scene_of("c2")
     fresh.set_scene(scene)
-    bufs = fresh.alloc_ss(W, H, None, rgba32f=True, rgba8=True, rgb64f=True, raycount=True)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        fresh.render_dof_into(e["cam"], W, H, depth, S, A, bufs, stream=s)       # warm-up outside the capture
-    s.synchronize()
-    _check_all(_host(bufs), e["rgb"], e["rc2"], "direct")
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fresh.render_dof_into(e["cam"], W, H, depth, S, A, bufs, stream=s)
-    for k in range(2):
-        for b in bufs.values():
-            if b is not None:
-                b.zero_()
-        g.replay()
-        _check_all(_host(bufs), e["rgb"], e["rc2"], f"replay {k}")
-        plain = _host(fresh.render(e["cam"], W, H, depth, rgb64f=True))          # another render in between
-        assert plain["rgb64f"].shape == (H, W, 3)
+    lg.check_graph_capture(fresh, e, depth,
+                           lambda bufs, s: fresh.render_dof_into(e["cam"], W, H, depth, S, A, bufs, stream=s))
 
 
 # 10. rt_render_dof: host buffers and the CLI -------------------------------------------------------------------
@@ -240,29 +161,12 @@ def test_render_dof_host_buffers(tr):
     e = dc.expected("c2", W, H, S, A)
     scene, depth = sc.scene_of("c2")
     tr.set_scene(scene)
-    f32 = np.zeros((H, W, 4), np.float32)
-    u8 = np.zeros((H, W, 4), np.uint8)
-    f64 = np.zeros((H, W, 3), np.float64)
-    st = abi.rt_stats()
     s_abi = scene.to_abi()
-    abi.check(abi.lib().rt_render_dof(tr._ctx, ctypes.byref(s_abi), ctypes.byref(e["cam"]), W, H, depth, S, A,
-                                      ctypes.c_void_p(f32.ctypes.data), ctypes.c_void_p(u8.ctypes.data),
-                                      ctypes.c_void_p(f64.ctypes.data), ctypes.byref(st)), "rt_render_dof")
-    sc.assert_same_bits(f64, e["rgb"], "rt_render_dof rgb64f")
-    sc.assert_same_bits(f32, sc.to_rgba32f(e["rgb"]), "rt_render_dof rgba32f")
-    assert np.array_equal(u8, sc.to_rgba8(e["rgb"]))
-    seg, sh = int(e["rc2"][..., 0].sum(dtype=np.uint64)), int(e["rc2"][..., 1].sum(dtype=np.uint64))
-    assert st.primary_rays == W * H * S * S
-    assert st.reflect_rays == seg - W * H * S * S and st.shadow_rays == sh
+    lg.check_host_buffers(e, S, "rt_render_dof", lambda *out: abi.lib().rt_render_dof(
+        tr._ctx, ctypes.byref(s_abi), ctypes.byref(e["cam"]), W, H, depth, S, A, *out))
     # every pointer optional
     abi.check(abi.lib().rt_render_dof(tr._ctx, ctypes.byref(s_abi), ctypes.byref(e["cam"]), W, H, depth, S, A,
                                       None, None, None, None), "rt_render_dof")
-
-
-def _read_ppm(path):
-    hdr, body = open(path, "rb").read().split(b"\n", 1)
-    assert hdr.split() == [b"P6", str(W).encode(), str(H).encode(), b"255"]
-    return np.frombuffer(body, np.uint8).reshape(H, W, 3)
 
 
 @pytest.mark.parametrize("ratio", [None, 0.5])
@@ -281,8 +185,7 @@ def test_cli(tmp_path, ratio):
 # 11. argument errors -----------------------------------------------------------------------------------------
 def _call_dev(t, cam, out, w, h, S, aperture):
     return abi.lib().rt_render_dof_dev(t._ctx, ctypes.byref(cam), w, h, 1, S, aperture, None, None,
-                                       ctypes.c_void_p(out.data_ptr()), None,
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+                                       ctypes.c_void_p(out.data_ptr()), None, lg.stream_ptr())
 
 
 def test_argument_errors(tr):
@@ -297,7 +200,7 @@ def test_argument_errors(tr):
         with pytest.raises(abi.RtError) as ei:
             tr.render_dof_into(cam, W, H, depth, S, A, bufs)
         assert ei.value.code == abi.RT_EINVAL and "samples" in str(ei.value)
-    for ap in (-1.0, -1e-300, float("nan"), float("inf"), -float("inf")):
+    for ap in lg.BAD:
         assert _call_dev(tr, cam, out, W, H, 2, ap) == abi.RT_EINVAL and "aperture" in abi.last_error(), ap
         with pytest.raises(abi.RtError) as ei:
             tr.render_dof_into(cam, W, H, depth, 2, ap, bufs)

@@ -18,60 +18,24 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from oracle import pyoracle as po  # noqa: E402
 from ray_tracer_fragment_shader_amd import abi, scenes  # noqa: E402
-from ray_tracer_fragment_shader_amd.tracer import Tracer  # noqa: E402
 
 from . import dof_common as dc  # noqa: E402
+from . import lens_gpu_common as lg  # noqa: E402
 from . import motion_common as mc  # noqa: E402
 from . import soft_common as so  # noqa: E402
 from . import ssaa_common as sc  # noqa: E402
+from .lens_gpu_common import BAD, H, OUTS, W, _check_all, _host, _read_ppm, fresh, tr  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
-W, H, A, R, F = 37, 21, 8.0, 40.0, 1.0
+A, R, F = 8.0, 40.0, 1.0
 MOVES = mc.MOVES
-OUTS = ("rgba32f", "rgba8", "rgb64f", "raycount")
-
-
-@pytest.fixture(scope="module")
-def tr():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a HIP device")
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-@pytest.fixture()
-def fresh():
-    """A context of its own: the tests of the context's state."""
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a HIP device")
-    t = Tracer(0)
-    yield t
-    t.close()
-
-
-def _host(bufs):
-    torch.cuda.synchronize()
-    out = {k: v.cpu().numpy() for k, v in bufs.items() if v is not None}
-    if "raycount" in out:
-        out["raycount"] = out["raycount"].view(np.uint32)
-    return out
 
 
 def _render(t, cam, w, h, depth, S, aperture, light_size, shutter):
     return _host(t.render_motion(cam, w, h, depth, S, aperture, light_size, shutter, rgba32f=True, rgba8=True,
                                  rgb64f=True, raycount=True))
-
-
-def _check_all(got, rgb, rc2, what):
-    """Every output of a motion-blurred render against the expected float64 frame and counters."""
-    sc.assert_same_bits(got["rgb64f"], rgb, what + " rgb64f")
-    sc.assert_same_bits(got["rgba32f"], sc.to_rgba32f(rgb), what + " rgba32f")
-    assert np.array_equal(got["rgba8"], sc.to_rgba8(rgb)), what + " rgba8"
-    assert got["raycount"].shape == rc2.shape and np.array_equal(got["raycount"], rc2), what + " raycount"
 
 
 def _scene_run(t, scene, cam, w, h, depth, S, aperture, light_size, shutter, d, what):
@@ -175,17 +139,8 @@ def test_frozen_pinhole_is_the_ssaa_fixture(tr, name, S):
 # 4. S = 1 ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["c2", "demo"])
 def test_one_sample_is_the_plain_render(tr, name):
-    scene, depth = sc.scene_of(name)
-    tr.set_scene(scene)
-    tr.set_motion(mc.displacement(scene, MOVES[name]))
-    cam = scenes.make_camera(W, H, 500.0 / W)
-    want, want_rc = po.render(scene.to_abi(), cam, W, H, depth)
-    plain = _host(tr.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True))
-    assert plain["rgb64f"].tobytes() == want.tobytes()
-    got = _render(tr, cam, W, H, depth, 1, A, R, F)
-    for k in ("rgba32f", "rgba8", "rgb64f"):
-        assert got[k].tobytes() == plain[k].tobytes(), k
-    assert np.array_equal(got["raycount"], sc.reduce_counts(want_rc, 1))
+    lg.check_one_sample_is_the_plain_render(tr, name, lambda cam, depth: _render(tr, cam, W, H, depth, 1, A, R, F),
+                                            lambda scene: tr.set_motion(mc.displacement(scene, MOVES[name])))
 
 
 # 5. sphere counts: one batch, the padding, a second batch, the >= 16 path, an index >= 64 ------------------------
@@ -263,10 +218,7 @@ def test_nan_frames(tr, S):
     assert depth == 3
     tr.set_scene(scene)
     tr.set_motion(e["d"])
-    got = _render(tr, e["cam"], W, H, depth, S, 0.0, 0.0, F)
-    assert np.array_equal(np.isnan(got["rgb64f"]), np.isnan(e["rgb"]))
-    _check_all(got, e["rgb"], e["rc2"], f"tree_c2 S={S}")
-    assert (got["rgba8"][..., :3][np.isnan(e["rgb"])] == 0).all()
+    lg.check_nan_frame(_render(tr, e["cam"], W, H, depth, S, 0.0, 0.0, F), e, S)
 
 
 # 8. a scene with no lights -----------------------------------------------------------------------------------
@@ -297,21 +249,12 @@ def test_nullable_outputs(tr, only):
     scene, depth = sc.scene_of("c2")
     tr.set_scene(scene)
     tr.set_motion(e["d"])
-    got = _host(tr.render_motion(e["cam"], W, H, depth, S, 0.0, 0.0, F, **{k: k == only for k in OUTS}))
-    assert list(got) == [only]
-    want = {"rgba32f": sc.to_rgba32f(e["rgb"]), "rgba8": sc.to_rgba8(e["rgb"]), "rgb64f": e["rgb"],
-            "raycount": e["rc2"]}[only]
-    assert got[only].shape == want.shape and got[only].tobytes() == want.tobytes()
+    lg.check_nullable_output(only, e,
+                             lambda **flags: tr.render_motion(e["cam"], W, H, depth, S, 0.0, 0.0, F, **flags))
 
 
 def test_no_outputs_is_a_no_op(tr):
-    scene, depth = sc.scene_of("c2")
-    tr.set_scene(scene)
-    cam = scenes.make_camera(W, H, 500.0 / W)
-    rc = abi.lib().rt_render_motion_dev(tr._ctx, ctypes.byref(cam), W, H, depth, 2, A, R, F, None, None, None, None,
-                                        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == abi.RT_OK
-    torch.cuda.synchronize()
+    lg.check_no_outputs_is_a_no_op(tr, "rt_render_motion_dev", A, R, F)
 
 
 # 11. the context's other state ---------------------------------------------------------------------------------
@@ -322,11 +265,7 @@ def test_no_side_effect(fresh):
     scene, depth = sc.scene_of("c2")
     fresh.set_scene(scene)
     cam = scenes.make_camera(W, H, 500.0 / W)
-    want, want_rc = po.render(scene.to_abi(), cam, W, H, depth)
-    frames = [_host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True, raycount=True))
-              for _ in range(3)]
-    assert frames[0]["rgb64f"].tobytes() == want.tobytes()
-    assert np.array_equal(frames[0]["raycount"], want_rc)
+    frames = lg.view_frames(fresh, scene, cam, depth)
     soft = _host(fresh.render_soft(cam, W, H, depth, 2, A, R, rgba32f=True, rgba8=True, rgb64f=True, raycount=True))
     sc.assert_same_bits(soft["rgb64f"], so.expected("c2", W, H, 2, A, R)["rgb"], "soft frame")
     other = scenes.make_camera(W, H, 500.0 / W)
@@ -338,10 +277,8 @@ def test_no_side_effect(fresh):
         e = mc.render(scene, c, W, H, depth, S, A, R, F, d)
         _check_all(_render(fresh, c, W, H, depth, S, A, R, F), e["rgb"], e["rc2"], f"S={S} {moves}")
     fresh.set_motion(mc.displacement(scene, MOVES["c2"]))                            # left set: others ignore it
-    frames.append(_host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True, raycount=True)))
-    for k, f in enumerate(frames[1:]):
-        for key in OUTS:
-            assert f[key].tobytes() == frames[0][key].tobytes(), (k + 1, key)
+    lg.check_view_unchanged(frames, _host(fresh.render(cam, W, H, depth, rgba32f=True, rgba8=True, rgb64f=True,
+                                                       raycount=True)))
     again = _host(fresh.render_soft(cam, W, H, depth, 2, A, R, rgba32f=True, rgba8=True, rgb64f=True, raycount=True))
     for key in OUTS:
         assert again[key].tobytes() == soft[key].tobytes(), key
@@ -372,23 +309,8 @@ def test_graph_capture(fresh):
     scene, depth = sc.scene_of("c2")
     fresh.set_scene(scene)
     fresh.set_motion(e["d"])
-    bufs = fresh.alloc_ss(W, H, None, rgba32f=True, rgba8=True, rgb64f=True, raycount=True)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        fresh.render_motion_into(e["cam"], W, H, depth, S, 0.0, 0.0, F, bufs, stream=s)   # warm-up outside the capture
-    s.synchronize()
-    _check_all(_host(bufs), e["rgb"], e["rc2"], "direct")
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fresh.render_motion_into(e["cam"], W, H, depth, S, 0.0, 0.0, F, bufs, stream=s)
-    for k in range(2):
-        for b in bufs.values():
-            if b is not None:
-                b.zero_()
-        g.replay()
-        _check_all(_host(bufs), e["rgb"], e["rc2"], f"replay {k}")
-        plain = _host(fresh.render(e["cam"], W, H, depth, rgb64f=True))              # another render in between
-        assert plain["rgb64f"].shape == (H, W, 3)
+    lg.check_graph_capture(fresh, e, depth, lambda bufs, s: fresh.render_motion_into(e["cam"], W, H, depth, S, 0.0, 0.0,
+                                                                                     F, bufs, stream=s))
 
 
 # 13. rt_render_motion: host buffers and the CLI ----------------------------------------------------------------
@@ -396,33 +318,16 @@ def test_render_motion_host_buffers(tr):
     S = 4
     e = mc.expected("c2", W, H, S, 0.0, 0.0, F, MOVES["c2"])
     scene, depth = sc.scene_of("c2")
-    f32 = np.zeros((H, W, 4), np.float32)
-    u8 = np.zeros((H, W, 4), np.uint8)
-    f64 = np.zeros((H, W, 3), np.float64)
-    st = abi.rt_stats()
     s_abi = scene.to_abi()
     d = np.ascontiguousarray(e["d"])
     dp = d.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-    abi.check(abi.lib().rt_render_motion(tr._ctx, ctypes.byref(s_abi), dp, ctypes.byref(e["cam"]), W, H, depth, S, 0.0,
-                                         0.0, F, ctypes.c_void_p(f32.ctypes.data), ctypes.c_void_p(u8.ctypes.data),
-                                         ctypes.c_void_p(f64.ctypes.data), ctypes.byref(st)), "rt_render_motion")
-    sc.assert_same_bits(f64, e["rgb"], "rt_render_motion rgb64f")
-    sc.assert_same_bits(f32, sc.to_rgba32f(e["rgb"]), "rt_render_motion rgba32f")
-    assert np.array_equal(u8, sc.to_rgba8(e["rgb"]))
-    seg, sh = int(e["rc2"][..., 0].sum(dtype=np.uint64)), int(e["rc2"][..., 1].sum(dtype=np.uint64))
-    assert st.primary_rays == W * H * S * S
-    assert st.reflect_rays == seg - W * H * S * S and st.shadow_rays == sh
+    f64 = lg.check_host_buffers(e, S, "rt_render_motion", lambda *out: abi.lib().rt_render_motion(
+        tr._ctx, ctypes.byref(s_abi), dp, ctypes.byref(e["cam"]), W, H, depth, S, 0.0, 0.0, F, *out))
     # every pointer optional; no displacement: the frozen frame
     abi.check(abi.lib().rt_render_motion(tr._ctx, ctypes.byref(s_abi), None, ctypes.byref(e["cam"]), W, H, depth, S,
                                          0.0, 0.0, F, None, None, ctypes.c_void_p(f64.ctypes.data), None),
               "rt_render_motion")
     sc.assert_same_bits(f64, so.expected("c2", W, H, S, 0.0, 0.0)["rgb"], "rt_render_motion without displacement")
-
-
-def _read_ppm(path):
-    hdr, body = open(path, "rb").read().split(b"\n", 1)
-    assert hdr.split() == [b"P6", str(W).encode(), str(H).encode(), b"255"]
-    return np.frombuffer(body, np.uint8).reshape(H, W, 3)
 
 
 @pytest.mark.parametrize("extra", [None, "panel and lens"])
@@ -444,11 +349,7 @@ def test_cli(tmp_path, extra):
 # 14. argument errors -----------------------------------------------------------------------------------------
 def _call_dev(t, cam, out, w, h, S, aperture, light_size, shutter):
     return abi.lib().rt_render_motion_dev(t._ctx, ctypes.byref(cam), w, h, 1, S, aperture, light_size, shutter, None,
-                                          None, ctypes.c_void_p(out.data_ptr()), None,
-                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-
-
-BAD = (-1.0, -1e-300, float("nan"), float("inf"), -float("inf"))
+                                          None, ctypes.c_void_p(out.data_ptr()), None, lg.stream_ptr())
 
 
 def test_argument_errors(tr):

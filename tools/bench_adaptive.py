@@ -31,6 +31,7 @@ import torch  # noqa: E402
 
 from ray_tracer_fragment_shader_amd import scenes  # noqa: E402
 from ray_tracer_fragment_shader_amd.tracer import Tracer  # noqa: E402
+from tools.sampled_bench import block_ms  # noqa: E402
 
 
 class Leg:
@@ -53,16 +54,6 @@ class Leg:
             self.tr.render_ss_into(*self.args, self.samples, self.bufs)
         else:
             self.tr.render_into(*self.args, self.bufs)
-
-
-def block_ms(leg, n):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(n):
-        leg.frame()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / n
 
 
 def main():
