@@ -86,6 +86,19 @@ int rt_diag_sky_tiles(const rt_scene* scene, const rt_camera* cam, int width, in
  * *sky how many took the early-out.  Both 0 when no calibrated view holds verdicts.  Waits for the device. */
 int rt_diag_sky_count(rt_ctx* ctx, int* tiles, int* sky);
 
+/* Runs of sky tiles: a cached render of a calibrated static view sends one wave per run of up to RT_SKY_RUN_MAX
+ * adjacent sky tiles of a tile row (read by rt_ctx_create; 1: one wave per tile, 0: whole streaks), from a
+ * run-compacted dispatch table its calibration builds beside the plain one.  Images are the same bytes either way.
+ * rt_diag_sky_run_plan evaluates the plan on the host, no device needed, with the function the device runs: for the
+ * verdict grid sky[ty * tiles_x + tx] (nonzero: sky) and run_max >= 1, run[ty * tiles_x + tx] = 0 for a tile that is
+ * a dispatch position of its own and traces, len >= 1 for the first tile of a run of len sky tiles, -1 for the run's
+ * other tiles; *positions the dispatch positions in all.  RT_EINVAL for bad arguments.
+ * rt_diag_disp_count: what the last cached render of this context's calibrated view launched — *positions its dispatch
+ * positions, *tiles the view's tiles, *run_max the longest run its table may hold (1: the plain table, positions =
+ * tiles).  All 0 before the first such render. */
+int rt_diag_sky_run_plan(const uint8_t* sky, int tiles_x, int tiles_y, int run_max, int32_t* run, int* positions);
+int rt_diag_disp_count(rt_ctx* ctx, int* positions, int* tiles, int* run_max);
+
 #ifdef __cplusplus
 }
 #endif

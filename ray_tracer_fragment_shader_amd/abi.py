@@ -208,10 +208,12 @@ SIGNATURES = {
     "rt_diag_render_route": (c_int, [c_int] * 13 + [_P(c_int)]),
     "rt_diag_sky_tiles": (c_int, [_P(rt_scene), _P(rt_camera), c_int, c_int, _P(rt_rows), c_void_p, ctypes.c_size_t]),
     "rt_diag_sky_count": (c_int, [c_void_p, _P(c_int), _P(c_int)]),
+    "rt_diag_sky_run_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _P(c_int)]),
+    "rt_diag_disp_count": (c_int, [c_void_p, _P(c_int), _P(c_int), _P(c_int)]),
 }
 
 _DIAG = {"rt_diag_tile_order", "rt_diag_kernel_resources", "rt_diag_kernel_occupancy", "rt_diag_copy_path",
-         "rt_diag_render_route", "rt_diag_sky_tiles", "rt_diag_sky_count"}
+         "rt_diag_render_route", "rt_diag_sky_tiles", "rt_diag_sky_count", "rt_diag_sky_run_plan", "rt_diag_disp_count"}
 _lib = None
 
 

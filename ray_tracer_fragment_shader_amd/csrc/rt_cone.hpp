@@ -220,4 +220,21 @@ inline bool sky_tile(const ConeCam& C, const DevSphereCone* cone, int np, const 
     return false;
 }
 
+// The run plan of one tile row of a cached view's dispatch, tile by tile (rt_kernel.hip rt_run_plan_kernel on the device,
+// rt_diag_sky_run_plan on the host): the row's n tiles in dispatch order, sky(x) their verdicts.  A tile that is not sky
+// is a dispatch position of its own (0).  A maximal streak of sky tiles is cut from its first tile into runs of at most
+// run_max tiles, each one position: its first tile is the run's head (the run's length, 1 .. run_max), the others are
+// covered by it (-1).  So runs never leave the row, every tile belongs to exactly one position, and run_max = 1 is one
+// position per tile.
+template <class Sky>
+RT_HD int sky_run_at(int n, int run_max, int x, Sky sky) {
+    if (!sky(x)) return 0;
+    int first = x;
+    while (first > 0 && sky(first - 1)) --first;
+    if ((x - first) % run_max != 0) return -1;
+    int len = 1;
+    while (len < run_max && x + len < n && sky(x + len)) ++len;
+    return len;
+}
+
 }  // namespace rt

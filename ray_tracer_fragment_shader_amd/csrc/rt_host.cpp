@@ -831,6 +831,25 @@ extern "C" int rt_diag_sky_tiles(const rt_scene* scene, const rt_camera* cam, in
     return RT_OK;
 }
 
+// The run plan of a grid of sky verdicts (include/rt_diag.h), tile by tile through the function the device's table
+// kernel runs (rt_cone.hpp sky_run_at).
+extern "C" int rt_diag_sky_run_plan(const uint8_t* sky, int tiles_x, int tiles_y, int run_max, int32_t* run,
+                                    int* positions) {
+    if (!sky || !run || !positions || tiles_x <= 0 || tiles_y <= 0 || run_max < 1)
+        return rt_fail(RT_EINVAL, "rt_diag_sky_run_plan: bad arguments");
+    int n = 0;
+    for (int ty = 0; ty < tiles_y; ++ty) {
+        const uint8_t* v = sky + (size_t)ty * tiles_x;
+        int32_t* r = run + (size_t)ty * tiles_x;
+        for (int x = 0; x < tiles_x; ++x) {
+            r[x] = rt::sky_run_at(tiles_x, run_max, x, [&](int q) { return v[q] != 0; });
+            n += r[x] >= 0;
+        }
+    }
+    *positions = n;
+    return RT_OK;
+}
+
 extern "C" int rt_write_ppm(const char* path, const uint8_t* px, int W, int H, int channels) {
     // writePpmScreenshot (Hw4/ppm.cpp:15-25): header "P6 W H 255\n", then the bottom-up GL image's rows
     // written top-down (image[3*w*(h-1-i)]).

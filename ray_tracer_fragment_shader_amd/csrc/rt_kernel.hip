@@ -131,6 +131,48 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     disp[cone_slot(k, n)] = r;
 }
 
+// The run-compacted dispatch table of a calibrated view in tile-row order (include/rt_diag.h; the plain table stays
+// beside it for every render that may not read runs).  rt_run_plan_kernel, one workgroup per dispatch row gy: the
+// row's verdicts (the calibration render's) in LDS, one byte per tile (tiles_x bytes of dynamic LDS), then the plan
+// (rt_cone.hpp sky_run_at) tile by tile, as a code per plain position — 0 covered by the run that starts to its left,
+// 1 a tracing tile, 1 + len the head of a run of len sky tiles.  An inclusive prefix sum of (code != 0) then numbers
+// the heads (hipcub, render_build_dispatch), and rt_run_disp_kernel writes each head's record at cone_slot(its number,
+// the heads' count).
+__global__ __launch_bounds__(256) void rt_run_plan_kernel(const int32_t* __restrict__ row_order,
+                                                          const uint64_t* __restrict__ sky, int tiles_x, int run_max,
+                                                          uint32_t* __restrict__ code) {
+    extern __shared__ uint8_t row_sky[];
+    const int gy = (int)blockIdx.x;
+    const uint64_t* v = sky + (size_t)row_order[gy] * tiles_x;
+    for (int x = threadIdx.x; x < tiles_x; x += 256) row_sky[x] = v[tile_col(x, gy, tiles_x)] != 0;
+    __syncthreads();
+    for (int x = threadIdx.x; x < tiles_x; x += 256)
+        code[(size_t)gy * tiles_x + x] =
+            (uint32_t)(1 + sky_run_at(tiles_x, run_max, x, [&](int q) { return row_sky[q] != 0; }));
+}
+
+struct RunHead {
+    __host__ __device__ uint32_t operator()(uint32_t code) const { return code != 0 ? 1u : 0u; }
+};
+
+__global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restrict__ row_order,
+                                                          const uint64_t* __restrict__ cone,
+                                                          const uint32_t* __restrict__ code,
+                                                          const uint32_t* __restrict__ number, int tiles_x, int tiles_y,
+                                                          DispRec* __restrict__ disp) {
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
+    if (k >= n || code[k] == 0) return;
+    const int gy = (int)(k / tiles_x), bx = (int)(k - (size_t)gy * tiles_x);
+    const int ty = row_order[gy], tx = tile_col(bx, gy, tiles_x);
+    const uint64_t m = cone[(size_t)ty * tiles_x + tx];
+    DispRec r;
+    r.cone_lo = (uint32_t)m;
+    r.cone_hi = (uint32_t)(m >> 32);
+    r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
+    r.sky = code[k] - 1u;
+    disp[cone_slot(number[k] - 1u, number[n - 1])] = r;   // (number[n - 1]: the heads' count, at most n)
+}
+
 // Per-eye primary-ray sphere data (run by rt_render_dev when the camera eye changes): deltaP = C - eye
 // and dot(deltaP, deltaP) exactly as Shape::intersection computes them for p0 = camera (:740, :750), and
 // the FP32 filter image f32(deltaP), c0 = (r2 - dd) + K (S0^2 + r2) rounded up, S0 = max|deltaP_i|.
@@ -635,6 +677,27 @@ struct rt_ctx {
     // leaves its waves' verdicts behind the cone masks in d_cone_tile (sky_tiles_n of them: rt_diag_sky_count).
     bool sky_tiles = true;
     size_t sky_tiles_n = 0;
+    // Runs of sky tiles (rt_run_plan_kernel): beside d_disp the calibration of a view in tile-row order builds
+    // d_disp_run, one position per run of up to sky_run_max adjacent sky tiles (RT_SKY_RUN_MAX; 1: no run table,
+    // 0: whole streaks), from the per-position codes d_run_code and their prefix sum d_run_num (hipcub, d_run_tmp).
+    // Its position count reaches the host without a stall of the calibrating call: a copy into the pinned word
+    // h_run_n queued behind the table kernels, then run_ev; the next render of the view waits for run_ev (long
+    // passed, as a rule) and sizes its grid from the count (run_n; run_w positions per grid row).  Only cached
+    // renders of exactly that view read d_disp_run (render_plan_view); it is view state like d_disp (view_ev).
+    int sky_run_max = 16;
+    DispRec* d_disp_run = nullptr;
+    uint32_t* d_run_code = nullptr;
+    uint32_t* d_run_num = nullptr;
+    void* d_run_tmp = nullptr;
+    size_t run_tmp_bytes = 0;
+    uint32_t* h_run_n = nullptr;
+    hipEvent_t run_ev = nullptr;
+    bool run_pending = false;                  // run_ev recorded, h_run_n not read yet
+    bool run_valid = false;                    // d_disp_run holds view order_key's table of run_n positions
+    uint32_t run_n = 0;
+    int run_w = 0, run_rows = 0;
+    int run_built_max = 1;                     // the run maximum d_disp_run was built with
+    int last_positions = 0, last_tiles = 0, last_run_max = 0;   // rt_diag_disp_count
     // Cross-stream ordering of the per-view state: the per-eye records inside d_scene (rt_prepare_kernel) and the
     // calibration buffers (d_row_cost, d_tile_rows, d_tile_cost, d_cone_tile, d_disp).  Every render reads the per-eye
     // records; a render that prepares a new eye or calibrates also writes.  A writer records view_ev on its stream
@@ -729,9 +792,14 @@ extern "C" int rt_device_count(int* count) {
 // The per-tile view buffers (dispatch table, tile times, cone masks, sort buffers) of a context.
 static void rt_free_view_bufs(rt_ctx* c) {
     void* bufs[] = {c->d_disp, c->d_tile_cost, c->d_cone_tile, c->d_sort_keys, c->d_sort_in, c->d_sort_out,
-                    c->d_sort_tmp};
+                    c->d_sort_tmp, c->d_disp_run, c->d_run_code, c->d_run_num, c->d_run_tmp};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    c->d_disp_run = nullptr;
+    c->d_run_code = c->d_run_num = nullptr;
+    c->d_run_tmp = nullptr;
+    c->run_tmp_bytes = 0;
+    c->run_valid = c->run_pending = false;
     c->d_disp = nullptr;
     c->d_tile_cost = c->d_sort_keys = nullptr;
     c->d_cone_tile = nullptr;
@@ -765,6 +833,27 @@ static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
         rt_free_view_bufs(c);
         return false;
     }
+    // the run table's buffers (all or none: without them every render reads the plain table)
+    if (c->sky_run_max != 1) {
+        size_t tmp = 0;
+        const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(c->d_run_code, RunHead{});
+        const bool run_ok = hipMalloc(&c->d_disp_run, slots * sizeof(DispRec)) == hipSuccess &&
+                            hipMalloc(&c->d_run_code, tiles * sizeof(uint32_t)) == hipSuccess &&
+                            hipMalloc(&c->d_run_num, tiles * sizeof(uint32_t)) == hipSuccess &&
+                            hipcub::DeviceScan::InclusiveSum(nullptr, tmp, heads, c->d_run_num, (int)tiles) == hipSuccess &&
+                            hipMalloc(&c->d_run_tmp, std::max(tmp, (size_t)16)) == hipSuccess;
+        if (run_ok) {
+            c->run_tmp_bytes = tmp;
+        } else {
+            (void)hipGetLastError();
+            void* rb[] = {c->d_disp_run, c->d_run_code, c->d_run_num, c->d_run_tmp};
+            for (void* b : rb)
+                if (b) (void)hipFree(b);
+            c->d_disp_run = nullptr;
+            c->d_run_code = c->d_run_num = nullptr;
+            c->d_run_tmp = nullptr;
+        }
+    }
     c->view_cap = tiles;
     return true;
 }
@@ -796,6 +885,8 @@ extern "C" int rt_ctx_destroy(rt_ctx* c) {
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->view_ev) (void)hipEventDestroy(c->view_ev);
+    if (c->run_ev) (void)hipEventDestroy(c->run_ev);
+    if (c->h_run_n) (void)hipHostFree(c->h_run_n);
     for (int b = 0; b < rt_ctx::kSlots; ++b) {
         if (c->rendered[b]) (void)hipEventDestroy(c->rendered[b]);
         if (c->copied[b]) (void)hipEventDestroy(c->copied[b]);
@@ -833,6 +924,7 @@ extern "C" int rt_ctx_create(int device, rt_ctx** out) {
     if (const char* e = getenv("RT_CONE_CACHE")) c->cone_cache = atoi(e) != 0;
     if (const char* e = getenv("RT_LEVEL_MASKS")) c->level_masks = atoi(e) != 0;
     if (const char* e = getenv("RT_SKY_TILES")) c->sky_tiles = atoi(e) != 0;
+    if (const char* e = getenv("RT_SKY_RUN_MAX")) c->sky_run_max = std::min(std::max(atoi(e), 0), 65535);   // 0: whole streaks
     if (const char* e = getenv("RT_ORDER_POLICY")) c->order_policy = std::min(std::max(atoi(e), 0), 1);
     if (const char* e = getenv("RT_ACHRO_OFF")) c->achro_off = atoi(e) != 0;
     if (hipMalloc(&c->d_tile_rows, sizeof(int32_t) * kOrderMax) != hipSuccess ||
@@ -844,6 +936,8 @@ extern "C" int rt_ctx_create(int device, rt_ctx** out) {
     bool ok = hipMemset(c->d_tile_rows, 0, sizeof(int32_t) * kOrderMax) == hipSuccess &&
               hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
               hipEventCreateWithFlags(&c->view_ev, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&c->run_ev, hipEventDisableTiming) == hipSuccess &&
+              hipHostMalloc(&c->h_run_n, sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
               hipStreamCreateWithFlags(&c->rs, hipStreamDefault) == hipSuccess &&
               hipStreamCreateWithFlags(&c->cs, hipStreamNonBlocking) == hipSuccess;
     for (int b = 0; b < rt_ctx::kSlots && ok; ++b)
@@ -1029,7 +1123,28 @@ struct RenderJob {
     rt_ctx::ViewKey key;
     bool calibrate, cone_calib, lm_calib;               // this render times its tiles / records cone / level masks
     bool prepare;                                       // ... writes the per-eye scene records first
+    bool runs;                                          // the launch reads the run-compacted table (c->run_*)
 };
+
+// The grid of a launch over n dispatch positions of a table of its own width: w positions per grid row, at most kGridY
+// rows, so that the rows x w - n padding positions (each traces a clamped tile and stores nothing) number at most 7
+// wherever such a width exists in the range searched (w = 8 always is one up to 8 kGridY positions), else the fewest.
+static void run_grid(uint32_t n, int* w, int* rows) {
+    if (n <= 1024) {
+        *w = (int)n;
+        *rows = 1;
+        return;
+    }
+    const uint32_t lo = std::max(8u, (n + kGridY - 1) / kGridY);
+    uint32_t best = std::max(lo, 1024u), best_pad = ~0u;
+    for (uint32_t k = std::max(lo, 1024u); k >= lo; --k) {
+        const uint32_t pad = (k - n % k) % k;
+        if (pad < best_pad) best = k, best_pad = pad;
+        if (pad <= 7) break;
+    }
+    *w = (int)best;
+    *rows = (int)((n + best - 1) / best);
+}
 
 // Step 1: the kernel parameters, the pixel formats and the output mode; the kernel instance of the frame.
 static int render_job_params(rt_ctx* c, int fmt_f, int fmt_8, RenderJob& J) {
@@ -1074,7 +1189,7 @@ static int render_plan_view(rt_ctx* c, RenderJob& J) {
     RT_HIP(hipStreamIsCapturing(J.st, &cap));
     J.capturing = cap != hipStreamCaptureStatusNone;
     if (J.capturing) c->ever_captured = true;
-    J.calibrate = J.cone_calib = J.lm_calib = false;
+    J.calibrate = J.cone_calib = J.lm_calib = J.runs = false;
     // level masks per tile (opaque scenes, one-wave tiles): B ray masks + (B + 1) nl shadow masks.  The culling
     // kernels compute them in their calibration render; for the fast kernels' scenes (< kConeMin spheres) a culling
     // kernel writes them in a launch of its own right after the calibration render (no image outputs), and later
@@ -1107,6 +1222,23 @@ static int render_plan_view(rt_ctx* c, RenderJob& J) {
             P.disp = c->d_disp;
             // (the cached masks hold one mask per one-wave 8 x 8 tile: the 256-thread A/B instances never read them)
             P.cone_use = c->cone_valid && !big ? 1 : 0;
+            // the run-compacted table of this view, once its position count has arrived (a wait that has, as a rule,
+            // long passed: the copy was queued behind the calibration's table kernels)
+            if (c->run_pending) {
+                c->run_pending = false;
+                if (hipEventSynchronize(c->run_ev) == hipSuccess) {
+                    c->run_n = *c->h_run_n;
+                    c->run_valid = c->run_n > 0 && c->run_n < J.tiles;   // (no sky tile: the plain table)
+                    if (c->run_valid) run_grid(c->run_n, &c->run_w, &c->run_rows);
+                } else {
+                    (void)hipGetLastError();
+                }
+            }
+            J.runs = c->run_valid && P.cone_use && P.sky;
+            if (J.runs) P.disp = c->d_disp_run;
+            c->last_positions = J.runs ? (int)c->run_n : (int)J.tiles;
+            c->last_tiles = (int)J.tiles;
+            c->last_run_max = J.runs ? c->run_built_max : 1;
             if (c->lmask_valid && J.lm_stride > 0 && c->lmask_stride == J.lm_stride) {   // this view's level masks
                 P.lmask_in = c->d_lmask;
                 P.lmask_stride = J.lm_stride;
@@ -1116,12 +1248,14 @@ static int render_plan_view(rt_ctx* c, RenderJob& J) {
             if (c->recalibrate > 0 && ++c->stale >= c->recalibrate) {   // ... re-timed every recalibrate-th render
                 J.calibrate = true;
                 c->order_valid = false;
+                c->run_valid = c->run_pending = false;
             }
         } else if (c->seen_valid && J.key == c->seen_key) {   // (by default a moving camera's views come here: the
                                                               // first render of a view in identity order, its second
                                                               // the calibration — a camera that stops is calibrated)
             J.calibrate = true;                         // calibration render (identity order)
             c->order_valid = false;                     // rt_disp_kernel rewrites d_disp below
+            c->run_valid = c->run_pending = false;      // ... and d_disp_run
             // the calibration records one mask per tile from lane 0 of its wave: one-wave workgroups only
             J.cone_calib = c->cone_cache && c->n_padded >= kPrimaryConeMin && !c->tree && !c->transparent && !big &&
                            RT_WG_FAST == 64;
@@ -1209,6 +1343,13 @@ static int render_launch(rt_ctx* c, const RenderJob& J) {
     RenderLaunch L;
     L.key = J.route.key;
     L.grid = dim3((unsigned)J.tiles_x, (unsigned)std::min(J.tiles_y, kGridY), (unsigned)((J.tiles_y + kGridY - 1) / kGridY));
+    L.disp_w = J.tiles_x;
+    L.disp_n = J.tiles_y * J.tiles_x;
+    if (J.runs) {                                   // one position per tracing tile and per run of sky tiles
+        L.grid = dim3((unsigned)c->run_w, (unsigned)c->run_rows, 1);
+        L.disp_w = c->run_w;
+        L.disp_n = (int32_t)c->run_n;
+    }
     L.lds = (size_t)J.route.lds;
     L.stream = J.st;
     L.scene = c->d_scene;
@@ -1264,6 +1405,28 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
         hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, c->d_row_cost, tiles_y, c->d_tile_rows);
         hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, c->d_tile_rows, nullptr, cones, tiles_x, tiles_y,
                            c->d_disp);
+        // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
+        // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
+        // plan runs along dispatch columns and the kernel stores image columns tx .. tx + r - 1: the same thing only
+        // while tile_col() is the identity, so an RT_XCD_SWIZZLE build (columns rotated per row) builds no run table.
+        const int run_max = c->sky_run_max == 0 ? 65535 : c->sky_run_max;
+        if (!RT_XCD_SWIZZLE && J.cone_calib && c->sky_tiles && run_max > 1 && c->d_disp_run && J.mode != kModeSS) {
+            const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(c->d_run_code, RunHead{});
+            size_t tmp = c->run_tmp_bytes;
+            hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, c->d_tile_rows,
+                               c->d_cone_tile + J.tiles, tiles_x, run_max, c->d_run_code);
+            if (hipcub::DeviceScan::InclusiveSum(c->d_run_tmp, tmp, heads, c->d_run_num, tiles, st) == hipSuccess) {
+                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, c->d_tile_rows, c->d_cone_tile, c->d_run_code,
+                                   c->d_run_num, tiles_x, tiles_y, c->d_disp_run);
+                if (hipMemcpyAsync(c->h_run_n, c->d_run_num + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   st) == hipSuccess &&
+                    hipEventRecord(c->run_ev, st) == hipSuccess) {
+                    c->run_pending = true;
+                    c->run_built_max = run_max;
+                }
+            }
+            if (!c->run_pending) (void)hipGetLastError();   // (the view keeps the plain table)
+        }
     }
     e = hipGetLastError();
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("dispatch table: ") + hipGetErrorString(e));
@@ -2265,6 +2428,15 @@ extern "C" int rt_diag_sky_count(rt_ctx* c, int* tiles, int* sky) {
     for (uint64_t x : v) n += x != 0;
     *tiles = (int)v.size();
     *sky = n;
+    return RT_OK;
+}
+
+// Diagnostics (include/rt_diag.h): the dispatch positions of the last cached render of the calibrated view.
+extern "C" int rt_diag_disp_count(rt_ctx* c, int* positions, int* tiles, int* run_max) {
+    if (!c || !positions || !tiles || !run_max) return rt_fail(RT_EINVAL, "rt_diag_disp_count: bad args");
+    *positions = c->last_positions;
+    *tiles = c->last_tiles;
+    *run_max = c->last_run_max;
     return RT_OK;
 }
 

@@ -47,6 +47,10 @@
 #ifndef RT_NT_STORES
 #define RT_NT_STORES 1                         // non-temporal RGBA32F/RGBA8 stores (0: A/B)
 #endif
+// A run of sky tiles (render_body) stores eight tiles at a time as whole rows of 64 pixels (0: tile by tile only; A/B)
+#ifndef RT_RUN_ROW_STORES
+#define RT_RUN_ROW_STORES 1
+#endif
 #ifndef RT_WG_FAST
 #define RT_WG_FAST 64                          // workgroup of the default render kernels: 64 (8 x 8) or 128 (16 x 8)
 #endif
@@ -138,9 +142,10 @@ __host__ __device__ __forceinline__ size_t cone_slot(size_t L, size_t n) { retur
 __host__ __device__ __forceinline__ size_t cone_slots(size_t n) { return ((n + 7) >> 3) << 3; }
 
 // One dispatch position of a calibrated view (rt_kernel.hip rt_disp_kernel): the tile its workgroup traces
-// (ty << 16 | tx), that tile's primary cone mask and its sky verdict (1: no primary ray of the tile hits anything;
-// both valid when RenderParams::cone_use).  The table is indexed by cone_slot(position): one 16-byte scalar load per
-// wave brings all three.
+// (ty << 16 | tx), that tile's primary cone mask and its sky verdict (0: trace; r >= 1: no primary ray of the r tiles
+// tx .. tx + r - 1 of that tile row hits anything — r = 1 in the plain table, up to the run maximum in the run-compacted
+// one, rt_run_disp_kernel; both valid when RenderParams::cone_use).  The table is indexed by cone_slot(position): one
+// 16-byte scalar load per wave brings all three.
 struct alignas(16) DispRec {
     uint32_t cone_lo, cone_hi;
     uint32_t tile;
@@ -193,8 +198,10 @@ struct RenderParams {
 // first memory access is its dispatch record.  Measured (r05, tools/ab_libs.py, 9 rounds): preloading 4 or 6
 // dwords within +-0.8% of none at c2 / c3 / c5 (and the preloaded registers cost 20 more SGPR spills), so off.
 struct DispGeom {
-    int32_t tiles_x;                           // tiles per tile row (= grid.x)
-    int32_t n;                                 // dispatch positions with a record (tile rows x tiles_x)
+    int32_t tiles_x;                           // dispatch positions per grid row (= grid.x: the tiles per tile row, or
+                                               // the run-compacted table's own width)
+    int32_t n;                                 // dispatch positions with a record (tile rows x tiles per row, or the
+                                               // run-compacted table's count)
 };
 
 // The render kernels' arguments, in order: the kernel-argument segment lays them out as this struct (each at its
@@ -283,11 +290,12 @@ __device__ __forceinline__ unsigned char to_u8(double c) {
 // Store pixel k of the two images in their formats.  PACKED = false: RGBA32F / RGBA8 only (the benchmark
 // kernels: the runtime format branches cost c3 8% through the whole kernel's register allocation, same-box
 // A/B); PACKED = true: fmt_f / fmt_8 are kernel arguments (scalar branches).
+// (store_pixel_fmt: the formats as values, for code without the RenderParams at hand)
 template <bool PACKED>
-__device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 col, void* __restrict__ out32,
-                                            void* __restrict__ out8) {
+__device__ __forceinline__ void store_pixel_fmt(int fmt_f, int fmt_8, size_t k, d3 col, void* __restrict__ out32,
+                                                void* __restrict__ out8) {
     if (out32) {
-        if (PACKED && P.fmt_f == kFmtF_GRAY) {
+        if (PACKED && fmt_f == kFmtF_GRAY) {
             reinterpret_cast<float*>(out32)[k] = (float)col.x;
         } else {
 #if RT_NT_STORES
@@ -302,9 +310,9 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 
         }
     }
     if (out8) {
-        if (PACKED && P.fmt_8 == kFmt8_GRAY) {
+        if (PACKED && fmt_8 == kFmt8_GRAY) {
             reinterpret_cast<uint8_t*>(out8)[k] = to_u8(col.x);
-        } else if (PACKED && P.fmt_8 == kFmt8_RGB) {
+        } else if (PACKED && fmt_8 == kFmt8_RGB) {
             uint8_t* o = reinterpret_cast<uint8_t*>(out8) + 3 * k;
             o[0] = to_u8(col.x);
             o[1] = to_u8(col.y);
@@ -319,6 +327,46 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 
 #endif
         }
     }
+}
+
+template <bool PACKED>
+__device__ __forceinline__ void store_pixel(const RenderParams& P, size_t k, d3 col, void* __restrict__ out32,
+                                            void* __restrict__ out8) {
+    store_pixel_fmt<PACKED>(P.fmt_f, P.fmt_8, k, col, out32, out8);
+}
+
+// The stores of a run of sky tiles (render_body's run branch; one-wave 8 x 8 tiles): the miss constants — colour 0, one
+// ray segment, no shadow ray — of tiles tx .. tx + run - 1 of tile row ty into every output that is present, in its
+// format, under the epilogue's per-pixel width and local-row checks.  One store step per tile of the run.  ROWS: a
+// group of eight tiles that lies wholly in the run goes out row by row — step y of the group stores row y, 64
+// consecutive pixels per store instruction (1 KB of RGBA32F, 256 B of RGBA8: whole lines) instead of eight 8-pixel
+// segments — and the remainder tile by tile; the same bytes.  The run length and the loop are scalar.
+template <bool PACKED, bool ROWS>
+__device__ __forceinline__ void store_sky_run(const RenderOuts O, int width, int local_rows, int fmt_f, int fmt_8, int tx,
+                                              int ty, int run, int lane) {
+    for (int t = 0; t < run; ++t) {
+        const bool rows = ROWS && (t | 7) < run;
+        const int i_r = rows ? (tx + (t & ~7)) * 8 + lane : (tx + t) * 8 + (lane & 7);
+        const int lr_r = ty * kTileH + (rows ? (t & 7) : (lane >> 3));
+        if (i_r < width && lr_r < local_rows) {
+            const size_t k = (size_t)lr_r * width + i_r;
+            store_pixel_fmt<PACKED>(fmt_f, fmt_8, k, mk(0.0, 0.0, 0.0), O.o32, O.o8);
+            if (O.o64) { O.o64[3 * k] = 0.0; O.o64[3 * k + 1] = 0.0; O.o64[3 * k + 2] = 0.0; }
+            if (O.orc) O.orc[k] = 1u;
+        }
+    }
+}
+// ... as a function of its own, for the culling kernels: inlined into them, in either form, the run branch moved the
+// register allocation of their tracing path (7-wave instances of depth 1 and 3: 12 B/lane of scratch with the row form;
+// achromatic depth-2 instances: 71 -> 73 VGPRs, 7 -> 6 waves, even tile by tile).  Called, it is a few arguments and a
+// return.  The kernel reads the output pointers and hands them over: the kernel-argument segment pointer is the kernel's
+// alone (in a called function the builtin behind late_outputs() compiles to a null pointer).  Arguments travel in vector
+// registers, so the wave-uniform ones are made scalars again.
+template <bool PACKED, bool ROWS>
+__device__ __attribute__((noinline)) void store_sky_run_call(const RenderOuts O, int width, int local_rows, int fmt_f,
+                                                             int fmt_8, int tx, int ty, int run, int lane) {
+    const auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    store_sky_run<PACKED, ROWS>(O, uni(width), uni(local_rows), uni(fmt_f), uni(fmt_8), uni(tx), uni(ty), uni(run), lane);
 }
 
 // ---- The sample-grid contract of include/rt_api.h (rt_render_ss_dev), spelled once for render_body's supersampled
@@ -502,6 +550,56 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     // (The verdict is made a scalar again — it went through per-lane values on its way — so that the branch is a
     // scalar one and no exec mask is held through trace().)
     sky = __builtin_amdgcn_readfirstlane((int)sky) != 0;
+    // A cached view's sky record holds a run length (rt_cone.hpp sky_run_at; 1 in the plain table): the wave stores
+    // the miss constants of tiles tx .. tx + run - 1 of its tile row — what the sky epilogue below stores, pixel by
+    // pixel, under the same width and local-row checks — and retires: one prologue per run instead of one per tile.
+    // A branch of its own ahead of the screen points, so that the tracing path below is compiled as it was; the run
+    // length and the loop stay scalar (store_sky_run).  (The supersampled epilogue reduces over the wave: those views
+    // keep the plain table.  Padding positions read the last record: ty_st puts their rows past every local row.)
+    // The branch leaves before the P.tile_cost store below, and a cached render of the plain table (run = 1) takes it
+    // too: a render that times its tiles never has cone_use set (render_plan_view: the cached branch never calibrates).
+    // One that did would have to store its time here, or it would order the view by stale costs of the sky tiles.
+#if RT_WAVE_TRACE
+    // The wave's trace record, by dispatch position (a tile; in the run-compacted table a tile or a run — how many
+    // there are: rt_diag_disp_count): 4 words per position, and (level 2) 3 more behind 4 words for every tile of the
+    // frame, whatever the grid's shape: the buffer holds 7 words per tile, and positions never outnumber tiles.
+    // Padding positions leave no record.
+    const auto wave_trace = [&](uint64_t mid, uint64_t traced) {
+        const size_t tiles = (size_t)P.tile_rows_n * P.tiles_x, n = disp ? (size_t)geom.n : tiles;
+        const size_t w = (size_t)gy * (disp ? geom.tiles_x : P.tiles_x) + bxd;
+        if (!P.wtrace || tid != 0 || w >= n || n > tiles) return;
+        P.wtrace[4 * w] = t_start;
+        P.wtrace[4 * w + 1] = __builtin_amdgcn_s_memrealtime();
+        P.wtrace[4 * w + 3] = mid;
+#if RT_WAVE_TRACE >= 2
+        P.wtrace[4 * tiles + 3 * w] = t_ty;
+        P.wtrace[4 * tiles + 3 * w + 1] = t_cone;
+        P.wtrace[4 * tiles + 3 * w + 2] = traced;
+#else
+        (void)traced;
+#endif
+        P.wtrace[4 * w + 2] = (uint64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
+                              ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+    };
+#endif
+    if constexpr (kSkyInst && !SS) {
+        if (sky && P.cone_use) {
+            const int run = __builtin_amdgcn_readfirstlane((int)sky_cached);
+#if RT_WAVE_TRACE
+            const uint64_t t_run = __builtin_amdgcn_s_memrealtime();   // the run is known; its stores next
+#endif
+            if constexpr (CULL)
+                store_sky_run_call<PACKED, RT_RUN_ROW_STORES != 0>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
+                                                                   ty_st, run, lane);
+            else
+                store_sky_run<PACKED, RT_RUN_ROW_STORES != 0>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
+                                                              ty_st, run, lane);
+#if RT_WAVE_TRACE
+            wave_trace(t_run, t_run);
+#endif
+            return;
+        }
+    }
     uint32_t seg = 1, sh = 0;
     d3 col = mk(0.0, 0.0, 0.0);
 #if RT_WAVE_TRACE
@@ -575,19 +673,11 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
         if (P.tile_cost && tid == 0 && ty_st < P.tile_rows_n)
             P.tile_cost[(size_t)ty_st * P.tiles_x + tx] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_cal);
 #if RT_WAVE_TRACE
-        if (P.wtrace && tid == 0) {
-            const size_t w = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-            P.wtrace[4 * w] = t_start;
-            P.wtrace[4 * w + 1] = __builtin_amdgcn_s_memrealtime();
-            P.wtrace[4 * w + 3] = t_mid;
 #if RT_WAVE_TRACE >= 2
-            P.wtrace[4 * (size_t)P.tile_rows_n * gridDim.x + 3 * w] = t_ty;
-            P.wtrace[4 * (size_t)P.tile_rows_n * gridDim.x + 3 * w + 1] = t_cone;
-            P.wtrace[4 * (size_t)P.tile_rows_n * gridDim.x + 3 * w + 2] = t_trace;
+        wave_trace(t_mid, t_trace);
+#else
+        wave_trace(t_mid, 0);
 #endif
-            P.wtrace[4 * w + 2] = (uint64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
-                                  ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
-        }
 #endif
         return;
     }
@@ -875,6 +965,7 @@ inline RenderRoute render_route(const RouteScene& s, const RouteKnobs& k, int de
 struct RenderLaunch {
     RenderKey key;                             // the instance (render_route)
     dim3 grid;
+    int32_t disp_w, disp_n;                    // the dispatch table's DispGeom: positions per grid row, positions in all
     size_t lds;
     hipStream_t stream;
     const DevScene* scene;
@@ -1026,7 +1117,7 @@ hipError_t launch_render_impl(const RenderLaunch& L) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kern, L.grid, dim3(L.key.WG), L.lds, L.stream, L.P.disp, L.P.tiles_x, L.P.tile_rows_n * L.P.tiles_x,
+    hipLaunchKernelGGL(kern, L.grid, dim3(L.key.WG), L.lds, L.stream, L.P.disp, L.disp_w, L.disp_n,
                        L.scene, L.P, L.o32, L.o8, L.o64, L.orc);
     return hipGetLastError();
 }

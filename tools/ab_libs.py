@@ -146,7 +146,7 @@ def main():
     for (c, name), v in res.items():
         base = statistics.median(res[(c, "base")])
         med = statistics.median(v)
-        print(json.dumps({"config": c, "lib": name, "median_ms": round(med, 4), "min_ms": round(min(v), 4),
+        print(json.dumps({"config": c, "lib": name, "median_ms": round(med, 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
                           "vs_base": round(med / base - 1, 4)}))
     for name, L in libs.items():
         L.rt_ctx_destroy(ctxs[name])

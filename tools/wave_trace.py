@@ -2,6 +2,10 @@
 """Per-wave timeline of one rt_render_kernel launch (diagnostic; needs the RT_WAVE_TRACE=1 build (copied over lib/librt_amd.so) from
 tools/variants.sh, e.g. `bash tools/variants.sh trace=-DRT_WAVE_TRACE=1`).
 Reports wave durations, concurrent waves over time (per XCD and total) and the tail.
+The traced launch is a cached render of the calibrated view: with runs of sky tiles (RT_SKY_RUN_MAX, 16 by default) it
+has one wave per dispatch position — a tracing tile or a run — and the kernel records waves by position, so the
+positions the launch really had (rt_diag_disp_count) say how many records to read; RT_SKY_RUN_MAX=1 in the environment
+traces the plain table, one wave per tile.
 usage: wave_trace.py [config]"""
 import ctypes
 import json
@@ -35,9 +39,17 @@ def main():
     assert lib.rt_debug_wave_trace(ctypes.c_void_p(tr.data_ptr())) == 0
     t.render_into(cfg.camera(), W, H, cfg.depth, bufs)
     torch.cuda.synchronize()
+    # the traced launch's positions: records 0 .. n - 1 of both blocks (the second starts behind 4 words per TILE)
+    pos, tiles, run_max = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    abi.check(lib.rt_diag_disp_count(t._ctx, ctypes.byref(pos), ctypes.byref(tiles), ctypes.byref(run_max)),
+              "rt_diag_disp_count")
+    n = pos.value if tiles.value == nwg else nwg
     ab = tr.cpu().numpy()
-    a = ab[: nwg * 4].reshape(nwg, 4)
-    b = ab[nwg * 4:].reshape(nwg, 3)
+    a = ab[: nwg * 4].reshape(nwg, 4)[:n]
+    b = ab[nwg * 4:].reshape(nwg, 3)[:n]
+    if not a[:, 0].all():
+        raise SystemExit(f"wave_trace: {int((a[:, 0] == 0).sum())} of {n} positions left no record "
+                         "(is lib/librt_amd.so an RT_WAVE_TRACE build?)")
     st, en, hw, md = a[:, 0], a[:, 1], a[:, 2], a[:, 3]
     t0 = st.min()
     st, en, md = ((x - t0) * 10.0 / 1000.0 for x in (st, en, md))      # 100 MHz ticks -> us
@@ -51,7 +63,7 @@ def main():
     grid = np.linspace(0, en.max(), 41)
     conc = [int(((st <= x) & (en > x)).sum()) for x in grid]
     out = {
-        "config": name, "waves": int(nwg), "span_us": round(float(en.max()), 2),
+        "config": name, "waves": int(n), "tiles": int(nwg), "run_max": run_max.value, "span_us": round(float(en.max()), 2),
         "dur_us": {q: round(float(np.percentile(dur, q)), 2) for q in (5, 25, 50, 75, 95, 99, 100)},
         "mean_dur_us": round(float(dur.mean()), 3),
         "prologue_us": {q: round(float(np.percentile(md - st, q)), 2) for q in (5, 50, 95)},
@@ -93,19 +105,23 @@ def main():
         out["attribution_us"] = att                    # sums to the span: slot-us of each phase / resident maximum
         out["resident_max"] = int(cap)
         out["t_full_us"], out["t_drop_us"] = round(float(t_full), 2), round(float(t_drop), 2)
-        out["mean_phase_us"] = {k: round(v / nwg, 3) for k, v in phases.items()}
+        out["mean_phase_us"] = {k: round(v / n, 3) for k, v in phases.items()}
         sky = dur <= np.percentile(dur, 50)
         out["trace_us_short_half"] = round(float((t_tr - md)[sky].mean()), 3)
         out["trace_us_long_half"] = round(float((t_tr - md)[~sky].mean()), 3)
-    # duration by image row band (bottom = board rows)
+    # duration by dispatch row (one wave per tile: rows of tiles_x positions, in the view's dispatch order), or, with
+    # runs, by sixteenths of the dispatch positions
     rows = (H + 7) // 8
-    d2 = dur.reshape(rows, (W + 7) // 8)
-    out["dur_by_tile_row_us"] = [round(float(x), 2) for x in d2.mean(axis=1)[:: max(1, rows // 16)]]
+    if n == nwg:
+        d2 = dur.reshape(rows, (W + 7) // 8)
+        out["dur_by_tile_row_us"] = [round(float(x), 2) for x in d2.mean(axis=1)[:: max(1, rows // 16)]]
+    else:
+        out["dur_by_position_16ths_us"] = [round(float(x.mean()), 2) for x in np.array_split(dur, 16)]
     print(json.dumps(out))
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     np.savez(os.path.join(ROOT, "gpurun_out", f"wave_trace_{name}.npz"), start_us=st, end_us=en, hw=hw, mid_us=md,
              ty_us=t_ty, cone_us=t_cone, trace_us=t_tr,
-             tiles_x=(W + 7) // 8, tiles_y=(H + 7) // 8)
+             tiles_x=(W + 7) // 8, tiles_y=(H + 7) // 8, positions=n)
 
 
 if __name__ == "__main__":
