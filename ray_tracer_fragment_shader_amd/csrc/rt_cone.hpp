@@ -220,7 +220,7 @@ inline bool sky_tile(const ConeCam& C, const DevSphereCone* cone, int np, const 
     return false;
 }
 
-// The run plan of one tile row of a cached view's dispatch, tile by tile (rt_kernel.hip rt_run_plan_kernel on the device,
+// The run plan of one tile row of a cached view's dispatch, tile by tile (rt_plain.hip rt_run_plan_kernel on the device,
 // rt_diag_sky_run_plan on the host): the row's n tiles in dispatch order, sky(x) their verdicts.  A tile that is not sky
 // is a dispatch position of its own (0).  A maximal streak of sky tiles is cut from its first tile into runs of at most
 // run_max tiles, each one position: its first tile is the run's head (the run's length, 1 .. run_max), the others are

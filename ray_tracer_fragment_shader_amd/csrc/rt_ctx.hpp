@@ -1,0 +1,264 @@
+// rt_ctx.hpp — the context behind the C ABI's rt_ctx handle, for the device-side units only (not part of the ABI;
+// rt_host.cpp, rt_screen.cpp and rt_group.cpp see the context through the accessors of rt_internal.hpp).
+//
+// Which unit holds what (the render, ray-list and sampled kernels are templates in rt_render.hpp and rt_sampled.hpp,
+// instantiated per depth in rt_render_b<B>.hip, rt_adaptive.hip and rt_lens.hip):
+//   rt_context.hip  the context's lifetime, its A/B knobs, scene and motion upload (rt_scene_init_kernel)
+//   rt_plain.hip    the plain render path, render_dev_impl and its eight steps, and the view cache it owns: the
+//                   dispatch-table kernels (rt_order / rowsum / iota / disp / run_plan / run_disp), rt_prepare_kernel
+//   rt_diag.hip     the view diagnostics of include/rt_diag.h
+//   rt_sampled.hip  adaptive supersampling (rt_classify_kernel) and the lens family's device entry points
+//   rt_frames.hip   every call that renders into host memory: the context's device buffers, the ray sums, the packed
+//                   and asynchronous frames, the pinned-memory registry, the copy kernel and the SDMA path
+//   rt_rays.hip     the ray-list entry points (rt_intersect_kernel, rt_probe_math_kernel)
+//   rt_gather.hip   multi-GPU: gathered row bands -> image order (rt_unshuffle_kernel, rt_unpack_kernel); no context
+//
+// Each member struct of rt_ctx is written by one unit (named beside it); rt_context.hip creates and destroys them all.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <hsa/hsa.h>                           // the types of rt_ctx::Sdma only (the calls: rt_frames.hip)
+
+#include <array>
+#include <string>
+#include <vector>
+
+#include "../../include/rt_api.h"
+#include "rt_internal.hpp"
+
+namespace rtk {
+struct DispRec;                                // rt_render.hpp
+struct RenderParams;
+}  // namespace rtk
+
+constexpr int kOrderMax = 8192;                // tile rows rt_order_kernel sorts (one workgroup, keys in LDS)
+#ifndef RT_CONE_CACHE_DEFAULT
+#define RT_CONE_CACHE_DEFAULT 1
+#endif
+constexpr int kRecalibrate = 8;                // renders of a moving camera per re-timing of the tile rows
+
+struct rt_ctx {
+    int device = 0;
+
+    // The uploaded scene (rt_context.hip).
+    struct Scene {
+        rt::DevScene* d_scene = nullptr;
+        size_t cap = 0;
+        int bytes = 0;
+        int lds_bytes = 0;
+        int n_padded = 0;
+        int n_stride = 0;
+        int n_lights = 0;
+        bool set = false;
+        bool transparent = false;              // some material is transparent: TRANSP kernel variants
+        bool tree = false;                     // some material transmits and reflects: TREE kernel variants
+        bool achromatic = false;               // R = G = B everywhere (rt_scene_achromatic): GRAY formats allowed
+        std::vector<unsigned char> blob;       // host image of d_scene (rt_set_scene skips an unchanged scene)
+        uint64_t gen = 0;
+        uint64_t hash = 0;                     // FNV-1a of `blob` (rt_ctx_scene_id)
+        // Motion blur (rt_set_motion, rt_render_motion_dev): the record d_motion (rt_layout.hpp DevMotion) always
+        // describes the uploaded scene — rt_set_scene builds it with no motion — from the scene-local centres the scene
+        // was set with.
+        rt::DevMotion* d_motion = nullptr;
+        size_t motion_cap = 0;
+        std::vector<double> local_c;           // rt_sphere::center of the uploaded scene, 3 per sphere
+        std::vector<double> disp;              // the displacements in force, 3 per sphere (all 0: no motion)
+    } scene;
+
+    // The A/B knobs rt_ctx_create reads from the environment (rt_context.hip knobs_from_env; the measurements behind a
+    // default stand where the knob is read).  Only order_mode changes later (rt_diag_tile_order).
+    struct Knobs {
+        int min_waves = 5;                     // >= 5: the RT_MINW / RT_MINW_CULL launch bounds for depth <= 3 (measured faster
+                                               // than no bound: tools/ab.py); RT_MIN_WAVES=0 disables
+        int use_lds = 0;                       // RT_SCENE_IN_LDS=1: header + exact records in LDS (A/B: tools/ab.py)
+        int wg_staging = 0;                    // RT_WG_STAGING=1: LDS-staged 32-pixel row stores (A/B)
+        // Where the packed host frames' device-to-host copy runs (rt_frames.hip render_packed_queue): RT_COPY_MODE
+        // (1: rs, 0: cs, 2: the kernel stores straight into the pinned buffer, 3: SDMA), RT_COPY_KERNEL
+        // (0: hipMemcpyAsync) and RT_COPY_BLOCKS override (A/B; -1 / 0: the defaults).
+        int copy_mode = -1;
+        int copy_kernel = -1;
+        int copy_blocks = 0;                   // RT_COPY_BLOCKS: workgroups of the copy kernel (0: the defaults)
+        int order_policy = 0;                  // RT_ORDER_POLICY: 0 tile rows longest first (r01-r04), 1 tiles longest first
+        int order_mode = 0;                    // RT_TILE_ORDER, rt_diag_tile_order: 0 adaptive, 1 bottom-to-top
+        int moving_order = 0;                  // RT_MOVING_ORDER=1: a moving camera keeps the last calibrated order ...
+        int recalibrate = kRecalibrate;        // ... re-timed every RT_RECALIBRATE-th render (rt_plain.hip render_plan_view)
+        int cone_cache = RT_CONE_CACHE_DEFAULT;    // RT_CONE_CACHE=0: always compute the masks in the kernel (A/B)
+        bool level_masks = true;               // RT_LEVEL_MASKS=0: the level masks computed in every render
+        // Sky tiles (rt_render.hpp render_body): waves whose primary rays provably all miss store the miss constants
+        // without tracing.  RT_SKY_TILES=0: every wave traces (A/B; the images are the same bytes).
+        bool sky_tiles = true;
+        int sky_run_max = 16;                  // RT_SKY_RUN_MAX: adjacent sky tiles per run (1: no run table, 0: whole streaks)
+        bool achro_off = false;                // RT_ACHRO_OFF=1: the three-channel kernels for achromatic scenes (A/B)
+        int sd_split = 2;                      // RT_SDMA_SPLIT: engines a frame's copy is split over (1, 2)
+        int sd_writer_req = 0;                 // RT_SDMA_WRITER (A/B): 1 or 2 forces the writer, 0 tries 2 then 1
+        int sd_wait_ms = 5000;                 // RT_SDMA_WAIT_MS: how often sdma_wait re-checks a slow render
+    } knobs;
+
+    // The eye the per-eye records inside d_scene were prepared for (rt_plain.hip; rt_set_scene clears `valid`).
+    struct Eye {
+        double pos[3] = {0, 0, 0};
+        bool valid = false;                    // the device *Prim arrays hold data for `pos`
+        bool ever_captured = false;            // a render was captured into a hipGraph: replays may rewrite
+                                               // the per-eye data, so every later render re-prepares it
+    } eye;
+
+    // The view cache (rt_plain.hip; read by rt_diag.hip).
+    // Adaptive tile-row order (rt_order_kernel): the first render of a new (scene, camera, size, rows,
+    // depth, outputs) view uses the identity order; the second render of the same view is a calibration
+    // render that also times its tile rows; later renders dispatch the rows by decreasing time.  A render
+    // of another camera with the same frame shape (size, rows, depth, outputs, scene) reuses the last
+    // calibrated order and every kRecalibrate-th such render re-times the rows under it when RT_MOVING_ORDER=1; by
+    // default (r06) it renders in identity order.  Any order is a permutation of the tile rows: images never depend
+    // on it.
+    using ViewKey = std::array<unsigned char, sizeof(rt_camera) + 6 * sizeof(int) + sizeof(rt_rows) + sizeof(uint64_t)>;
+    struct View {
+        int32_t* d_tile_rows = nullptr;        // row order: tile rows by decreasing calibrated time
+        uint32_t* d_row_cost = nullptr;        // ... their times (rt_rowsum_kernel)
+        int n_tile_rows = 0;                   // capacity of both (kOrderMax, allocated by rt_ctx_create)
+        // The view's dispatch table (rt_disp_kernel) and what builds it, per tile (`cap` tiles each): the calibration
+        // render's wave times (d_tile_cost) and cone masks (d_cone_tile), and the tile order's radix-sort buffers.
+        rtk::DispRec* d_disp = nullptr;
+        uint32_t* d_tile_cost = nullptr;
+        uint32_t* d_sort_keys = nullptr;
+        int32_t* d_sort_in = nullptr;
+        int32_t* d_sort_out = nullptr;
+        void* d_sort_tmp = nullptr;
+        size_t sort_tmp_bytes = 0;
+        size_t cap = 0;
+        bool order_valid = false;              // d_tile_rows holds the order of view `order_key`
+        ViewKey order_key{};
+        bool seen_valid = false;               // `seen_key`: the last view rendered once in identity order
+        ViewKey seen_key{};
+        int stale = 0;                         // renders of other cameras since the order was calibrated
+        // Primary cone masks of the calibrated view (scenes with >= kPrimaryConeMin spheres): the calibration render
+        // writes each tile's mask (d_cone_tile), rt_disp_kernel puts them in the dispatch table, and later renders of
+        // exactly that view (order_key) read them instead of recomputing them.  Renders of another camera compute their
+        // own.  One-wave (8 x 8 tile) variants only.  Ordering against renders on other streams: rt_ctx::Sync.
+        uint64_t* d_cone_tile = nullptr;
+        bool cone_valid = false;               // d_disp holds the masks of view order_key
+        // r06: the culling kernels' level masks of view order_key, lmask_stride per tile (rt_device.hpp LevelMasks),
+        // written by its calibration render (grow-only, lmask_cap masks)
+        uint64_t* d_lmask = nullptr;
+        size_t lmask_cap = 0;
+        int lmask_stride = 0;
+        bool lmask_valid = false;
+        // The calibration render leaves its waves' sky verdicts behind the cone masks in d_cone_tile (sky_tiles_n of
+        // them: rt_diag_sky_count).
+        size_t sky_tiles_n = 0;
+        // Runs of sky tiles (rt_run_plan_kernel): beside d_disp the calibration of a view in tile-row order builds
+        // d_disp_run, one position per run of up to Knobs::sky_run_max adjacent sky tiles, from the per-position codes
+        // d_run_code and their prefix sum d_run_num (hipcub, d_run_tmp).
+        // Its position count reaches the host without a stall of the calibrating call: a copy into the pinned word
+        // h_run_n queued behind the table kernels, then run_ev; the next render of the view waits for run_ev (long
+        // passed, as a rule) and sizes its grid from the count (run_n; run_w positions per grid row).  Only cached
+        // renders of exactly that view read d_disp_run (render_plan_view); it is view state like d_disp (Sync::view_ev).
+        rtk::DispRec* d_disp_run = nullptr;
+        uint32_t* d_run_code = nullptr;
+        uint32_t* d_run_num = nullptr;
+        void* d_run_tmp = nullptr;
+        size_t run_tmp_bytes = 0;
+        uint32_t* h_run_n = nullptr;
+        hipEvent_t run_ev = nullptr;
+        bool run_pending = false;              // run_ev recorded, h_run_n not read yet
+        bool run_valid = false;                // d_disp_run holds view order_key's table of run_n positions
+        uint32_t run_n = 0;
+        int run_w = 0, run_rows = 0;
+        int run_built_max = 1;                 // the run maximum d_disp_run was built with
+        int last_positions = 0, last_tiles = 0, last_run_max = 0;   // rt_diag_disp_count
+    } view;
+
+    // Cross-stream ordering of the per-view state (rt_plain.hip render_order_streams, render_record_view): the per-eye
+    // records inside d_scene (rt_prepare_kernel) and the calibration buffers (d_row_cost, d_tile_rows, d_tile_cost,
+    // d_cone_tile, d_disp).  Every render reads the per-eye records; a render that prepares a new eye or calibrates
+    // also writes.  A writer records view_ev on its stream after its last write; a render on another stream first
+    // waits for view_ev on the GPU (read-after-write, write-after-write).  Renders are tracked by stream: a writer
+    // drains the device first when renders were queued on a stream other than its own since the last drain
+    // (write-after-read); same-stream renders are ordered by the stream, so one stream per context (the benchmark's
+    // layout) never waits or drains.
+    struct Sync {
+        hipEvent_t view_ev = nullptr;
+        hipStream_t view_st = nullptr;
+        bool view_rec = false;                 // view_ev was recorded (on view_st)
+        hipStream_t reader_st = nullptr;       // the stream of the renders queued since the last drain ...
+        bool readers = false;                  // ... (any)
+        bool readers_multi = false;            // ... on more than one stream
+    } sync;
+
+    // rt_render_packed_async frame t uses slot t % kSlots (device buffer 5 + slot): up to kSlots - 1 frames of
+    // latency behind the one being queued
+    static constexpr int kSlots = 3;
+
+    // The host-buffer calls (rt_frames.hip: rt_render, rt_render_packed, rt_render_packed_async) run on the context's
+    // own streams: renders on `rs` (blocking w.r.t. the null stream, like the null-stream renders it replaced), the
+    // device-to-host copies on `cs`, so an asynchronous frame's copy overlaps the next frame's render.
+    struct Frames {
+        hipStream_t rs = nullptr, cs = nullptr;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the render: rt_stats::kernel_ms
+        hipEvent_t rendered[kSlots] = {};      // slot b's packed frame is in its device buffer
+        hipEvent_t copied[kSlots] = {};        // slot b's packed frame is in its host buffer
+        bool copied_rec[kSlots] = {};
+        bool copied_cs[kSlots] = {};           // ... by a copy on the copy stream (else on the render stream)
+        uint64_t ticket = 0;                   // rt_render_packed_async frames queued so far
+        int last_copy_mode = -1;               // the mode the last packed frame took (rt_diag_copy_path)
+        // rt_render's device buffers (grow-only, reused across calls): rgba32f, rgba8, rgb64f, raycount, sums,
+        // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace
+        static constexpr int kBufRefined = 5 + kSlots, kBufAdaptive = 6 + kSlots;
+        static constexpr int kBufs = 7 + kSlots;
+        void* d_out[kBufs] = {};
+        size_t out_cap[kBufs] = {};
+    } frames;
+
+    // copy_mode 3 (rt_frames.hip sdma_*): the frame leaves on a copy (SDMA) engine — no CUs taken from the next render.
+    // Per slot, the render stream stores 0 into `dep` (hipStreamWriteValue64 on the HSA signal's value) once the frame
+    // is in its device buffer; the SDMA copies, queued with `dep` as their dependency, then move it, each decrementing
+    // its own completion signal done[slot][half] (one signal per engine copy, initialised to 1).
+    struct Sdma {
+        bool tried = false, ok = false;
+        hsa_agent_t gpu{0}, cpu{0};
+        uint32_t engine = 0, engine2 = 0;      // the two lowest free engines (engine2 = 0: only one)
+        hsa_signal_t dep[kSlots] = {}, done[kSlots][2] = {};
+        volatile hsa_signal_value_t* dep_ptr[kSlots] = {};
+        hipEvent_t fired[kSlots] = {};         // recorded on rs right after slot b's sdma_fire
+        bool pending[kSlots] = {};
+        int copies[kSlots] = {};               // engine copies queued for slot b (1 or 2)
+        int writer = 0;                        // sdma_fire: 1 stream write-value, 2 signal kernel
+    } sdma;
+};
+
+#define RT_HIP(call)                                                                                  \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess) return rt_fail(RT_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// ---- what crosses the unit boundaries ------------------------------------------------------------------------------
+inline bool float_format(int f) { return f == RT_PIXEL_RGBA32F || f == RT_PIXEL_GRAY32F; }
+
+// log2 of a supersampling factor in {1, 2, 4, 8}, or -1.
+inline int ss_log2_of(int samples) {
+    return samples == 1 ? 0 : samples == 2 ? 1 : samples == 4 ? 2 : samples == 8 ? 3 : -1;
+}
+
+// rt_plain.hip.  The per-tile view buffers freed (rt_ctx_destroy); the device render behind rt_render_dev /
+// rt_render_dev_packed, with ray counters beside a packed image (render_packed_queue); the checks every render makes
+// on its context, camera, size, depth and row plan, and the rows this process renders; the front of the sampled _dev
+// entry points.
+void rt_free_view_bufs(rt_ctx* c);
+int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows, int fmt_f, void* pf,
+                    int fmt_8, void* p8, double* rgb64f, uint32_t* raycount, void* stream, int ss_log2 = -1);
+int render_local_rows(const rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
+                      int* local_rows);
+int sample_grid_front(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int* s,
+                      rtk::RenderParams* P);
+
+// rt_sampled.hip.  The kinds of the lens family (depth of field, soft shadows, motion blur), the checks on the arguments
+// a kind reads and the family's one device render, which the host entry points of rt_frames.hip call too.
+enum LensKind { kLensDof = 0, kLensSoft = 1, kLensMotion = 2 };
+int lens_arg_checks(LensKind kind, const char* who, double aperture, double light_size, double shutter);
+int lens_render_dev(LensKind kind, const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth,
+                    int samples, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                    double* rgb64f, uint32_t* raycount2, void* stream);
+
+// rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after
+// the context's streams have drained).
+void sdma_destroy(rt_ctx* c);

@@ -153,7 +153,7 @@ __device__ __forceinline__ d3 ld3(const double* p) { return mk(p[0], p[1], p[2])
 
 // ------------------------------------------------------------------------------------------------
 // Exact fast paths for |v| and v / |v|.
-// The compiler lowers IEEE sqrt and division on gfx950 to these sequences (lib/isa/rt_kernel.s):
+// The compiler lowers IEEE sqrt and division on gfx950 to these sequences (lib/isa/rt_rays.s):
 //   sqrt(x): x < 2^-767 is scaled by 2^256; y = rsq(x); g = x y; h = y / 2; r = fma(-h, g, 1/2);
 //            g = fma(g, r, g); d = fma(-g, g, x); h = fma(h, r, h); g = fma(d, h, g); d = fma(-g, g, x);
 //            g = fma(d, h, g); unscale; x in {+0, -0, +inf} returns x.

@@ -1,4 +1,5 @@
-// rt_internal.hpp — host-side helpers shared by rt_host.cpp and rt_kernel.hip (not part of the ABI).
+// rt_internal.hpp — host-side helpers shared by rt_host.cpp, rt_screen.cpp, rt_group.cpp and the device-side units (not part
+// of the ABI; the context itself: rt_ctx.hpp, for the device-side units alone).
 #pragma once
 
 #include <stdint.h>
@@ -60,7 +61,7 @@ int rt_unshuffle_dev_ex(const void* gathered, const void* rank0_slab, void* imag
 int rt_unpack_dev_ex(const void* gathered, const void* rank0_slab, void* image, int W, int H, int src_format,
                      int dst_format, int band_height, int n_ranks, int slab_rows, void* stream);
 
-// rt_render_screen's chunk traced in one launch (rt_kernel.hip): ray k of the chunk, window entry j of pixel q
+// rt_render_screen's chunk traced in one launch (rt_rays.hip): ray k of the chunk, window entry j of pixel q
 // (pix[q].off <= k < pix[q].off + pix[q].len), is Line(cam, pix[q].sp + 0.5 * jit[pix[q].base + j])
 // (ray.set(camera, screenPt + .5 * randomUnit()), MSA:1296); first[b] = the pixel of ray b * kScreenBlock.
 // All pointers device-visible; n rays, m pixels.

@@ -210,3 +210,9 @@ constexpr int kScreenMaxWindow = 128;          // len <= this (the window half-w
 #define RT_SCREEN_WG 256
 #endif
 constexpr int kScreenBlock = RT_SCREEN_WG;     // rays per first-pixel table entry (the screen trace launch's workgroup)
+
+// Work-items per workgroup of the utility kernels and the 256-thread render variants (here, not in rt_render.hpp: the
+// units without the render kernels size their launches by it too).
+namespace rtk {
+constexpr int kThreads = 256;
+}

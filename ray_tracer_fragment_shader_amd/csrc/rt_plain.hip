@@ -1,0 +1,797 @@
+// rt_plain.hip — the plain render path behind rt_render_dev, rt_render_dev_packed and rt_render_ss_dev: one
+// render_dev_impl call in eight steps, and the view cache those steps own (rt_ctx::View, rt_ctx::Sync).
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "rt_ctx.hpp"
+#include "rt_render.hpp"
+
+using namespace rt;
+
+namespace {
+
+using namespace rtk;
+
+#if RT_WAVE_TRACE
+uint64_t* g_wtrace = nullptr;                  // diagnostic build only (tools/wave_trace.py)
+#endif
+
+// Tile-row dispatch order from a calibration render's per-row costs: rows by decreasing cost (ties by
+// index), so the longest rows are dispatched first and the cheap ones fill the tail (longest-processing-
+// time-first list scheduling).  One workgroup, bitonic sort of (~cost, row) keys in LDS; n <= kOrderMax.
+__global__ __launch_bounds__(1024) void rt_order_kernel(const uint32_t* __restrict__ cost, int n,
+                                                        int32_t* __restrict__ order) {
+    __shared__ uint64_t key[kOrderMax];
+    int m = 1;
+    while (m < n) m <<= 1;
+    for (int k = threadIdx.x; k < m; k += blockDim.x)
+        key[k] = k < n ? ((uint64_t)(~cost[k]) << 32) | (uint32_t)k : ~0ull;
+    __syncthreads();
+    for (int size = 2; size <= m; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int k = threadIdx.x; k < m; k += blockDim.x) {
+                const int o = k ^ stride;
+                if (o > k) {
+                    const bool up = (k & size) == 0;
+                    const uint64_t a = key[k], b = key[o];
+                    if ((a > b) == up) { key[k] = b; key[o] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int k = threadIdx.x; k < n; k += blockDim.x) order[k] = (int32_t)(key[k] & 0xffffffffu);
+}
+
+// Per tile row, the sum of its tiles' wave times (the row order's cost); one workgroup per row.
+__global__ __launch_bounds__(256) void rt_rowsum_kernel(const uint32_t* __restrict__ tile_cost, int tiles_x,
+                                                        uint32_t* __restrict__ row_cost) {
+    __shared__ uint32_t part[256];
+    uint32_t acc = 0;
+    for (int x = threadIdx.x; x < tiles_x; x += 256) acc += tile_cost[(size_t)blockIdx.x * tiles_x + x];
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) row_cost[blockIdx.x] = part[0];
+}
+
+__global__ __launch_bounds__(256) void rt_iota_kernel(int32_t* __restrict__ v, int n) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n) v[k] = k;
+}
+
+// The dispatch table of a calibrated view: position L (linear workgroup id, L = gy * tiles_x + bx) traces tile
+// by_pos[L] (tile order: tile indices by decreasing calibrated time) or, row order (by_pos = nullptr), tile column
+// tile_col(bx, gy) of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
+// `cone` (else 0), and their sky verdicts (cone[n + tile], n the tile count).  Stored at cone_slot(L): grouped by the
+// XCD workgroup L runs on.
+__global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict__ row_order,
+                                                      const int32_t* __restrict__ by_pos,
+                                                      const uint64_t* __restrict__ cone, int tiles_x, int tiles_y,
+                                                      DispRec* __restrict__ disp) {
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
+    if (k >= n) return;
+    int tx, ty;
+    if (by_pos) {
+        const int t = by_pos[k];
+        ty = t / tiles_x;
+        tx = t - ty * tiles_x;
+    } else {
+        const int gy = (int)(k / tiles_x), bx = (int)(k - (size_t)gy * tiles_x);
+        ty = row_order[gy];
+        tx = tile_col(bx, gy, tiles_x);
+    }
+    const uint64_t m = cone ? cone[(size_t)ty * tiles_x + tx] : 0;
+    DispRec r;
+    r.cone_lo = (uint32_t)m;
+    r.cone_hi = (uint32_t)(m >> 32);
+    r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
+    r.sky = cone ? (uint32_t)cone[n + (size_t)ty * tiles_x + tx] : 0;   // (the verdicts follow the n masks)
+    disp[cone_slot(k, n)] = r;
+}
+
+// The run-compacted dispatch table of a calibrated view in tile-row order (include/rt_diag.h; the plain table stays
+// beside it for every render that may not read runs).  rt_run_plan_kernel, one workgroup per dispatch row gy: the
+// row's verdicts (the calibration render's) in LDS, one byte per tile (tiles_x bytes of dynamic LDS), then the plan
+// (rt_cone.hpp sky_run_at) tile by tile, as a code per plain position — 0 covered by the run that starts to its left,
+// 1 a tracing tile, 1 + len the head of a run of len sky tiles.  An inclusive prefix sum of (code != 0) then numbers
+// the heads (hipcub, render_build_dispatch), and rt_run_disp_kernel writes each head's record at cone_slot(its number,
+// the heads' count).
+__global__ __launch_bounds__(256) void rt_run_plan_kernel(const int32_t* __restrict__ row_order,
+                                                          const uint64_t* __restrict__ sky, int tiles_x, int run_max,
+                                                          uint32_t* __restrict__ code) {
+    extern __shared__ uint8_t row_sky[];
+    const int gy = (int)blockIdx.x;
+    const uint64_t* v = sky + (size_t)row_order[gy] * tiles_x;
+    for (int x = threadIdx.x; x < tiles_x; x += 256) row_sky[x] = v[tile_col(x, gy, tiles_x)] != 0;
+    __syncthreads();
+    for (int x = threadIdx.x; x < tiles_x; x += 256)
+        code[(size_t)gy * tiles_x + x] =
+            (uint32_t)(1 + sky_run_at(tiles_x, run_max, x, [&](int q) { return row_sky[q] != 0; }));
+}
+
+struct RunHead {
+    __host__ __device__ uint32_t operator()(uint32_t code) const { return code != 0 ? 1u : 0u; }
+};
+
+__global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restrict__ row_order,
+                                                          const uint64_t* __restrict__ cone,
+                                                          const uint32_t* __restrict__ code,
+                                                          const uint32_t* __restrict__ number, int tiles_x, int tiles_y,
+                                                          DispRec* __restrict__ disp) {
+    const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
+    if (k >= n || code[k] == 0) return;
+    const int gy = (int)(k / tiles_x), bx = (int)(k - (size_t)gy * tiles_x);
+    const int ty = row_order[gy], tx = tile_col(bx, gy, tiles_x);
+    const uint64_t m = cone[(size_t)ty * tiles_x + tx];
+    DispRec r;
+    r.cone_lo = (uint32_t)m;
+    r.cone_hi = (uint32_t)(m >> 32);
+    r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
+    r.sky = code[k] - 1u;
+    disp[cone_slot(number[k] - 1u, number[n - 1])] = r;   // (number[n - 1]: the heads' count, at most n)
+}
+
+// Per-eye primary-ray sphere data (run by rt_render_dev when the camera eye changes): deltaP = C - eye
+// and dot(deltaP, deltaP) exactly as Shape::intersection computes them for p0 = camera (:740, :750), and
+// the FP32 filter image f32(deltaP), c0 = (r2 - dd) + K (S0^2 + r2) rounded up, S0 = max|deltaP_i|.
+// Filter error < 35 eps32 S0^2 + 2 eps32 r2 << K (S0^2 + r2), K = 256 eps32.  Padding spheres have
+// r2 = -inf, hence c0 = -inf: always rejected.
+__global__ __launch_bounds__(kThreads) void rt_prepare_kernel(DevScene* __restrict__ g, double ex, double ey,
+                                                              double ez) {
+    const int np = g->n_padded, ns = g->n_stride;
+    DevSphere* sph = reinterpret_cast<DevSphere*>(g + 1);
+    DevSpherePrim* prim = reinterpret_cast<DevSpherePrim*>(sph + ns);
+    DevSphereF* sphf = reinterpret_cast<DevSphereF*>(prim + ns);
+    DevSpherePrimF* primf = reinterpret_cast<DevSpherePrimF*>(sphf + ns);
+    DevSphereCone* cone = reinterpret_cast<DevSphereCone*>(primf + ns);
+    const d3 eye = mk(ex, ey, ez);
+    const int k = blockIdx.x * kThreads + threadIdx.x;
+    if (k == 0) {
+        g->eye[0] = ex; g->eye[1] = ey; g->eye[2] = ez;
+        // board plane numerator for p0 = eye, as board_hit computes it (:657)
+        g->board_num = dot(ld3(g->tri[0].n), sub(ld3(g->tri[0].v0), eye));
+        g->hits_ok = hits_ok_from(g, eye);      // hit points of rays from this eye skip the cull (hits_inside)
+        // A primary ray that hits an object passes g_scene's cull when every object lies within R - 1 of bc
+        // (hits_inside) and the eye is at least R + 1 away: the line then passes within R - 1 of bc, so its exact
+        // disc >= R^2 - (R - 1)^2 = 2R - 1, and the eye being outside the bound puts the entry root at
+        // s >= D - R >= 1 (the hit lies ahead of the eye, past the entry); the FP64 rounding of disc and s is
+        // ~2^-49 (D^2 + R^2) and ~2^-50 (D + R), far below 2R - 1 and 1 - eps for D <= 2^20 (R + 1).  (s >= 1 clears the
+        // reference's |s| < eps cull only for eps < 1: required explicitly, as hits_inside does through inner2.)
+        const double bx = eye.x - g->bc[0], by = eye.y - g->bc[1], bz = eye.z - g->bc[2];
+        const double D2 = bx * bx + by * by + bz * bz, R1 = sqrt(g->br2) + 1.0;
+        g->prim_bound_ok = (g->bound_on != 0) & (g->hits_inside != 0) & (g->eps < 0.5) &
+                           (D2 >= R1 * R1 * (1.0 + 0x1p-30)) & (D2 <= R1 * R1 * 0x1p40);
+    }
+    // the board's four edges seen from this eye (the wave-level board miss of primary_cone_mask)
+    if (k < 4) g->edge[k] = board_edge_record(g, ex, ey, ez, k);
+    if (k >= np) return;
+    d3 dP = sub(ld3(sph[k].c), eye);
+    double dd = dot(dP, dP);
+    DevSpherePrim pp;
+    pp.dP[0] = dP.x; pp.dP[1] = dP.y; pp.dP[2] = dP.z;
+    pp.dd = dd;
+    prim[k] = pp;
+    double s0 = fmax(fabs(dP.x), fmax(fabs(dP.y), fabs(dP.z)));
+    double r2 = sph[k].r2;
+    double c0 = (r2 - dd) + (double)kFilterK * (s0 * s0 + r2);
+    DevSpherePrimF f;
+    f.dx = (float)dP.x; f.dy = (float)dP.y; f.dz = (float)dP.z;
+    f.c0 = __double2float_ru(c0);
+    primf[k] = f;
+    // Cone of directions from the eye that can hit sphere k (primary_cone_mask)
+    cone[k] = sphere_cone_record(dP.x, dP.y, dP.z, dd, r2);
+}
+
+}  // namespace
+
+#if RT_WAVE_TRACE
+extern "C" int rt_debug_wave_trace(void* dev_buf) {
+    g_wtrace = reinterpret_cast<uint64_t*>(dev_buf);
+    return RT_OK;
+}
+#endif
+
+// ---- the view cache (rt_ctx::View): only the functions from here to render_record_view write it ------------------------
+// The calibrated view is no more: its order — every cached mask is read under order_valid only — and its run table.
+// Both branches of render_plan_view that start a calibration come here; render_build_dispatch makes the next view valid.
+static void view_invalidate(rt_ctx::View& v) {
+    v.order_valid = false;
+    v.run_valid = v.run_pending = false;
+}
+
+// The run table's buffers freed (all or none are held).
+static void view_free_run_bufs(rt_ctx::View& v) {
+    void* bufs[] = {v.d_disp_run, v.d_run_code, v.d_run_num, v.d_run_tmp};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    v.d_disp_run = nullptr;
+    v.d_run_code = v.d_run_num = nullptr;
+    v.d_run_tmp = nullptr;
+}
+
+// The per-tile view buffers (dispatch table, tile times, cone masks, sort buffers) of a context.
+void rt_free_view_bufs(rt_ctx* c) {
+    rt_ctx::View& v = c->view;
+    void* bufs[] = {v.d_disp, v.d_tile_cost, v.d_cone_tile, v.d_sort_keys, v.d_sort_in, v.d_sort_out, v.d_sort_tmp};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    view_free_run_bufs(v);
+    v.run_tmp_bytes = 0;
+    // (the run table's flags alone, not view_invalidate: the row order in d_tile_rows is not freed here, and the one
+    // caller with a view to lose, a calibrating render, has invalidated it in step 2)
+    v.run_valid = v.run_pending = false;
+    v.d_disp = nullptr;
+    v.d_tile_cost = v.d_sort_keys = nullptr;
+    v.d_cone_tile = nullptr;
+    v.d_sort_in = v.d_sort_out = nullptr;
+    v.d_sort_tmp = nullptr;
+    v.sort_tmp_bytes = 0;
+    v.cap = 0;
+}
+
+// ... grown to hold `tiles` tiles (the caller has drained the device: renders may read the old ones).  False (and no
+// buffers) when the device is out of memory: the view then keeps the identity order.
+static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
+    rt_ctx::View& v = c->view;
+    if (tiles <= v.cap) return true;
+    rt_free_view_bufs(c);
+    const size_t slots = cone_slots(tiles);
+    bool ok = hipMalloc(&v.d_disp, slots * sizeof(DispRec)) == hipSuccess &&
+              hipMalloc(&v.d_tile_cost, tiles * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc(&v.d_cone_tile, 2 * tiles * sizeof(uint64_t)) == hipSuccess &&   // masks, then sky verdicts
+              hipMalloc(&v.d_sort_keys, tiles * sizeof(uint32_t)) == hipSuccess &&
+              hipMalloc(&v.d_sort_in, tiles * sizeof(int32_t)) == hipSuccess &&
+              hipMalloc(&v.d_sort_out, tiles * sizeof(int32_t)) == hipSuccess;
+    if (ok) {
+        size_t tmp = 0;
+        ok = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, v.d_tile_cost, v.d_sort_keys, v.d_sort_in,
+                                                          v.d_sort_out, (int)tiles) == hipSuccess &&
+             hipMalloc(&v.d_sort_tmp, tmp) == hipSuccess;
+        v.sort_tmp_bytes = tmp;
+    }
+    if (!ok) {
+        (void)hipGetLastError();
+        rt_free_view_bufs(c);
+        return false;
+    }
+    // the run table's buffers (all or none: without them every render reads the plain table)
+    if (c->knobs.sky_run_max != 1) {
+        size_t tmp = 0;
+        const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.d_run_code, RunHead{});
+        const bool run_ok = hipMalloc(&v.d_disp_run, slots * sizeof(DispRec)) == hipSuccess &&
+                            hipMalloc(&v.d_run_code, tiles * sizeof(uint32_t)) == hipSuccess &&
+                            hipMalloc(&v.d_run_num, tiles * sizeof(uint32_t)) == hipSuccess &&
+                            hipcub::DeviceScan::InclusiveSum(nullptr, tmp, heads, v.d_run_num, (int)tiles) == hipSuccess &&
+                            hipMalloc(&v.d_run_tmp, std::max(tmp, (size_t)16)) == hipSuccess;
+        if (run_ok) {
+            v.run_tmp_bytes = tmp;
+        } else {
+            (void)hipGetLastError();
+            view_free_run_bufs(v);
+        }
+    }
+    v.cap = tiles;
+    return true;
+}
+
+static int render_params(const rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
+                         RenderParams* P) {
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!c->scene.set) return rt_fail(RT_EINVAL, "render: rt_set_scene has not been called");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31)) return rt_fail(RT_EINVAL, "render: bad image size");
+    if (depth < 0 || depth > RT_MAX_DEPTH) return rt_fail(RT_EINVAL, "render: depth out of range [0, 7]");
+    int nl = 0;
+    int rc = rt_local_rows(H, rows, &nl);
+    if (rc) return rc;
+    memset(P, 0, sizeof(*P));
+    double right[3], upp[3];
+    rt_camera_basis(cam, right, upp);
+    for (int q = 0; q < 3; ++q) {
+        P->eye[q] = cam->eye[q];
+        P->look[q] = cam->look_at[q];
+        P->right[q] = right[q];
+        P->upp[q] = upp[q];
+    }
+    P->pitch = cam->pitch;
+    P->bottom_x = cam->bottom_x;
+    P->bottom_y = cam->bottom_y;
+    P->width = W;
+    P->height = H;
+    P->local_rows = nl;
+    bool banded = rows && rows->n_ranks > 1;
+    P->band_height = banded ? rows->band_height : H;
+    P->n_ranks = banded ? rows->n_ranks : 1;
+    P->rank = banded ? rows->rank : 0;
+    P->frames = (rows && rows->frames > 1) ? rows->frames : 1;
+    P->frame_rows = nl / P->frames;
+    P->lds_bytes = c->scene.lds_bytes;
+    P->np = c->scene.n_padded;
+    P->ns = c->scene.n_stride;
+    P->nl = c->scene.n_lights;
+    P->wg_staging = c->knobs.wg_staging;
+#if RT_WAVE_TRACE
+    P->wtrace = g_wtrace;
+#endif
+    // FP32 camera for the per-wave cone culling, and the bound on its error (rt_cone.hpp)
+    const ConeCam C = cone_camera(P->look, P->right, P->upp, P->eye, P->pitch, P->bottom_x, P->bottom_y, W, H);
+    for (int q = 0; q < 3; ++q) {
+        P->look32[q] = C.look[q];
+        P->right32[q] = C.right[q];
+        P->upp32[q] = C.upp[q];
+        P->eye32[q] = C.eye[q];
+    }
+    P->pitch32 = C.pitch;
+    P->cone_slack = C.slack;
+    P->sky = c->knobs.sky_tiles ? 1 : 0;
+    return RT_OK;
+}
+
+// render_params' checks alone, and the rows of the frame this process renders (the host-frame calls).
+int render_local_rows(const rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
+                      int* local_rows) {
+    RenderParams P;
+    const int rc = render_params(c, cam, W, H, depth, rows, &P);
+    if (!rc) *local_rows = P.local_rows;
+    return rc;
+}
+
+static bool byte_format(int f) { return f == RT_PIXEL_RGBA8 || f == RT_PIXEL_RGB8 || f == RT_PIXEL_GRAY8; }
+
+// render_route() (rt_render.hpp) for this context's scene kind and A/B knobs.
+static RenderRoute ctx_route(const rt_ctx* c, int depth, int mode, bool level_mask) {
+    const rt_ctx::Scene& s = c->scene;
+    const rt_ctx::Knobs& k = c->knobs;
+    return render_route(RouteScene{s.tree, s.transparent, s.n_padded, s.n_stride, s.achromatic, s.lds_bytes},
+                        RouteKnobs{k.use_lds != 0, k.wg_staging != 0, k.min_waves, k.achro_off}, depth, mode, level_mask);
+}
+
+// One render_dev_impl call: what it was asked for, and what its steps (below, in the order they run) decide.
+struct RenderJob {
+    const rt_camera* cam;
+    int W, H, depth;
+    const rt_rows* rows;
+    void *pf, *p8;                                      // the outputs, each nullable
+    double* o64;
+    uint32_t* orc;
+    hipStream_t st;
+    int ss_log2;
+    RenderParams P;                                     // step 1
+    int mode;                                           // kModePlain / kModePacked / kModeSS
+    RenderRoute route;                                  // the kernel instance, its LDS bytes and tile width
+    int tiles_x, tiles_y;                               // step 2
+    size_t tiles;
+    bool capturing, cull_kernel;                        // (cull_kernel: the render kernel itself writes the level masks)
+    int lm_stride;                                      // level-mask slots per tile (0: none)
+    rt_ctx::ViewKey key;
+    bool calibrate, cone_calib, lm_calib;               // this render times its tiles / records cone / level masks
+    bool prepare;                                       // ... writes the per-eye scene records first
+    bool runs;                                          // the launch reads the run-compacted table (c->view.run_*)
+};
+
+// The grid of a launch over n dispatch positions of a table of its own width: w positions per grid row, at most kGridY
+// rows, so that the rows x w - n padding positions (each traces a clamped tile and stores nothing) number at most 7
+// wherever such a width exists in the range searched (w = 8 always is one up to 8 kGridY positions), else the fewest.
+static void run_grid(uint32_t n, int* w, int* rows) {
+    if (n <= 1024) {
+        *w = (int)n;
+        *rows = 1;
+        return;
+    }
+    const uint32_t lo = std::max(8u, (n + kGridY - 1) / kGridY);
+    uint32_t best = std::max(lo, 1024u), best_pad = ~0u;
+    for (uint32_t k = std::max(lo, 1024u); k >= lo; --k) {
+        const uint32_t pad = (k - n % k) % k;
+        if (pad < best_pad) best = k, best_pad = pad;
+        if (pad <= 7) break;
+    }
+    *w = (int)best;
+    *rows = (int)((n + best - 1) / best);
+}
+
+// Step 1: the kernel parameters, the pixel formats and the output mode; the kernel instance of the frame.
+static int render_job_params(rt_ctx* c, int fmt_f, int fmt_8, RenderJob& J) {
+    RenderParams& P = J.P;
+    int rc = render_params(c, J.cam, J.W, J.H, J.depth, J.rows, &P);
+    if (rc) return rc;
+    const bool ss = J.ss_log2 >= 0;
+    if (ss) {
+        P.ss_log2 = J.ss_log2;
+        P.wg_staging = 0;                           // one-wave direct-store instances only
+    }
+    if ((J.pf && !float_format(fmt_f)) || (J.p8 && !byte_format(fmt_8)))
+        return rt_fail(RT_EINVAL, "render: bad pixel format for the float / byte image");
+    if (((J.pf && fmt_f == RT_PIXEL_GRAY32F) || (J.p8 && fmt_8 == RT_PIXEL_GRAY8)) && !c->scene.achromatic)
+        return rt_fail(RT_EINVAL, "render: GRAY pixel formats need an achromatic scene (rt_scene_achromatic)");
+    P.fmt_f = fmt_f == RT_PIXEL_GRAY32F ? kFmtF_GRAY : kFmtF_RGBA;
+    P.fmt_8 = fmt_8 == RT_PIXEL_GRAY8 ? kFmt8_GRAY : fmt_8 == RT_PIXEL_RGB8 ? kFmt8_RGB : kFmt8_RGBA;
+    const bool packed = (J.pf && P.fmt_f != kFmtF_RGBA) || (J.p8 && P.fmt_8 != kFmt8_RGBA);
+    if (packed) P.wg_staging = 0;                   // the LDS-staged stores (A/B variant) write RGBA only
+    J.mode = ss ? kModeSS : packed ? kModePacked : kModePlain;
+    // One-wave workgroups (8 x 8 tiles) by default: measured faster than 256-thread workgroups (32 x 8
+    // tiles) at every config (c2 -1%, c3 -3%, c5 -12%: a finished wave's slot is refilled without
+    // waiting for three siblings).  The A/B instances that share a workgroup-wide LDS copy (scene in LDS,
+    // staged row stores) keep 256 threads; packed formats and supersampling have one-wave instances only.
+    J.route = ctx_route(c, J.depth, J.mode, false);
+    return RT_OK;
+}
+
+// r06: a moving camera renders in identity order (RT_MOVING_ORDER=1: the last calibrated order, re-timed every
+// RT_RECALIBRATE-th render, 8 by default then — the r03-r05 policy).  tools/moving_probe.py, c2 orbit, 3 frames in
+// flight: identity 22.8 us per frame, the static view's order kept 24.2, re-timed every 8th render 26.9 (the
+// re-timing's order kernels stall the context's stream; the static view's row costs are not the orbit's).
+//
+// Step 2: the tiles, and which render of its view this is — a later one in calibrated order, one of a moving camera,
+// the calibration render, or the first (identity order).
+static int render_plan_view(rt_ctx* c, RenderJob& J) {
+    rt_ctx::View& v = c->view;
+    RenderParams& P = J.P;
+    const bool big = J.route.key.WG == kThreads;    // 32 x 8 tiles, four waves each
+    J.tiles_x = (J.W + J.route.tile_w - 1) / J.route.tile_w;
+    J.tiles_y = (P.local_rows + kTileH - 1) / kTileH;
+    J.tiles = (size_t)J.tiles_x * J.tiles_y;
+    P.tile_rows_n = J.tiles_y;
+    P.tiles_x = J.tiles_x;
+    // A render captured into a hipGraph must be self-contained: it always prepares its eye's data and uses
+    // the identity tile-row order (the context's order buffer belongs to whatever view it last calibrated).
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    RT_HIP(hipStreamIsCapturing(J.st, &cap));
+    J.capturing = cap != hipStreamCaptureStatusNone;
+    if (J.capturing) c->eye.ever_captured = true;
+    J.calibrate = J.cone_calib = J.lm_calib = J.runs = false;
+    // level masks per tile (opaque scenes, one-wave tiles): B ray masks + (B + 1) nl shadow masks.  The culling
+    // kernels compute them in their calibration render; for the fast kernels' scenes (< kConeMin spheres) a culling
+    // kernel writes them in a launch of its own right after the calibration render (no image outputs), and later
+    // renders skip the filter batches they rule out
+    const bool opaque_tiles = !c->scene.tree && !c->scene.transparent && !big && RT_WG_FAST == 64;
+    J.cull_kernel = c->scene.n_padded >= kConeMin && opaque_tiles;
+    J.lm_stride = opaque_tiles && c->knobs.level_masks && c->knobs.cone_cache ? J.depth + (J.depth + 1) * c->scene.n_lights : 0;
+    if (J.lm_stride > kLevelMaskSlotsMax) J.lm_stride = 0;
+    J.key = rt_ctx::ViewKey{};
+    // (dispatch records pack the tile as ty << 16 | tx)
+    if (!J.capturing && c->knobs.order_mode == 0 && J.tiles_y <= v.n_tile_rows && J.tiles_x < 65536 && J.tiles_y < 65536) {
+        // Key of the frame's work: camera, size, outputs, row plan, depth and scene generation.
+        unsigned char* kp = J.key.data();               // fixed size: no host allocation per render
+        memcpy(kp, J.cam, sizeof(rt_camera)); kp += sizeof(rt_camera);
+        // which outputs are written (and in which format) changes the rows' relative cost (an RGB64F parity
+        // render writes 24 B per pixel): each output set gets its own calibration
+        // (and a supersampled render its own: it shares the camera and size of a plain render of its sample grid,
+        // not its stores)
+        const int outs = (J.pf ? 1 : 0) | (J.p8 ? 2 : 0) | (J.o64 ? 4 : 0) | (J.orc ? 8 : 0) | (P.fmt_f << 4) |
+                         (P.fmt_8 << 6) | ((J.mode == kModeSS ? J.ss_log2 + 1 : 0) << 8);
+        const int ints[6] = {J.W, J.H, J.depth, J.tiles_x, J.tiles_y, outs};
+        memcpy(kp, ints, sizeof(ints)); kp += sizeof(ints);
+        if (J.rows) memcpy(kp, J.rows, sizeof(rt_rows));
+        kp += sizeof(rt_rows);
+        memcpy(kp, &c->scene.gen, sizeof(uint64_t));
+        constexpr size_t kCam = sizeof(rt_camera);
+        const bool same_shape = v.order_valid &&
+                                memcmp(J.key.data() + kCam, v.order_key.data() + kCam, J.key.size() - kCam) == 0;
+        if (v.order_valid && J.key == v.order_key) {
+            P.disp = v.d_disp;
+            // (the cached masks hold one mask per one-wave 8 x 8 tile: the 256-thread A/B instances never read them)
+            P.cone_use = v.cone_valid && !big ? 1 : 0;
+            // the run-compacted table of this view, once its position count has arrived (a wait that has, as a rule,
+            // long passed: the copy was queued behind the calibration's table kernels)
+            if (v.run_pending) {
+                v.run_pending = false;
+                if (hipEventSynchronize(v.run_ev) == hipSuccess) {
+                    v.run_n = *v.h_run_n;
+                    v.run_valid = v.run_n > 0 && v.run_n < J.tiles;   // (no sky tile: the plain table)
+                    if (v.run_valid) run_grid(v.run_n, &v.run_w, &v.run_rows);
+                } else {
+                    (void)hipGetLastError();
+                }
+            }
+            J.runs = v.run_valid && P.cone_use && P.sky;
+            if (J.runs) P.disp = v.d_disp_run;
+            v.last_positions = J.runs ? (int)v.run_n : (int)J.tiles;
+            v.last_tiles = (int)J.tiles;
+            v.last_run_max = J.runs ? v.run_built_max : 1;
+            if (v.lmask_valid && J.lm_stride > 0 && v.lmask_stride == J.lm_stride) {   // this view's level masks
+                P.lmask_in = v.d_lmask;
+                P.lmask_stride = J.lm_stride;
+            }
+        } else if (same_shape && c->knobs.moving_order) {
+            P.disp = v.d_disp;                         // another camera: the last calibrated order, its own masks
+            if (c->knobs.recalibrate > 0 && ++v.stale >= c->knobs.recalibrate) {   // ... re-timed every recalibrate-th render
+                J.calibrate = true;
+                view_invalidate(v);
+            }
+        } else if (v.seen_valid && J.key == v.seen_key) {   // (by default a moving camera's views come here: the
+                                                              // first render of a view in identity order, its second
+                                                              // the calibration — a camera that stops is calibrated)
+            J.calibrate = true;                         // calibration render (identity order)
+            view_invalidate(v);                         // rt_disp_kernel rewrites d_disp below, and d_disp_run
+            // the calibration records one mask per tile from lane 0 of its wave: one-wave workgroups only
+            J.cone_calib = c->knobs.cone_cache && c->scene.n_padded >= kPrimaryConeMin && !c->scene.tree &&
+                           !c->scene.transparent && !big && RT_WG_FAST == 64;
+            J.lm_calib = J.cone_calib && J.lm_stride > 0;
+        } else {
+            v.seen_key = J.key;                        // first render of this view: identity order
+            v.seen_valid = true;
+        }
+    }
+    J.prepare = J.capturing || c->eye.ever_captured || !c->eye.valid || memcmp(c->eye.pos, J.cam->eye, sizeof(c->eye.pos)) != 0;
+    return RT_OK;
+}
+
+// Step 3: order this render against the renders queued on other streams (a captured render carries its own prepare
+// launch and touches no view state).
+static int render_order_streams(rt_ctx* c, const RenderJob& J) {
+    if (J.capturing) return RT_OK;
+    // read-after-write / write-after-write: the last write of the view state was queued on another stream
+    if (c->sync.view_rec && c->sync.view_st != J.st) RT_HIP(hipStreamWaitEvent(J.st, c->sync.view_ev, 0));
+    if (J.prepare || J.calibrate) {
+        // write-after-read: renders queued on other streams may still read what this render rewrites (or frees)
+        if ((c->sync.readers && (c->sync.readers_multi || c->sync.reader_st != J.st)) ||
+            (J.calibrate && J.tiles > c->view.cap) ||
+            (J.lm_calib && J.tiles * (size_t)J.lm_stride > c->view.lmask_cap))
+            RT_HIP(hipDeviceSynchronize());
+        c->sync.readers = c->sync.readers_multi = false;      // same-stream renders are ordered before the rewrite
+    }
+    if (!c->sync.readers) {                              // this render reads the view state on st
+        c->sync.readers = true;
+        c->sync.reader_st = J.st;
+    } else if (c->sync.reader_st != J.st) {
+        c->sync.readers_multi = true;
+    }
+    return RT_OK;
+}
+
+// Step 4 (calibration renders): the buffers the render writes every tile's wave time and, a static view's, its cone
+// and level masks to.  They grow here: step 3 drained the device.
+static void render_grow_calibration(rt_ctx* c, RenderJob& J) {
+    rt_ctx::View& v = c->view;
+    RenderParams& P = J.P;
+    // (the masks' flags fall here, not in step 2's view_invalidate: step 3 may fail in between, and nothing reads them
+    // while order_valid is false)
+    v.cone_valid = false;
+    v.lmask_valid = false;
+    if (!rt_grow_view_bufs(c, J.tiles)) {           // out of memory: identity order, masks in the kernel
+        J.calibrate = J.cone_calib = J.lm_calib = false;
+        P.disp = nullptr;
+        P.cone_use = 0;
+    } else {
+        P.tile_cost = v.d_tile_cost;
+        if (J.cone_calib) P.cone_out = v.d_cone_tile;
+    }
+    if (J.lm_calib && J.tiles * (size_t)J.lm_stride > v.lmask_cap) {
+        if (v.d_lmask) (void)hipFree(v.d_lmask);
+        v.d_lmask = nullptr;
+        v.lmask_cap = 0;
+        if (hipMalloc(&v.d_lmask, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t)) == hipSuccess)
+            v.lmask_cap = J.tiles * (size_t)J.lm_stride;
+        else
+            (void)hipGetLastError();                // out of memory: the masks stay in the kernel
+    }
+    if (J.lm_calib && v.d_lmask) {
+        if (J.cull_kernel) {                        // (fast scenes: the level-mask launch of step 6 writes them)
+            P.lmask_out = v.d_lmask;
+            P.lmask_stride = J.lm_stride;
+        }
+    } else {
+        J.lm_calib = false;
+    }
+}
+
+// Step 5: the primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
+// that carry their own prepare launch exist).
+static int render_prepare_eye(rt_ctx* c, const RenderJob& J) {
+    c->eye.valid = false;
+    dim3 pg((unsigned)((std::max(c->scene.n_padded, 1) + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(rt_prepare_kernel, pg, dim3(kThreads), 0, J.st, c->scene.d_scene, J.cam->eye[0], J.cam->eye[1],
+                       J.cam->eye[2]);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_prepare_kernel: ") + hipGetErrorString(e));
+    memcpy(c->eye.pos, J.cam->eye, sizeof(c->eye.pos));
+    c->eye.valid = true;
+    return RT_OK;
+}
+
+// Step 6: the render, and behind a fast scene's calibration render the launch that writes its level masks.
+static int render_launch(rt_ctx* c, const RenderJob& J) {
+    RenderLaunch L;
+    L.key = J.route.key;
+    L.grid = dim3((unsigned)J.tiles_x, (unsigned)std::min(J.tiles_y, kGridY), (unsigned)((J.tiles_y + kGridY - 1) / kGridY));
+    L.disp_w = J.tiles_x;
+    L.disp_n = J.tiles_y * J.tiles_x;
+    if (J.runs) {                                   // one position per tracing tile and per run of sky tiles
+        L.grid = dim3((unsigned)c->view.run_w, (unsigned)c->view.run_rows, 1);
+        L.disp_w = c->view.run_w;
+        L.disp_n = (int32_t)c->view.run_n;
+    }
+    L.lds = (size_t)J.route.lds;
+    L.stream = J.st;
+    L.scene = c->scene.d_scene;
+    L.P = J.P;
+    L.o32 = J.pf;
+    L.o8 = J.p8;
+    L.o64 = J.o64;
+    L.orc = J.orc;
+    hipError_t e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
+    if (J.lm_calib && !J.cull_kernel) {
+        // a fast kernel's scene: the level masks of the view from a culling kernel that stores nothing else (identity
+        // order, its own primary cone masks, no image) — stream-ordered before the renders that read them
+        const RenderRoute mask = ctx_route(c, J.depth, J.mode, true);
+        RenderLaunch M = L;
+        M.key = mask.key;
+        M.lds = (size_t)mask.lds;
+        M.P.lmask_out = c->view.d_lmask;
+        M.P.lmask_in = nullptr;
+        M.P.lmask_stride = J.lm_stride;
+        M.P.disp = nullptr;
+        M.P.cone_use = 0;
+        M.P.cone_out = nullptr;
+        M.P.tile_cost = nullptr;
+        M.o32 = M.o8 = nullptr;
+        M.o64 = nullptr;
+        M.orc = nullptr;
+        e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(M); });
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("level-mask launch: ") + hipGetErrorString(e));
+    }
+    return RT_OK;
+}
+
+// Step 7 (calibration renders): the dispatch table of this view, stream-ordered after the render that wrote the tile
+// times; only then does the context call the view calibrated.
+static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
+    rt_ctx::View& v = c->view;
+    const int tiles = (int)J.tiles, tiles_x = J.tiles_x, tiles_y = J.tiles_y;
+    const hipStream_t st = J.st;
+    hipError_t e;
+    const dim3 tg((unsigned)((J.tiles + 255) / 256));
+    const uint64_t* cones = J.cone_calib ? v.d_cone_tile : nullptr;
+    if (c->knobs.order_policy == 1) {                     // tiles longest first
+        hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, v.d_sort_in, (int)tiles);
+        size_t tmp = v.sort_tmp_bytes;
+        e = hipcub::DeviceRadixSort::SortPairsDescending(v.d_sort_tmp, tmp, v.d_tile_cost, v.d_sort_keys,
+                                                         v.d_sort_in, v.d_sort_out, (int)tiles, 0, 32, st);
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, tiles_x, tiles_y,
+                           v.d_disp);
+    } else {                                        // tile rows longest first
+        hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, v.d_tile_cost, tiles_x,
+                           v.d_row_cost);
+        hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, v.d_row_cost, tiles_y, v.d_tile_rows);
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, tiles_x, tiles_y,
+                           v.d_disp);
+        // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
+        // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
+        // plan runs along dispatch columns and the kernel stores image columns tx .. tx + r - 1: the same thing only
+        // while tile_col() is the identity, so an RT_XCD_SWIZZLE build (columns rotated per row) builds no run table.
+        const int run_max = c->knobs.sky_run_max == 0 ? 65535 : c->knobs.sky_run_max;
+        if (!RT_XCD_SWIZZLE && J.cone_calib && c->knobs.sky_tiles && run_max > 1 && v.d_disp_run && J.mode != kModeSS) {
+            const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.d_run_code, RunHead{});
+            size_t tmp = v.run_tmp_bytes;
+            hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, v.d_tile_rows,
+                               v.d_cone_tile + J.tiles, tiles_x, run_max, v.d_run_code);
+            if (hipcub::DeviceScan::InclusiveSum(v.d_run_tmp, tmp, heads, v.d_run_num, tiles, st) == hipSuccess) {
+                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, v.d_run_code,
+                                   v.d_run_num, tiles_x, tiles_y, v.d_disp_run);
+                if (hipMemcpyAsync(v.h_run_n, v.d_run_num + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                   st) == hipSuccess &&
+                    hipEventRecord(v.run_ev, st) == hipSuccess) {
+                    v.run_pending = true;
+                    v.run_built_max = run_max;
+                }
+            }
+            if (!v.run_pending) (void)hipGetLastError();   // (the view keeps the plain table)
+        }
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("dispatch table: ") + hipGetErrorString(e));
+    v.order_key = J.key;                           // only once the order kernel is queued
+    v.order_valid = true;
+    v.cone_valid = J.cone_calib;
+    v.sky_tiles_n = J.cone_calib ? J.tiles : 0;
+    v.lmask_valid = J.lm_calib;
+    v.lmask_stride = J.lm_calib ? J.lm_stride : 0;
+    v.stale = 0;
+    return RT_OK;
+}
+
+// Step 8: later renders on other streams wait for this render's writes of the view state.
+static int render_record_view(rt_ctx* c, const RenderJob& J) {
+    RT_HIP(hipEventRecord(c->sync.view_ev, J.st));
+    c->sync.view_st = J.st;
+    c->sync.view_rec = true;
+    return RT_OK;
+}
+
+// The device render behind rt_render_dev / rt_render_dev_packed: the float image (fmt_f) and the byte image
+// (fmt_8) in their formats, the FP64 colour and the ray counters, each nullable.
+// ss_log2 >= 0 (rt_render_ss_dev): cam, W, H and rows describe the SAMPLE grid of a supersampled render with
+// S = 1 << ss_log2 samples per axis; the outputs hold (W / S) x (local rows / S) pixels, RGBA formats, and the ray
+// counters are two words per pixel.  Everything per view (order, calibration, cached masks, capture rules) is the
+// sample grid's, unchanged; the kernels are the supersampled instances, which differ in their epilogue only.
+int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows, int fmt_f, void* pf,
+                    int fmt_8, void* p8, double* rgb64f, uint32_t* raycount, void* stream, int ss_log2) {
+    RenderJob J{cam, W, H, depth, rows, pf, p8, rgb64f, raycount, (hipStream_t)stream, ss_log2};
+    int rc = render_job_params(c, fmt_f, fmt_8, J);                             // 1
+    if (rc || J.P.local_rows == 0) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    if ((rc = render_plan_view(c, J))) return rc;                               // 2
+    if ((rc = render_order_streams(c, J))) return rc;                           // 3
+    if (J.calibrate) render_grow_calibration(c, J);                             // 4
+    if (J.prepare && (rc = render_prepare_eye(c, J))) return rc;                // 5
+    if ((rc = render_launch(c, J))) return rc;                                  // 6
+    if (J.calibrate && (rc = render_build_dispatch(c, J))) return rc;           // 7
+    if ((J.prepare || J.calibrate) && !J.capturing) return render_record_view(c, J);   // 8
+    return RT_OK;
+}
+
+extern "C" int rt_render_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
+                             float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount, void* stream) {
+    return render_dev_impl(c, cam, W, H, depth, rows, RT_PIXEL_RGBA32F, rgba32f, RT_PIXEL_RGBA8, rgba8, rgb64f,
+                           raycount, stream);
+}
+
+extern "C" int rt_render_dev_packed(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,
+                                    int float_format, void* float_pixels, int byte_format, void* byte_pixels,
+                                    void* stream) {
+    return render_dev_impl(c, cam, W, H, depth, rows, float_format, float_pixels, byte_format, byte_pixels, nullptr,
+                           nullptr, stream);
+}
+
+
+// The front of the sampled _dev entry points: the checks on samples (*s: its log2), context, camera and frame size;
+// then, with P given (the list-free kernels of rt_sampled.hpp, which index a whole frame of at most 2^31 pixels), the
+// sample-grid camera and the sample grid's RenderParams with ss_log2 set.
+int sample_grid_front(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int* s,
+                      RenderParams* P) {
+    *s = ss_log2_of(samples);
+    if (*s < 0) return rt_fail(RT_EINVAL, "render: samples must be 1, 2, 4 or 8");
+    if (!c) return rt_fail(RT_EINVAL, "render: null context");
+    if (!cam) return rt_fail(RT_EINVAL, "render: null camera");
+    if (W <= 0 || H <= 0 || (P && (long long)W * H > (1LL << 31)) || (long long)W * samples > INT32_MAX ||
+        (long long)H * samples > INT32_MAX)
+        return rt_fail(RT_EINVAL, "render: bad image size (width, height)");
+    if (!P) return RT_OK;
+    rt_camera cam_s;
+    int rc = rt_camera_supersample(cam, samples, &cam_s);   // (int32 overflow of the sample-grid camera)
+    if (rc) return rc;
+    rc = render_params(c, &cam_s, W * samples, H * samples, depth, nullptr, P);   // (at most 2^31 samples)
+    if (rc) return rc;
+    P->ss_log2 = *s;
+    return RT_OK;
+}
+
+// rt_render_ss_dev: the render of the sample grid (camera rt_camera_supersample, S W x S H, row bands S times as
+// high, so every S-row block of samples stays inside one band) through the supersampled kernel instances.
+extern "C" int rt_render_ss_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                const rt_rows* rows, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                uint32_t* raycount2, void* stream) {
+    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, nullptr);
+    if (rc) return rc;
+    int nl = 0;
+    rc = rt_local_rows(H, rows, &nl);                   // the caller's row plan, checked as given
+    if (rc) return rc;
+    if (rows && rows->frames > 1 && samples > 1)
+        return rt_fail(RT_EINVAL, "rt_render_ss_dev: frames > 1 is not supported with samples > 1");
+    // S = 1 without counters is rt_render_dev itself (the two-word counters need the supersampled instances)
+    if (s == 0 && !raycount2)
+        return render_dev_impl(c, cam, W, H, depth, rows, RT_PIXEL_RGBA32F, rgba32f, RT_PIXEL_RGBA8, rgba8, rgb64f,
+                               nullptr, stream);
+    rt_camera cam_s;
+    rc = rt_camera_supersample(cam, samples, &cam_s);
+    if (rc) return rc;
+    rt_rows rows_s{};
+    if (rows) {
+        rows_s = *rows;
+        if (rows->n_ranks > 1) {
+            if ((long long)rows->band_height * samples > INT32_MAX) return rt_fail(RT_EINVAL, "render: bad band height");
+            rows_s.band_height = rows->band_height * samples;
+        }
+    }
+    return render_dev_impl(c, &cam_s, W * samples, H * samples, depth, rows ? &rows_s : nullptr, RT_PIXEL_RGBA32F,
+                           rgba32f, RT_PIXEL_RGBA8, rgba8, rgb64f, raycount2, stream, s);
+}

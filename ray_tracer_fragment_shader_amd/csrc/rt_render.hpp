@@ -1,7 +1,8 @@
-// rt_render.hpp — the per-pixel render kernel and the ray-list kernel (templates), shared by rt_kernel.hip
-// (the C ABI) and the per-depth instance files rt_render_b<B>.hip.  The bounce depth B is a template
-// parameter (the bounce loop is unrolled); each depth's instances live in their own translation unit so the
-// eight depths compile in parallel (one file with all of them took > 5 minutes of one core).
+// rt_render.hpp — the per-pixel render kernel and the ray-list kernel (templates), shared by the units of the C ABI
+// that launch them (rt_plain.hip, rt_rays.hip, rt_diag.hip; rt_ctx.hpp has the map) and the per-depth instance files
+// rt_render_b<B>.hip.  The bounce depth B is a template parameter (the bounce loop is unrolled); each depth's instances
+// live in their own translation unit so the eight depths compile in parallel (one file with all of them took > 5
+// minutes of one core).
 //
 //   rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE>  one work-item per pixel, FP64, iterative bounce
 //                             loop (rt_device.hpp).  Default: one-wave workgroups (WG = 64), each owning an
@@ -96,7 +97,6 @@ using namespace rt;
 
 constexpr int kTileW = 32;   // workgroup tile of the 256-thread variants: 32 columns ...
 constexpr int kTileH = 8;    // ... x 8 rows = 256 pixels
-constexpr int kThreads = 256;
 static_assert(kThreads == kSlotStride, "one LDS colour slot column per work-item");
 constexpr int kGridY = 32768;                  // grid.y per grid.z slice
 
@@ -141,7 +141,7 @@ __host__ __device__ __forceinline__ int tile_col(int bx, int gy, int tiles_x) {
 __host__ __device__ __forceinline__ size_t cone_slot(size_t L, size_t n) { return (L & 7) * ((n + 7) >> 3) + (L >> 3); }
 __host__ __device__ __forceinline__ size_t cone_slots(size_t n) { return ((n + 7) >> 3) << 3; }
 
-// One dispatch position of a calibrated view (rt_kernel.hip rt_disp_kernel): the tile its workgroup traces
+// One dispatch position of a calibrated view (rt_plain.hip rt_disp_kernel): the tile its workgroup traces
 // (ty << 16 | tx), that tile's primary cone mask and its sky verdict (0: trace; r >= 1: no primary ray of the r tiles
 // tx .. tx + r - 1 of that tile row hits anything — r = 1 in the plain table, up to the run maximum in the run-compacted
 // one, rt_run_disp_kernel; both valid when RenderParams::cone_use).  The table is indexed by cone_slot(position): one

@@ -1,0 +1,230 @@
+// rt_sampled.hip — the device entry points of the sampled renders of rt_sampled.hpp: adaptive supersampling
+// (base render, rt_classify_kernel, the refine launch) and the lens family's one launch.
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "rt_ctx.hpp"
+#include "rt_sampled.hpp"
+
+using namespace rt;
+
+namespace {
+
+using namespace rtk;
+
+// Adaptive supersampling, pass 2 (rt_render_adaptive_dev): the criterion on the W x H base frame and the work list.
+// Pixel k = j W + i is refined iff some in-frame 4-neighbour differs from it by more than T in some colour byte of
+// the base RGBA8 image (T = -1: any in-frame neighbour).  Sets refined[k] (when given) and appends the flagged
+// pixels to `list` behind *count (zeroed on the stream by the caller).  A workgroup of kClassifyThreads work-items
+// takes kClassifyPer runs of kClassifyThreads consecutive pixels; every wave ballots each of its runs and counts the
+// bits, the waves' counts meet in LDS, and ONE atomic add per workgroup reserves its stretch of the list: returning
+// atomics on one word complete at about 88 per us on this chip, and one per wave of 64 pixels (7500 of them in a
+// 1920 x 1080 c2 frame) made this pass 86 us long.  Each flagged lane stores at the workgroup's base + the flagged
+// pixels of earlier waves and runs + the flagged lanes below it.  The list's order depends on the workgroups'
+// arrival; no output does.
+constexpr int kClassifyThreads = 1024, kClassifyPer = 8;
+__global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uint32_t* __restrict__ base8, int W, int H,
+                                                                       int T, uint8_t* __restrict__ refined,
+                                                                       uint32_t* __restrict__ count,
+                                                                       uint32_t* __restrict__ list) {
+    __shared__ uint32_t wave_first[kClassifyThreads / 64];
+    __shared__ uint32_t block_first;
+    const size_t n = (size_t)W * (size_t)H;
+    const size_t k0 = (size_t)blockIdx.x * (kClassifyThreads * kClassifyPer) + threadIdx.x;
+    uint32_t flags = 0;                                     // bit r: this lane's pixel of run r is refined
+    // The loads of all runs first, without branches (a neighbour outside the frame, and a pixel past the frame's end,
+    // is replaced by an in-frame address and masked below): the 5 kClassifyPer loads of a lane are in flight together,
+    // where one dependent round trip per run made the pass latency-bound.
+    uint32_t px[kClassifyPer][5], edge[kClassifyPer];
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        const size_t k = k0 + (size_t)r * kClassifyThreads, kc = k < n ? k : n - 1;   // (n <= 2^31: kc fits 32 bits)
+        const uint32_t j = (uint32_t)kc / (uint32_t)W, i = (uint32_t)kc - j * (uint32_t)W;
+        const uint32_t l = i > 0, rr = i + 1 < (uint32_t)W, d = j > 0, u = j + 1 < (uint32_t)H;
+        edge[r] = k < n ? (l | (rr << 1) | (d << 2) | (u << 3)) : 0u;
+        px[r][0] = base8[kc];
+        px[r][1] = base8[kc - l];
+        px[r][2] = base8[kc + rr];
+        px[r][3] = base8[kc - (d ? (size_t)W : 0)];
+        px[r][4] = base8[kc + (u ? (size_t)W : 0)];
+    }
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        const size_t k = k0 + (size_t)r * kClassifyThreads;
+        bool flag = false;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            int worst = -1;
+            for (int c = 0; c < 24; c += 8) {
+                const int df = (int)((px[r][0] >> c) & 0xffu) - (int)((px[r][nb + 1] >> c) & 0xffu);
+                worst = max(worst, df < 0 ? -df : df);
+            }
+            flag |= ((edge[r] >> nb) & 1u) && worst > T;
+        }
+        if (k < n && refined) refined[k] = flag ? 1 : 0;
+        flags |= (flag ? 1u : 0u) << r;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t ballot[kClassifyPer];                          // every lane of the workgroup is here
+    uint32_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        ballot[r] = __ballot((flags >> r) & 1u);
+        mine += (uint32_t)__popcll(ballot[r]);
+    }
+    if (lane == 0) wave_first[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kClassifyThreads / 64; ++w) {
+            const uint32_t c = wave_first[w];
+            wave_first[w] = sum;
+            sum += c;
+        }
+        block_first = sum ? atomicAdd(count, sum) : 0u;
+    }
+    __syncthreads();
+    uint32_t at = block_first + wave_first[wave];
+#pragma unroll
+    for (int r = 0; r < kClassifyPer; ++r) {
+        if ((flags >> r) & 1u)
+            list[at + (uint32_t)__popcll(ballot[r] & ((1ull << lane) - 1ull))] = (uint32_t)(k0 + (size_t)r * kClassifyThreads);
+        at += (uint32_t)__popcll(ballot[r]);
+    }
+}
+
+}  // namespace
+
+// ---- adaptive supersampling (include/rt_api.h, ABI 9) -------------------------------------------------------------
+// Workgroups of the refine launch: a fixed grid of one-wave workgroups (the list's length is only known on the
+// device) that covers the device's wave slots a few times over; the grid-stride loop takes the rest.
+constexpr unsigned kRefineGrid = 8192;
+
+// Three passes on `stream`: the one-sample base render (rt_render_ss_dev with S = 1: rt_render_dev's instances, or
+// the two-word-counter ones when counters are asked for) straight into the caller's outputs, rt_classify_kernel on
+// its RGBA8 bytes, rt_refine_kernel over the work list.  No shortcut for any threshold.
+extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                      int threshold, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                      uint32_t* raycount2, uint8_t* refined, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (threshold < -1 || threshold > 255)
+        return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: threshold must lie in -1 .. 255");
+    SampledLaunch L{};                                      // P: the sample grid's, the refine kernel's ray set-up
+    int s, rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
+    const size_t npx = (size_t)W * (size_t)H;
+    const AdaptiveLayout lay = rt_adaptive_layout(npx);
+    if (!workspace || workspace_bytes < lay.bytes || (uintptr_t)workspace % 16 != 0)
+        return rt_fail(RT_EINVAL, "rt_render_adaptive_dev: null, misaligned or too small workspace "
+                                  "(rt_adaptive_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+    uint32_t* count = reinterpret_cast<uint32_t*>(ws);
+    uint32_t* list = reinterpret_cast<uint32_t*>(ws + lay.list);
+    uint8_t* base8 = rgba8 ? rgba8 : ws + lay.base8;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+    rc = rt_render_ss_dev(c, cam, W, H, depth, 1, nullptr, rgba32f, base8, rgb64f, raycount2, st);
+    if (rc) return rc;
+    constexpr size_t kClassifyBlock = (size_t)kClassifyThreads * kClassifyPer;
+    hipLaunchKernelGGL(rt_classify_kernel, dim3((unsigned)((npx + kClassifyBlock - 1) / kClassifyBlock)),
+                       dim3(kClassifyThreads), 0, st,
+                       reinterpret_cast<const uint32_t*>(base8), W, H, threshold, refined, count, list);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_classify_kernel: ") + hipGetErrorString(e));
+    // S = 1: a refined pixel's only sample is the base sample itself, already in place
+    if (s == 0 || (!rgba32f && !rgba8 && !rgb64f && !raycount2)) return RT_OK;
+    L.variant = trace_variant(c->scene.tree, c->scene.transparent);
+    const size_t per_wave = (size_t)64 >> (2 * s);
+    L.grid = (unsigned)std::min<size_t>((npx + per_wave - 1) / per_wave, kRefineGrid);
+    L.stream = st;
+    L.scene = c->scene.d_scene;
+    L.out_w = W;
+    L.count = count;
+    L.list = list;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    e = with_depth(depth, [&](auto B) { return launch_refine<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_refine_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// ---- the lens family: depth of field, soft shadows, motion blur (include/rt_api.h, ABI 10) -------------------------
+// rt_render_motion_dev with shutter 0 is rt_render_soft_dev, and that with light_size 0 is rt_render_dof_dev: one
+// kernel (rt_lens_kernel<.., AREA, MOTION>, rt_sampled.hpp) in three kinds behind the three pairs of entry points.
+
+// The arguments a kind reads, in the order aperture, light_size, shutter.
+int lens_arg_checks(LensKind kind, const char* who, double aperture, double light_size, double shutter) {
+    if (!(aperture >= 0.0) || !std::isfinite(aperture))
+        return rt_fail(RT_EINVAL, std::string(who) + ": aperture must be finite and >= 0");
+    if (kind >= kLensSoft && (!(light_size >= 0.0) || !std::isfinite(light_size)))
+        return rt_fail(RT_EINVAL, std::string(who) + ": light_size must be finite and >= 0");
+    if (kind >= kLensMotion && !(shutter >= 0.0 && shutter <= 1.0))
+        return rt_fail(RT_EINVAL, std::string(who) + ": shutter must be in [0, 1]");
+    return RT_OK;
+}
+
+// One launch of the kind's rt_lens_kernel on `stream`: S x S lens samples per pixel through the generic trace path;
+// soft: sample (a, b) lit by point (a, b) of every light's square panel; motion: sample (a, b) also at its own shutter
+// time.  The light shift and the displaced centres are formed in the kernel, from light_size and from the context's
+// motion record: the scene record is read, never written or re-uploaded.  Nothing per view: no rt_prepare_kernel, no
+// calibration, no dispatch table, and no field of the context is written, so the context's cone and level masks and
+// its tile order stay what the last rt_render_dev left.  No shortcut for shutter 0, an unset motion, light_size 0,
+// aperture 0 or samples 1.  `who` is the entry point, the prefix of its messages.
+int lens_render_dev(LensKind kind, const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth,
+                    int samples, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                    double* rgb64f, uint32_t* raycount2, void* stream) {
+    int s, rc = lens_arg_checks(kind, who, aperture, light_size, shutter);
+    if (rc) return rc;
+    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
+    if (kind == kLensMotion && !c->scene.d_motion) return rt_fail(RT_EINVAL, std::string(who) + ": no scene set");
+    L.variant = trace_variant(c->scene.tree, c->scene.transparent);
+    L.stream = (hipStream_t)stream;
+    L.scene = c->scene.d_scene;
+    L.aperture = aperture;
+    L.light_size = light_size;                              // 0 from the kinds without it
+    L.shutter = shutter;
+    if (kind == kLensMotion) L.motion = c->scene.d_motion;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    const hipError_t e = with_depth(depth, [&](auto B) {
+        constexpr int b = decltype(B)::value;
+        return kind == kLensMotion ? launch_lens<b, true, true>(L)
+               : kind == kLensSoft ? launch_lens<b, true, false>(L)
+                                   : launch_lens<b, false, false>(L);
+    });
+    // the names the kinds' kernels had as kernels of their own: the messages keep them
+    static const char* const kKernel[] = {"rt_dof_kernel: ", "rt_soft_kernel: ", "rt_motion_kernel: "};
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string(kKernel[kind]) + hipGetErrorString(e));
+    return RT_OK;
+}
+
+extern "C" int rt_render_dof_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                 double aperture, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                 uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensDof, "rt_render_dof_dev", c, cam, W, H, depth, samples, aperture, 0.0, 0.0, rgba32f,
+                           rgba8, rgb64f, raycount2, stream);
+}
+
+extern "C" int rt_render_soft_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                  double aperture, double light_size, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                  uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensSoft, "rt_render_soft_dev", c, cam, W, H, depth, samples, aperture, light_size, 0.0,
+                           rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                                    double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                                    double* rgb64f, uint32_t* raycount2, void* stream) {
+    return lens_render_dev(kLensMotion, "rt_render_motion_dev", c, cam, W, H, depth, samples, aperture, light_size,
+                           shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}

@@ -21,7 +21,7 @@
 
 namespace rtk {
 
-// One-wave workgroups; a fixed grid (the pixel count is only known on the device: rt_classify_kernel, rt_kernel.hip,
+// One-wave workgroups; a fixed grid (the pixel count is only known on the device: rt_classify_kernel, rt_sampled.hip,
 // writes the list and its length) walks the list with a grid-stride loop.  A wave takes 64 / S^2 listed pixels per
 // step: lane l traces sample (a, b) of the pixel of its group l >> 2 log2 S, a = the low log2 S bits of l, b the next
 // log2 S: reduce_samples with lane stride S.  Lanes past the end of the list repeat its last pixel.

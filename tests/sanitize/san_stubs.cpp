@@ -106,7 +106,7 @@ extern "C" int rt_trace_rays_dev(rt_ctx* c, const double* starts, const double* 
     if (!c) return rt_fail(RT_EINVAL, "rt_trace_rays_dev: null context");
     return oracle_trace_rays(&c->scene, starts, ends, n, depth, rgb64f, raycount, 1);
 }
-// rt_render_screen's device-side ray formation (rt_kernel.hip), restated on the host with the same operations.
+// rt_render_screen's device-side ray formation (rt_render.hpp), restated on the host with the same operations.
 int rt_trace_screen_dev(rt_ctx* c, const double cam[3], const ScreenPix* pix, const int32_t* first, int m,
                         const double* jit, int n, int depth, double* rgb64f, uint32_t* done, uint32_t seq, void*) {
     if (!c) return rt_fail(RT_EINVAL, "rt_trace_screen_dev: null context");

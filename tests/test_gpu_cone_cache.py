@@ -1,4 +1,4 @@
-"""GPU tests of the per-view primary cone-mask cache (rt_kernel.hip render_dev_impl, rt_disp_kernel):
+"""GPU tests of the per-view primary cone-mask cache (rt_plain.hip render_dev_impl, rt_disp_kernel):
 the calibration render of a static view records each 8x8 tile's primary-ray sphere mask, later renders of
 exactly that view read it (one scalar load) instead of recomputing it, and renders of any other camera
 compute their own.  The masks only skip spheres a tile's rays provably miss, so every frame must stay

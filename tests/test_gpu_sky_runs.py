@@ -1,4 +1,4 @@
-"""GPU tests of the runs of sky tiles (rt_render.hpp render_body, rt_kernel.hip rt_run_plan_kernel): a cached render of
+"""GPU tests of the runs of sky tiles (rt_render.hpp render_body, rt_plain.hip rt_run_plan_kernel): a cached render of
 a calibrated static view sends one wave per run of up to RT_SKY_RUN_MAX adjacent sky tiles, which stores the miss
 constants of the whole run.  Every frame equals the oracle bit for bit and the frame of a twin context created under
 RT_SKY_RUN_MAX=1 (the plain table) byte for byte; the output buffers are filled with a sentinel before every render (the

@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 listings of the sampled and render kernels of two builds, kernel by kernel: were the lens-family
-kernels of a parent (rt_dof_kernel, rt_soft_kernel, rt_motion_kernel, one listing each per depth) compiled to the same
-code as the instances of rt_lens_kernel (rt_lens_k<kind>_b<B>.s)?
+"""Compare the gfx950 listings of two builds, kernel by kernel.
+
+  python tools/isa_compare.py --by-symbol PARENT_DIR BRANCH_DIR > profiles/split/isa_compare.md
+
+Directory against directory, keyed by symbol: every kernel of every listing of PARENT_DIR against the kernel of the
+same symbol wherever it lies among the listings of BRANCH_DIR (a change that moves kernels between translation units
+and should change none); a kernel missing from the branch, or found in more than one of its listings, is a difference.
 
   python tools/isa_compare.py PARENT_DIR BRANCH_DIR > profiles/lens/isa_compare.md
+
+The record of the lens fold (reproducible from the trees of that change only, whose parent still had the three kernels):
+were the lens-family kernels of a parent (rt_dof_kernel, rt_soft_kernel, rt_motion_kernel, one listing each per depth)
+compiled to the same code as the instances of rt_lens_kernel (rt_lens_k<kind>_b<B>.s)?
 
 Each directory holds rt_render_b<B>.s, rt_adaptive_b<B>.s and the lens family's listings for B = 0..7, made with the
 Makefile's flags and --cuda-device-only -S (the `isa` target's command, for every depth).  A kernel's instruction
@@ -81,7 +89,63 @@ def verdict(a, b):
     return "; ".join(diffs) or "equal"
 
 
+def listing_group(f):
+    """rt_render_b3.s -> rt_render_b<B>.s: the per-depth listings of one source are one row of the table."""
+    return re.sub(r"_k\d_b\d\.s$", "_k<K>_b<B>.s", re.sub(r"(?<!_k\d)_b\d\.s$", "_b<B>.s", f))
+
+
+def main_by_symbol(parent, branch):
+    files = lambda d: sorted(f for f in os.listdir(d) if f.endswith(".s"))
+    where = {}                                              # symbol -> [(branch listing, kernel)]
+    for f in files(branch):
+        for sym, v in kernels(os.path.join(branch, f)).items():
+            where.setdefault(sym, []).append((f, v))
+    rows, detail, differ, seen = {}, [], 0, set()
+    for f in files(parent):
+        for sym, v in sorted(kernels(os.path.join(parent, f)).items()):
+            seen.add(sym)
+            hits = where.get(sym, [])
+            verd = verdict(v, hits[0][1]) if len(hits) == 1 else f"in {len(hits)} listings of the branch"
+            differ += verd != "equal"
+            r = rows.setdefault(listing_group(f), {"n": 0, "bad": [], "to": set()})
+            r["n"] += 1
+            r["to"].update(listing_group(h[0]) for h in hits)
+            if verd != "equal":
+                r["bad"].append(sym)
+            if listing_group(f) == f:                       # a listing that is not one of a per-depth family: by kernel
+                if re.search(r"\d+rt_\w+_kernel", sym):
+                    detail.append((f, sym, v, hits[0][0] if hits else "-", verd))
+                else:                                       # the sort's and the scan's (rocprim, through hipcub)
+                    lib = rows.setdefault(f"`{f}`: library kernels", {"n": 0, "bad": [], "to": set()})
+                    lib["n"] += 1
+                    lib["to"].update(h[0] for h in hits)
+                    if verd != "equal":
+                        lib["bad"].append(sym)
+    new = sorted(s for s in where if s not in seen)
+    print("# Parent against branch, kernel by kernel\n")
+    print("Made by `tools/isa_compare.py --by-symbol` (its docstring says what is compared and what is normalised).  \"equal\":")
+    print("the kernel of that symbol is in exactly one listing of the branch, the instruction streams are equal line by line")
+    print("and the five resource figures are equal.\n")
+    print("| parent listings | kernels | found in the branch's | differing |")
+    print("|---|---|---|---|")
+    for g, r in rows.items():
+        print(f"| {g if '`' in g else '`' + g + '`'} | {r['n']} | " + ", ".join(f"`{t}`" for t in sorted(r["to"])) + f" | {len(r['bad'])}" +
+              "".join(f" `{s}`" for s in r["bad"]) + " |")
+    print("\n(The library kernels are also counted in their listing's row.)")
+    print("\n## The project's kernels of the listings that are not per depth\n")
+    print("| parent listing | kernel | lines | VGPRs | SGPRs | accum_offset | scratch | LDS | branch listing | verdict |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for f, sym, v, to, verd in detail:
+        name = sym if len(sym) <= 72 else sym[:69] + "..."
+        print(f"| `{f}` | `{name}` | {len(v[0])} | " + " | ".join(v[1].get(x, "-") for x in FIGURES) + f" | `{to}` | {verd} |")
+    print(f"\nKernels of the branch with no counterpart in the parent: {len(new)}" + "".join(f" `{s}`" for s in new) + ".")
+    print(f"\n{differ} kernels differ.")
+    sys.exit(1 if differ or new else 0)
+
+
 def main():
+    if sys.argv[1] == "--by-symbol":
+        return main_by_symbol(*sys.argv[2:4])
     parent, branch = sys.argv[1:3]
     kind_name = {v: k for k, v in KINDS.items()}
     inst = {(0, 0): "opaque", (1, 0): "FULL", (1, 1): "tree"}
