@@ -440,6 +440,61 @@ int rt_render_motion(rt_ctx* ctx, const rt_scene* scene, const double* displacem
                      int height, int depth, int samples, double aperture, double light_size, double shutter,
                      float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
+/* ---- adaptive sampling of the lens, soft-shadow and motion-blur renders (ABI 10: new symbols only) ------------- */
+/* Two levels of rt_render_motion_dev: every pixel gets S_lo x S_lo samples, and the pixels whose coarse samples disagree
+ * or that stand on a contrast edge of the coarse frame get S_hi x S_hi.  Deterministic, and defined entirely by
+ * rt_render_motion_dev.  For a full width x height frame, S_lo = `samples_lo` <= S_hi = `samples_hi`, both in
+ * {1, 2, 4, 8}, T = `threshold` in {-1, .., 255}, and A, R, F and the displacements as for rt_render_motion_dev:
+ *  1. Coarse frame.  C is the frame rt_render_motion_dev(cam, width, height, depth, S_lo, A, R, F) writes; c(a, b),
+ *     0 <= a, b < S_lo, are a pixel's samples before the reduction; q(v) is the RGBA8 byte of a colour value,
+ *     floor(clamp(v, 0, 1) * 255 + 0.5) of the FP64 value, NaN -> 0.
+ *  2. Criterion.  Pixel (i, j) is REFINED iff (a) or (b):
+ *     (a) spread: for some channel, the maximum over (a, b) of q(c(a, b)) minus the minimum over (a, b) is > T;
+ *     (b) contrast: rule 2 of rt_render_adaptive_dev on the bytes q(C): some in-frame 4-neighbour differs by more than
+ *         T in some channel.
+ *     Both read coarse data only, never a refined value.  T = -1 refines every pixel, a 1 x 1 frame included ((a) holds:
+ *     rt_render_adaptive_dev refines nothing there); T = 255 refines nothing; with S_lo = 1, (a) never holds for T >= 0.
+ *  3. Value.  A refined pixel has exactly the value and the two counters rt_render_motion_dev(.., S_hi, A, R, F) gives
+ *     it, an unrefined pixel exactly those of C.  The outputs derive from that value as in rt_render_ss_dev rules 3-5.
+ *     `refined`: a nullable uint8 image, width x height, 1 for a refined pixel and 0 otherwise.
+ *  4. Pins that follow, with NO shortcut in the implementation (the same three passes run for every argument): T = 255
+ *     writes C; T = -1 writes the S_hi frame; S_lo = S_hi writes that frame for every T; F = 0, R = 0 and A = 0 reduce
+ *     the frame to rt_render_soft_dev's, rt_render_dof_dev's and rt_render_ss_dev's as for rt_render_motion_dev; and
+ *     A = R = F = 0, S_lo = 1, T >= 0 on a frame larger than 1 x 1 writes exactly what rt_render_adaptive_dev(S_hi, T)
+ *     writes, `refined` included.
+ *  5. rt_render_lens_adaptive_dev: full frames only.  Asynchronous on `stream`, no allocation and no host
+ *     synchronisation, so the call may be captured in a hipGraph.  No per-view state: it reads the scene and motion
+ *     records and never writes them, and the cone masks, the level masks and the tile order stay intact.  Three passes:
+ *     the coarse render into the caller's outputs, which also leaves one spread byte per pixel in the workspace; a
+ *     classification pass that writes `refined` and compacts the refined pixels into a work list (whose order is
+ *     unspecified and influences no output); a refine pass over the list, S_hi x S_hi lanes per pixel reduced in the
+ *     wave, which overwrites the refined pixels in every requested output.
+ *     `workspace`: workspace_bytes >= rt_lens_adaptive_workspace_bytes(...) of device memory, 16-byte aligned, owned by
+ *     the caller and used by one call at a time.  It holds the counter, the work list, the spread bytes and room for
+ *     the coarse RGBA8 image (used when `rgba8` is null); its first uint32 holds the number of refined pixels once the
+ *     call's work is done.
+ *  6. RT_EINVAL (rt_last_error names the argument), and no pixel written, for a sample count outside {1, 2, 4, 8},
+ *     S_lo > S_hi, a `threshold` outside -1 .. 255, rt_render_motion_dev's checks of A, R and F, a null, misaligned or
+ *     too small `workspace`, and an int32 overflow of either sample-grid camera.
+ *  7. Not offered: row bands, multi-GPU and the packed or asynchronous host paths; more than two levels; a dilation of
+ *     the mask; jittered samples; a threshold per effect. */
+/* Host only: the bytes of device workspace rt_render_lens_adaptive_dev needs for a width x height frame.  RT_EINVAL for
+ * a null pointer or a bad size. */
+int rt_lens_adaptive_workspace_bytes(int width, int height, size_t* bytes);
+/* Device pointers, each output nullable, width * height pixels. */
+int rt_render_lens_adaptive_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples_lo,
+                                int samples_hi, int threshold, double aperture, double light_size, double shutter,
+                                float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, uint8_t* refined,
+                                void* workspace, size_t workspace_bytes, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_motion: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the frame with the context's own workspace.  *n_refined (nullable): the
+ * number of refined pixels n.  *stats from the summed raycount2: primary_rays = (width * height - n) * S_lo * S_lo +
+ * n * S_hi * S_hi. */
+int rt_render_lens_adaptive(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                            int width, int height, int depth, int samples_lo, int samples_hi, int threshold,
+                            double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                            double* rgb64f, uint8_t* refined, rt_stats* stats, uint64_t* n_refined);
+
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.
  * GRAY formats hold the R channel only and are accepted only for an ACHROMATIC scene (rt_scene_achromatic):

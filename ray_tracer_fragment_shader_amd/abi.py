@@ -195,6 +195,13 @@ SIGNATURES = {
                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rt_render_motion": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int,
                                  c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, _P(rt_stats)]),
+    "rt_lens_adaptive_workspace_bytes": (c_int, [c_int, c_int, _P(ctypes.c_size_t)]),
+    "rt_render_lens_adaptive_dev": (c_int, [c_void_p, _P(rt_camera), c_int, c_int, c_int, c_int, c_int, c_int, c_double,
+                                            c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, ctypes.c_size_t, c_void_p]),
+    "rt_render_lens_adaptive": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, _P(rt_stats), _P(c_uint64)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

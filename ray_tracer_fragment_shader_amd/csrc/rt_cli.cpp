@@ -36,6 +36,12 @@
 //                                                  motion blur: sphere 0 moves by +-(40, 0, 0) (scene-local) during the
 //                                                  exposure, of which the shutter is open for the share 1; each of the
 //                                                  S x S samples has its own time (rt_render_motion)
+//   rt_render --config c2 --samples 4 --coarse 2 --refine 8 [--aperture 8 [--focus 0.8]] [--light-size 40]
+//             [--shutter 1 --move 0:40,0,0 ...] --out c2_lens_ad.ppm
+//                                                  the frame of the three modes above with 2 x 2 samples per pixel, and
+//                                                  4 x 4 only where the 2 x 2 samples' RGBA8 bytes spread by more than 8
+//                                                  or the coarse RGBA8 differs from a 4-neighbour by more than 8
+//                                                  (rt_render_lens_adaptive; threshold in -1 .. 255)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -74,6 +80,9 @@ struct Options {
     double light_size = 0.0;
     bool motion = false;                     // --shutter F: rt_render_motion with the --move displacements (needs --samples)
     double shutter = 0.0;
+    int coarse = 0;                          // --coarse C with --refine T: rt_render_lens_adaptive, C x C samples per pixel
+    bool refine = false;                     // ... and --samples x --samples where they disagree by more than T
+    int refine_t = 0;
     std::vector<int> move_k;                 // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -234,10 +243,12 @@ int main(int argc, char** argv) {
         else if (a == "--light-size") { o.soft = true; o.light_size = number_arg(a, next()); }
         else if (a == "--shutter") { o.motion = true; o.shutter = number_arg(a, next()); }
         else if (a == "--move") move_arg(next(), &o);
+        else if (a == "--coarse") o.coarse = std::atoi(next().c_str());
+        else if (a == "--refine") { o.refine = true; o.refine_t = std::atoi(next().c_str()); }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
     }
@@ -279,6 +290,30 @@ int main(int argc, char** argv) {
     }
     if (o.focus && (!o.dof || !(o.focus_ratio > 0.0))) {
         std::fprintf(stderr, "rt_render: --focus needs --aperture and a ratio > 0\n");
+        return 2;
+    }
+    if ((o.coarse != 0) != o.refine) {
+        std::fprintf(stderr, "rt_render: --coarse and --refine need each other\n");
+        return 2;
+    }
+    if (o.refine && o.samples == 0) {
+        std::fprintf(stderr, "rt_render: --coarse and --refine need --samples\n");
+        return 2;
+    }
+    if (o.refine && o.adaptive) {
+        std::fprintf(stderr, "rt_render: --coarse and --refine exclude --adaptive\n");
+        return 2;
+    }
+    if (o.refine && o.faithful >= 0) {
+        std::fprintf(stderr, "rt_render: --coarse and --refine exclude --faithful\n");
+        return 2;
+    }
+    if (o.refine && o.gpus > 0) {
+        std::fprintf(stderr, "rt_render: --coarse and --refine exclude --gpus\n");
+        return 2;
+    }
+    if (o.refine && o.coarse > o.samples) {
+        std::fprintf(stderr, "rt_render: --coarse must not exceed --samples\n");
         return 2;
     }
     if (o.samples != 0 && (o.faithful >= 0 || o.gpus > 0)) {
@@ -402,7 +437,11 @@ int main(int argc, char** argv) {
     uint64_t n_refined = 0;
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k < o.repeat; ++k) {
-        if (o.motion)
+        if (o.refine)
+            check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
+                                          o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
+                                          rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
+        else if (o.motion)
             check(rt_render_motion(ctx, &scene, displacement.data(), &cam, W, H, depth, o.samples, o.aperture,
                                    o.light_size, o.shutter, nullptr, rgba8.data(), nullptr, &st), "rt_render_motion");
         else if (o.soft)
@@ -429,7 +468,12 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.motion)
+    if (o.refine)
+        std::printf("rt_render: adaptive lens render, threshold %d, shutter %g, light half-width %g, lens half-width %g: "
+                    "%llu of %llu pixels refined from %d x %d to %d x %d samples\n", o.refine_t, o.shutter, o.light_size,
+                    o.aperture, (unsigned long long)n_refined, (unsigned long long)W * H, o.coarse, o.coarse, o.samples,
+                    o.samples);
+    else if (o.motion)
         std::printf("rt_render: motion blur, shutter %g, %d moving spheres, light half-width %g, lens half-width %g: "
                     "%d x %d shutter times per pixel, %llu primary rays\n", o.shutter, (int)o.move_k.size(),
                     o.light_size, o.aperture, o.samples, o.samples, (unsigned long long)st.primary_rays);

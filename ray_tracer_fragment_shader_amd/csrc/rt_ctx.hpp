@@ -2,12 +2,13 @@
 // rt_host.cpp, rt_screen.cpp and rt_group.cpp see the context through the accessors of rt_internal.hpp).
 //
 // Which unit holds what (the render, ray-list and sampled kernels are templates in rt_render.hpp and rt_sampled.hpp,
-// instantiated per depth in rt_render_b<B>.hip, rt_adaptive.hip and rt_lens.hip):
+// instantiated per depth in rt_render_b<B>.hip, rt_adaptive.hip, rt_lens.hip and rt_lens_adaptive.hip):
 //   rt_context.hip  the context's lifetime, its A/B knobs, scene and motion upload (rt_scene_init_kernel)
 //   rt_plain.hip    the plain render path, render_dev_impl and its eight steps, and the view cache it owns: the
 //                   dispatch-table kernels (rt_order / rowsum / iota / disp / run_plan / run_disp), rt_prepare_kernel
 //   rt_diag.hip     the view diagnostics of include/rt_diag.h
-//   rt_sampled.hip  adaptive supersampling (rt_classify_kernel) and the lens family's device entry points
+//   rt_sampled.hip  adaptive supersampling (rt_classify_kernel), the lens family's device entry points and the
+//                   adaptive lens render's
 //   rt_frames.hip   every call that renders into host memory: the context's device buffers, the ray sums, the packed
 //                   and asynchronous frames, the pinned-memory registry, the copy kernel and the SDMA path
 //   rt_rays.hip     the ray-list entry points (rt_intersect_kernel, rt_probe_math_kernel)

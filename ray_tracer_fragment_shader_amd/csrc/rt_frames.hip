@@ -349,6 +349,44 @@ extern "C" int rt_render_motion(rt_ctx* c, const rt_scene* scene, const double* 
                             aperture, light_size, shutter, rgba32f, rgba8, rgb64f, stats);
 }
 
+// rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
+// rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
+// back.
+extern "C" int rt_render_lens_adaptive(rt_ctx* c, const rt_scene* scene, const double* displacement,
+                                       const rt_camera* cam, int W, int H, int depth, int samples_lo, int samples_hi,
+                                       int threshold, double aperture, double light_size, double shutter,
+                                       float* rgba32f, uint8_t* rgba8, double* rgb64f, uint8_t* refined,
+                                       rt_stats* stats, uint64_t* n_refined) {
+    const char* who = "rt_render_lens_adaptive";
+    int rc = sampled_host_checks(who, c, W, H, samples_lo);
+    if (rc || (rc = sampled_host_checks(who, c, W, H, samples_hi))) return rc;
+    if (samples_lo > samples_hi) return rt_fail(RT_EINVAL, std::string(who) + ": samples_lo must not exceed samples_hi");
+    if (threshold < -1 || threshold > 255)
+        return rt_fail(RT_EINVAL, std::string(who) + ": threshold must lie in -1 .. 255");
+    if ((rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const size_t npx = (size_t)W * H;
+    const size_t ws_bytes = rt_lens_adaptive_layout(npx).bytes;
+    ExtraBuf x[2] = {{rt_ctx::Frames::kBufRefined, refined ? npx : 0, refined, nullptr},
+                     {rt_ctx::Frames::kBufAdaptive, ws_bytes, nullptr, nullptr}};
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, x, 2,
+        [&](void* const* d) {
+            return rt_render_lens_adaptive_dev(c, cam, W, H, depth, samples_lo, samples_hi, threshold, aperture,
+                                               light_size, shutter, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                                               (uint32_t*)d[3], (uint8_t*)x[0].dev, x[1].dev, ws_bytes, c->frames.rs);
+        },
+        [&](uint64_t* prim) {
+            uint32_t n = 0;                                 // the work list's length: the refined pixels
+            RT_HIP(hipMemcpy(&n, x[1].dev, sizeof(n), hipMemcpyDeviceToHost));
+            if (n_refined) *n_refined = n;
+            *prim = (uint64_t)(npx - n) * (uint64_t)(samples_lo * samples_lo) +
+                    (uint64_t)n * (uint64_t)(samples_hi * samples_hi);
+            return RT_OK;
+        });
+}
+
 // ---- copy_mode 3: device-to-host frames on an SDMA engine (HSA runtime, hsa_amd_memory_async_copy_on_engine) ----
 struct SdmaAgents {
     uint32_t domain = 0, bdf = 0;

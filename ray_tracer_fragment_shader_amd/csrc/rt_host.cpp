@@ -235,6 +235,15 @@ extern "C" int rt_adaptive_workspace_bytes(int width, int height, int samples, s
     return RT_OK;
 }
 
+extern "C" int rt_lens_adaptive_workspace_bytes(int width, int height, size_t* bytes) {
+    if (!bytes) return rt_fail(RT_EINVAL, "rt_lens_adaptive_workspace_bytes: null pointer");
+    *bytes = 0;
+    if (width <= 0 || height <= 0 || (long long)width * height > (1LL << 31))
+        return rt_fail(RT_EINVAL, "rt_lens_adaptive_workspace_bytes: bad image size");
+    *bytes = rt_lens_adaptive_layout((size_t)width * (size_t)height).bytes;
+    return RT_OK;
+}
+
 namespace {
 
 int frames_of(const rt_rows* r) { return (r && r->frames > 1) ? r->frames : 1; }

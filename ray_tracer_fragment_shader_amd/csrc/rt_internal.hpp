@@ -41,6 +41,18 @@ inline AdaptiveLayout rt_adaptive_layout(size_t npx) {
     return AdaptiveLayout{kAdaptiveAlign, kAdaptiveAlign + img, kAdaptiveAlign + 2 * img};
 }
 
+// The workspace of rt_render_lens_adaptive_dev for a W x H frame (rt_lens_adaptive_workspace_bytes): the adaptive
+// workspace's three parts at their offsets (the coarse RGBA8 image in place of the base image), then one spread byte
+// per pixel.
+struct LensAdaptiveLayout {
+    size_t base8, list, spread, bytes;         // offsets (the counter is at 0); total
+};
+inline LensAdaptiveLayout rt_lens_adaptive_layout(size_t npx) {
+    const AdaptiveLayout a = rt_adaptive_layout(npx);
+    return LensAdaptiveLayout{a.base8, a.list, a.bytes,
+                              a.bytes + (npx + kAdaptiveAlign - 1) / kAdaptiveAlign * kAdaptiveAlign};
+}
+
 // Device ordinal of a context (rt_group.cpp).
 int rt_ctx_device(const rt_ctx* ctx);
 

@@ -23,8 +23,13 @@ using namespace rtk;
 // 1920 x 1080 c2 frame) made this pass 86 us long.  Each flagged lane stores at the workgroup's base + the flagged
 // pixels of earlier waves and runs + the flagged lanes below it.  The list's order depends on the workgroups'
 // arrival; no output does.
+// SPREAD (rt_render_lens_adaptive_dev): base8 is the coarse lens frame, and a pixel is also refined when its samples'
+// spread byte (rt_lens_coarse_kernel) is above T — for T = -1 every pixel, a lone one included.  spread is not read
+// without the flag.
 constexpr int kClassifyThreads = 1024, kClassifyPer = 8;
-__global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uint32_t* __restrict__ base8, int W, int H,
+template <bool SPREAD>
+__global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uint32_t* __restrict__ base8,
+                                                                       const uint8_t* __restrict__ spread, int W, int H,
                                                                        int T, uint8_t* __restrict__ refined,
                                                                        uint32_t* __restrict__ count,
                                                                        uint32_t* __restrict__ list) {
@@ -36,7 +41,7 @@ __global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uin
     // The loads of all runs first, without branches (a neighbour outside the frame, and a pixel past the frame's end,
     // is replaced by an in-frame address and masked below): the 5 kClassifyPer loads of a lane are in flight together,
     // where one dependent round trip per run made the pass latency-bound.
-    uint32_t px[kClassifyPer][5], edge[kClassifyPer];
+    uint32_t px[kClassifyPer][5], edge[kClassifyPer], spr[kClassifyPer];
 #pragma unroll
     for (int r = 0; r < kClassifyPer; ++r) {
         const size_t k = k0 + (size_t)r * kClassifyThreads, kc = k < n ? k : n - 1;   // (n <= 2^31: kc fits 32 bits)
@@ -48,6 +53,7 @@ __global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uin
         px[r][2] = base8[kc + rr];
         px[r][3] = base8[kc - (d ? (size_t)W : 0)];
         px[r][4] = base8[kc + (u ? (size_t)W : 0)];
+        if constexpr (SPREAD) spr[r] = spread[kc];
     }
 #pragma unroll
     for (int r = 0; r < kClassifyPer; ++r) {
@@ -62,6 +68,7 @@ __global__ __launch_bounds__(kClassifyThreads) void rt_classify_kernel(const uin
             }
             flag |= ((edge[r] >> nb) & 1u) && worst > T;
         }
+        if constexpr (SPREAD) flag |= k < n && (int)spr[r] > T;
         if (k < n && refined) refined[k] = flag ? 1 : 0;
         flags |= (flag ? 1u : 0u) << r;
     }
@@ -128,9 +135,9 @@ extern "C" int rt_render_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, in
     rc = rt_render_ss_dev(c, cam, W, H, depth, 1, nullptr, rgba32f, base8, rgb64f, raycount2, st);
     if (rc) return rc;
     constexpr size_t kClassifyBlock = (size_t)kClassifyThreads * kClassifyPer;
-    hipLaunchKernelGGL(rt_classify_kernel, dim3((unsigned)((npx + kClassifyBlock - 1) / kClassifyBlock)),
-                       dim3(kClassifyThreads), 0, st,
-                       reinterpret_cast<const uint32_t*>(base8), W, H, threshold, refined, count, list);
+    hipLaunchKernelGGL(rt_classify_kernel<false>, dim3((unsigned)((npx + kClassifyBlock - 1) / kClassifyBlock)),
+                       dim3(kClassifyThreads), 0, st, reinterpret_cast<const uint32_t*>(base8),
+                       (const uint8_t*)nullptr, W, H, threshold, refined, count, list);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_classify_kernel: ") + hipGetErrorString(e));
     // S = 1: a refined pixel's only sample is the base sample itself, already in place
@@ -227,4 +234,70 @@ extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int 
                                     double* rgb64f, uint32_t* raycount2, void* stream) {
     return lens_render_dev(kLensMotion, "rt_render_motion_dev", c, cam, W, H, depth, samples, aperture, light_size,
                            shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+// ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------
+// Three passes on `stream`, all of the motion kind: rt_lens_coarse_kernel on the samples_lo grid straight into the
+// caller's outputs (the RGBA8 image into the workspace when the caller has none) with each pixel's spread byte,
+// rt_classify_kernel<true> on those bytes, rt_lens_refine_kernel on the samples_hi grid over the work list.  No
+// shortcut for any threshold, for equal sample counts or for an argument of 0; nothing per view, no field of the
+// context written (lens_render_dev).
+extern "C" int rt_render_lens_adaptive_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples_lo,
+                                           int samples_hi, int threshold, double aperture, double light_size,
+                                           double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                           uint32_t* raycount2, uint8_t* refined, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    const char* who = "rt_render_lens_adaptive_dev";
+    if (ss_log2_of(samples_lo) < 0) return rt_fail(RT_EINVAL, std::string(who) + ": samples_lo must be 1, 2, 4 or 8");
+    if (ss_log2_of(samples_hi) < 0) return rt_fail(RT_EINVAL, std::string(who) + ": samples_hi must be 1, 2, 4 or 8");
+    if (samples_lo > samples_hi) return rt_fail(RT_EINVAL, std::string(who) + ": samples_lo must not exceed samples_hi");
+    if (threshold < -1 || threshold > 255)
+        return rt_fail(RT_EINVAL, std::string(who) + ": threshold must lie in -1 .. 255");
+    int s_lo, s_hi, rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter);
+    if (rc) return rc;
+    SampledLaunch lo{}, hi{};                               // P: each sample grid's ray set-up
+    if ((rc = sample_grid_front(c, cam, W, H, depth, samples_lo, &s_lo, &lo.P))) return rc;
+    if ((rc = sample_grid_front(c, cam, W, H, depth, samples_hi, &s_hi, &hi.P))) return rc;
+    if (!c->scene.d_motion) return rt_fail(RT_EINVAL, std::string(who) + ": no scene set");
+    const size_t npx = (size_t)W * (size_t)H;
+    const LensAdaptiveLayout lay = rt_lens_adaptive_layout(npx);
+    if (!workspace || workspace_bytes < lay.bytes || (uintptr_t)workspace % 16 != 0)
+        return rt_fail(RT_EINVAL, std::string(who) + ": null, misaligned or too small workspace "
+                                                     "(rt_lens_adaptive_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+    uint32_t* count = reinterpret_cast<uint32_t*>(ws);
+    uint32_t* list = reinterpret_cast<uint32_t*>(ws + lay.list);
+    uint8_t* base8 = rgba8 ? rgba8 : ws + lay.base8;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+    lo.variant = hi.variant = trace_variant(c->scene.tree, c->scene.transparent);
+    lo.stream = hi.stream = st;
+    lo.scene = hi.scene = c->scene.d_scene;
+    lo.motion = hi.motion = c->scene.d_motion;
+    lo.aperture = hi.aperture = aperture;
+    lo.light_size = hi.light_size = light_size;
+    lo.shutter = hi.shutter = shutter;
+    lo.o32 = hi.o32 = rgba32f;
+    lo.o8 = base8;
+    hi.o8 = rgba8;
+    lo.o64 = hi.o64 = rgb64f;
+    lo.orc2 = hi.orc2 = raycount2;
+    lo.spread = ws + lay.spread;
+    hipError_t e = with_depth(depth, [&](auto B) { return launch_lens_coarse<decltype(B)::value>(lo); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_lens_coarse_kernel: ") + hipGetErrorString(e));
+    constexpr size_t kClassifyBlock = (size_t)kClassifyThreads * kClassifyPer;
+    hipLaunchKernelGGL(rt_classify_kernel<true>, dim3((unsigned)((npx + kClassifyBlock - 1) / kClassifyBlock)),
+                       dim3(kClassifyThreads), 0, st, reinterpret_cast<const uint32_t*>(base8),
+                       (const uint8_t*)lo.spread, W, H, threshold, refined, count, list);
+    e = hipGetLastError();
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_classify_kernel: ") + hipGetErrorString(e));
+    const size_t per_wave = (size_t)64 >> (2 * s_hi);
+    hi.grid = (unsigned)std::min<size_t>((npx + per_wave - 1) / per_wave, kRefineGrid);
+    hi.out_w = W;
+    hi.count = count;
+    hi.list = list;
+    e = with_depth(depth, [&](auto B) { return launch_lens_refine<decltype(B)::value>(hi); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_lens_refine_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
 }

@@ -6,6 +6,9 @@
 //                                      depth of field (rt_render_dof_dev), AREA: soft shadows (rt_render_soft_dev), each
 //                                      ray lit by its own light points, and AREA, MOTION: motion blur
 //                                      (rt_render_motion_dev), each sample at its own shutter time.
+//   rt_lens_coarse_kernel<B, TRANSP, TREE>, rt_lens_refine_kernel<B, TRANSP, TREE>  the two tracing passes of the
+//                                      adaptive lens render (rt_render_lens_adaptive_dev): the motion kind over the
+//                                      whole frame with each pixel's sample spread, and over a compacted work list.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -14,7 +17,8 @@
 // reduces over the whole wave: every lane stays active, lanes without a sample trace a clamped one and store nothing.
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
-// rt_adaptive.hip (rt_adaptive_b<B>.o) and, once per depth and kind, rt_lens.hip (rt_lens_k<kind>_b<B>.o).
+// rt_adaptive.hip (rt_adaptive_b<B>.o), once per depth and kind rt_lens.hip (rt_lens_k<kind>_b<B>.o), and
+// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o).
 #pragma once
 
 #include "rt_render.hpp"
@@ -129,6 +133,107 @@ __global__ __launch_bounds__(64) void rt_lens_kernel(const DevScene* __restrict_
     }
 }
 
+// ---- The adaptive lens render (rt_render_lens_adaptive_dev, include/rt_api.h): both tracing passes run the motion
+// kind (AREA, MOTION) — an unset motion is the zero record the context keeps, R = 0 and A = 0 run the same code — so a
+// depth has one instance of each per scene variant. ----
+
+// The lanes' packed colour bytes (r | g << 8 | b << 16), channel by channel the larger one.
+__device__ __forceinline__ uint32_t max_bytes3(uint32_t p, uint32_t q) {
+    return max(p & 0xffu, q & 0xffu) | max(p & 0xff00u, q & 0xff00u) | max(p & 0xff0000u, q & 0xff0000u);
+}
+
+// The coarse pass: rt_lens_kernel<B, TRANSP, TREE, true, true> statement for statement — the same frame, bit for bit —
+// plus the pixel's sample spread: before the reduction every lane packs the three RGBA8 bytes of its own sample
+// (to_u8: NaN -> 0), an integer max butterfly with reduce_samples' partners at lane stride 8 runs over the bytes and
+// over their complements (255 - byte: the minimum), and the block's first lane stores
+//     max over channels of (max - min over the S x S samples)
+// as one byte at spread[k].  An S x S block lies wholly inside or outside the sample frame (rt_lens_kernel), so a
+// clamped lane never enters an in-frame pixel's spread.  S = 1: no partner, spread 0.  A kernel of its own, not a flag
+// of rt_lens_kernel: that one's parameter list, hence its instances' code, stays what it was.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_lens_coarse_kernel(const DevScene* __restrict__ S,
+                                                            const DevMotion* __restrict__ M, RenderParams P,
+                                                            double aperture, double light_size, double shutter,
+                                                            int tile_rows, void* o32, void* o8, double* o64,
+                                                            uint32_t* orc2, uint8_t* __restrict__ spread) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const d3 sp = screen_point(P, ic, j, right, upp);
+    const double inv_s = ldexp(1.0, -s);
+    const double ta = (double)(2 * (x & S1) - S1) * inv_s, tb = (double)(2 * (y & S1) - S1) * inv_s;
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    uint32_t seg = 0, sh = 0;
+    const int n = (x & S1) + ((y & S1) << s);
+    const double sigma = shutter * ((double)(2 * n + 1 - (1 << 2 * s)) * ldexp(1.0, -2 * s));
+    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];
+    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+    const Motion mo{sigma, M};
+    d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                            LightShift{light_size * ta, light_size * tb}, &mo);
+    const uint32_t mine = (uint32_t)to_u8(col.x) | ((uint32_t)to_u8(col.y) << 8) | ((uint32_t)to_u8(col.z) << 16);
+    uint32_t hi = mine, lo = 0xffffffu - mine;              // lo: the complements, so one max serves both
+    for (int m = 1; m <= 8 * S1; m = 2 * m == 1 << s ? 8 : 2 * m) {
+        hi = max_bytes3(hi, (uint32_t)__shfl_xor((int)hi, m));
+        lo = max_bytes3(lo, (uint32_t)__shfl_xor((int)lo, m));
+    }
+    reduce_samples(s, 8, col, seg, sh);
+    if ((x & S1) == 0 && (y & S1) == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+        const uint32_t d = hi + lo - 0xffffffu;             // per byte max - min >= 0: no borrow between the bytes
+        spread[k] = (uint8_t)max(max(d & 0xffu, (d >> 8) & 0xffu), (d >> 16) & 0xffu);
+    }
+}
+
+// The refine pass: rt_refine_kernel's walk of the work list with the lens family's rays.  P is the S x S sample grid
+// of the refined pixels; lane l traces sample (a, b) of the pixel of its group l >> 2 log2 S exactly as lane
+// (x, y) = (a, b) mod S of rt_lens_kernel<.., true, true> does — lens point e(a, b), light shift (R t_a, R t_b), time
+// sigma of n = a + S b, hits_ok from the motion record's swept proof per lane — and reduce_samples at lane stride S is
+// the same tree, so a listed pixel gets the value and the counters rt_render_motion_dev gives it.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_lens_refine_kernel(const DevScene* __restrict__ S,
+                                                            const DevMotion* __restrict__ M, RenderParams P,
+                                                            double aperture, double light_size, double shutter,
+                                                            int out_w, const uint32_t* __restrict__ count,
+                                                            const uint32_t* __restrict__ list, void* o32, void* o8,
+                                                            double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const uint32_t n = *count;                              // pixels on the list
+    const int s = P.ss_log2, s2 = 2 * s, S1 = (1 << s) - 1;
+    const uint32_t per_wave = 64u >> s2;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    const int a = lane & S1, b = (lane >> s) & S1;
+    const double inv_s = ldexp(1.0, -s);
+    const double ta = (double)(2 * a - S1) * inv_s, tb = (double)(2 * b - S1) * inv_s;
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    const double sigma = shutter * ((double)(2 * (a + (b << s)) + 1 - (1 << s2)) * ldexp(1.0, -s2));
+    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];
+    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+    const Motion mo{sigma, M};
+    const LightShift ls{light_size * ta, light_size * tb};
+    for (uint64_t g = blockIdx.x; g * per_wave < n; g += gridDim.x) {
+        const uint32_t q = (uint32_t)(g * per_wave) + (uint32_t)(lane >> s2);
+        const uint32_t pix = list[q < n ? q : n - 1];       // j * out_w + i
+        const int j0 = (int)(pix / (uint32_t)out_w), i0 = (int)(pix - (uint32_t)j0 * (uint32_t)out_w);
+        const d3 sp = screen_point(P, (i0 << s) + a, (j0 << s) + b, right, upp);
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh, ls, &mo);
+        reduce_samples(s, 1 << s, col, seg, sh);
+        if ((lane & ((1 << s2) - 1)) == 0 && q < n) store_sampled(P, pix, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -149,17 +254,26 @@ struct SampledLaunch {
     double light_size;                         // AREA: half-width of the lights' panels
     double shutter;                            // MOTION: share of the displacements the exposure covers
     const DevMotion* motion;                   // MOTION: the context's motion record (rt_set_motion)
+    uint8_t* spread;                           // rt_lens_coarse_kernel: one byte per output pixel
 };
 
-// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip) and, per kind, in rt_lens_k<kind>_b<B>.o
-// (rt_lens.hip).
+// Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
+// and, the adaptive lens render's two, in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
+template <int B>
+hipError_t launch_lens_coarse(const SampledLaunch& L);
+template <int B>
+hipError_t launch_lens_refine(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
     template <>                                                       \
     hipError_t launch_refine<B>(const SampledLaunch& L);              \
+    template <>                                                       \
+    hipError_t launch_lens_coarse<B>(const SampledLaunch& L);         \
+    template <>                                                       \
+    hipError_t launch_lens_refine<B>(const SampledLaunch& L);         \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -208,6 +322,26 @@ hipError_t launch_lens_impl(const SampledLaunch& L) {
         hipLaunchKernelGGL((rt_lens_kernel<B, decltype(transp)::value, decltype(tree)::value, AREA, MOTION>), g,
                            dim3(64), lds, L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter,
                            tile_rows, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_lens_coarse_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_lens_coarse_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter, tile_rows, L.o32, L.o8,
+                           L.o64, L.orc2, L.spread);
+    });
+}
+
+template <int B>
+hipError_t launch_lens_refine_impl(const SampledLaunch& L) {
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_lens_refine_kernel<B, decltype(transp)::value, decltype(tree)::value>), dim3(L.grid),
+                           dim3(64), lds, L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter, L.out_w,
+                           L.count, L.list, L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

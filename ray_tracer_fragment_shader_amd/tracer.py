@@ -210,6 +210,43 @@ class Tracer:
         return self._render_lens_into("rt_render_motion_dev", (aperture, light_size, shutter), cam, width, height,
                                       depth, samples, bufs, stream)
 
+    # ------------------------------------------------------------ adaptive sampling of the lens family's renders
+    def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
+                            refined=True):
+        """Buffers of an adaptive lens render (full frames): as alloc_ss(), plus `refined` (H, W) uint8 and the
+        `workspace` byte tensor sized by rt_lens_adaptive_workspace_bytes (one render at a time may use it)."""
+        n = ctypes.c_size_t()
+        abi.check(abi.lib().rt_lens_adaptive_workspace_bytes(width, height, ctypes.byref(n)),
+                  "rt_lens_adaptive_workspace_bytes")
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        dev = torch.device("cuda", self.device)
+        bufs["refined"] = torch.empty((height, width), dtype=torch.uint8, device=dev) if refined else None
+        bufs["workspace"] = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+        return bufs
+
+    def render_lens_adaptive_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples_lo: int,
+                                  samples_hi: int, threshold: int, aperture: float, light_size: float,
+                                  shutter: float, bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_lens_adaptive_dev: the frame of render_motion_into() with samples_lo x samples_lo samples per
+        pixel, and samples_hi x samples_hi for the pixels whose coarse samples' RGBA8 bytes spread by more than
+        `threshold` or whose coarse RGBA8 differs from a 4-neighbour by more than it; asynchronous on `stream`
+        (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        ws = bufs.get("workspace")
+        abi.check(abi.lib().rt_render_lens_adaptive_dev(
+            self._ctx, ctypes.byref(cam), width, height, depth, samples_lo, samples_hi, threshold, float(aperture),
+            float(light_size), float(shutter), _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
+            _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")), _ptr(bufs.get("refined")), _ptr(ws),
+            ws.numel() if ws is not None else 0, ctypes.c_void_p(st.cuda_stream)), "rt_render_lens_adaptive_dev")
+        return bufs
+
+    def render_lens_adaptive(self, cam, width, height, depth, samples_lo, samples_hi, threshold, aperture, light_size,
+                             shutter, rgba32f=True, rgba8=False, rgb64f=False, raycount=False, stream=None):
+        """-> the buffers of alloc_lens_adaptive(), `refined` included."""
+        bufs = self.alloc_lens_adaptive(width, height, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_lens_adaptive_into(cam, width, height, depth, samples_lo, samples_hi, threshold, aperture,
+                                              light_size, shutter, bufs, stream)
+
     def render_packed(self, cam, width, height, depth, float_format=None, byte_format=None, rows=None,
                       stream=None):
         """rt_render_dev_packed: the float image in float_format (RT_PIXEL_RGBA32F / GRAY32F) and the byte
