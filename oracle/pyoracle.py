@@ -69,13 +69,24 @@ def ref_available() -> bool:
     return os.path.exists(REF_SO) or os.path.exists(REF_SRC)
 
 
+def _ref_so_has(symbol: bytes) -> bool:
+    """The built reference library names `symbol` (read from the file: it is not loaded yet)."""
+    with open(REF_SO, "rb") as f:
+        return symbol in f.read()
+
+
 def ref() -> ctypes.CDLL:
     global _ref
     if _ref is None:
-        if not os.path.exists(REF_SO):
-            if not os.path.exists(REF_SRC):
-                raise RuntimeError("reference build unavailable (no /root/reference here)")
+        if os.path.exists(REF_SRC):
+            # make rebuilds a library older than ref_harness.cpp; one that is newer by date and still lacks this
+            # harness's entry points (a copy brought in from another build) is rebuilt outright.  A build that fails
+            # raises, with the compiler's messages on stderr.
             build(ref=True)
+            if not _ref_so_has(b"ref_trace_rays_at"):
+                subprocess.run(["make", "-B", "-C", HERE, "ref"], check=True, stdout=subprocess.DEVNULL)
+        elif not os.path.exists(REF_SO):
+            raise RuntimeError("reference build unavailable (no /root/reference here)")
         L = ctypes.CDLL(REF_SO)
         scene_args = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_char_p, c_void_p, c_int]
         L.ref_render.restype = c_int
@@ -88,6 +99,13 @@ def ref() -> ctypes.CDLL:
         L.ref_intersect.restype = c_int
         L.ref_intersect.argtypes = [c_char_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p]
+        if hasattr(L, "ref_trace_rays_at"):               # (an older library without its source: _ref_at says so)
+            L.ref_trace_rays_at.restype = c_int
+            L.ref_trace_rays_at.argtypes = [c_void_p, c_void_p, c_int, c_char_p, c_void_p, c_int, c_void_p, c_void_p,
+                                            c_int, c_int, c_void_p]
+            L.ref_intersect_at.restype = c_int
+            L.ref_intersect_at.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_void_p]
         L.ref_convert_string_coordinate.restype = None
         L.ref_convert_string_coordinate.argtypes = [c_char_p, c_void_p]
         L.ref_set_materials.restype = None
@@ -252,6 +270,54 @@ def ref_trace_rays(scene, starts, ends, depth):
     rgb = np.zeros((starts.shape[0], 3), np.float64)
     _ref_scene(scene).ref_trace_rays(*scene.ref_args(), _ptr(starts), _ptr(ends), starts.shape[0], depth, _ptr(rgb))
     return rgb
+
+
+def _centres_radii(centres, radii):
+    centres = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+    radii = np.ascontiguousarray(radii, np.float64).reshape(-1)
+    assert len(centres) == len(radii)
+    return centres, radii
+
+
+def _ref_at(scene, name):
+    """The by-centre entry point `name` of the reference library, or an error that says why it is not there."""
+    L = _ref_scene(scene)
+    if not hasattr(L, name):
+        raise RuntimeError(f"{REF_SO} was built from an older oracle/ref_harness.cpp (no {name}) and {REF_SRC} is not "
+                           "here to rebuild it")
+    return getattr(L, name)
+
+
+def ref_trace_rays_at(scene, centres, radii, starts, ends, depth):
+    """ref_trace_rays on `scene`'s board, lights and materials with the spheres Sphere(centres[k], radii[k])
+    (scene-local centres, any position: the reference harness otherwise places spheres by board square)."""
+    if not scene.has_board or any(lt.square is None for lt in scene.lights):
+        raise ValueError("the reference harness always inserts the board and places lights by square")
+    centres, radii = _centres_radii(centres, radii)
+    starts = np.ascontiguousarray(starts, np.float64)
+    ends = np.ascontiguousarray(ends, np.float64)
+    nl = len(scene.lights)
+    lsq = "".join(lt.square for lt in scene.lights).encode()
+    lcol = np.array([c for lt in scene.lights for c in lt.color] or [0.0], np.float64)
+    rgb = np.zeros((starts.shape[0], 3), np.float64)
+    _ref_at(scene, "ref_trace_rays_at")(_ptr(centres), _ptr(radii), len(radii), lsq, _ptr(lcol), nl, _ptr(starts),
+                                        _ptr(ends), starts.shape[0], depth, _ptr(rgb))
+    return rgb
+
+
+def ref_intersect_at(scene, centres, radii, starts, ends):
+    """ref_intersect with the spheres of ref_trace_rays_at."""
+    centres, radii = _centres_radii(centres, radii)
+    starts = np.ascontiguousarray(starts, np.float64)
+    ends = np.ascontiguousarray(ends, np.float64)
+    n = starts.shape[0]
+    out12 = np.zeros((n, 12), np.float64)
+    hit = np.zeros(n, np.int32)
+    mat = np.zeros(n, np.int32)
+    _ref_at(scene, "ref_intersect_at")(_ptr(centres), _ptr(radii), len(radii), _ptr(starts), _ptr(ends), n,
+                                       _ptr(out12), _ptr(hit), _ptr(mat))
+    return {"point": out12[:, 0:3], "normal": out12[:, 3:6], "reflected_end": out12[:, 6:9],
+            "transmitted_end": out12[:, 9:12], "hit": hit, "material": mat}
 
 
 def ref_intersect(scene, starts, ends):

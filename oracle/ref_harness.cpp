@@ -19,11 +19,22 @@ struct RefScene {
     vector<Light> lights;
 };
 
-RefScene build(const char* children, int n_children, const double* sph_yoff, const double* sph_r,
-               const double* mesh_edge, const char* light_sq, const double* light_col, int n_lights) {
+// The g_scene-like root with the board as its first child, and the light list of one frame (lights by square).
+RefScene root_and_lights(const char* light_sq, const double* light_col, int n_lights) {
     RefScene r;
     r.scene = new Shape(Point(BOARD_POSITION), Material(), sqrt((double)3) * BOARD_HALF_SIZE, false);
     r.scene->addRayObject(new CheckerBoard(Point(0.0, 0.0, 0.0)));
+    for (int k = 0; k < n_lights; ++k) {
+        string sq(light_sq + 2 * k, 2);
+        Point pos = Point(BOARD_POSITION) + Point(0.0, 3.5 * SQUARE_EDGE_SIZE, 0.0) + convertStringCoordinate(sq);
+        r.lights.push_back(Light(Point(light_col + 3 * k), pos));
+    }
+    return r;
+}
+
+RefScene build(const char* children, int n_children, const double* sph_yoff, const double* sph_r,
+               const double* mesh_edge, const char* light_sq, const double* light_col, int n_lights) {
+    RefScene r = root_and_lights(light_sq, light_col, n_lights);
     int ks = 0, km = 0;
     for (int c = 0; c < n_children; ++c) {
         char type = children[3 * c];
@@ -39,11 +50,16 @@ RefScene build(const char* children, int n_children, const double* sph_yoff, con
             r.scene->addRayObject(new Cube(p, mesh_edge[km++]));
         }
     }
-    for (int k = 0; k < n_lights; ++k) {
-        string sq(light_sq + 2 * k, 2);
-        Point pos = Point(BOARD_POSITION) + Point(0.0, 3.5 * SQUARE_EDGE_SIZE, 0.0) + convertStringCoordinate(sq);
-        r.lights.push_back(Light(Point(light_col + 3 * k), pos));
-    }
+    return r;
+}
+
+// The same g_scene with every sphere given by its scene-local centre instead of a board square (the tangent
+// constructions of tests/tangent_common.py place spheres anywhere): the board first, then Sphere(centres[k], radii[k])
+// in order; the lights by square, as build() places them.
+RefScene build_at(const double* centres, const double* radii, int n_spheres, const char* light_sq,
+                  const double* light_col, int n_lights) {
+    RefScene r = root_and_lights(light_sq, light_col, n_lights);
+    for (int k = 0; k < n_spheres; ++k) r.scene->addRayObject(new Sphere(Point(centres + 3 * k), radii[k]));
     return r;
 }
 
@@ -138,6 +154,46 @@ int ref_intersect(const char* children, int n_children, const double* sph_yoff, 
                   const double* mesh_edge, const double* starts, const double* ends, int n, double* out12,
                   int32_t* hit, int32_t* mat) {
     RefScene rs = build(children, n_children, sph_yoff, sph_r, mesh_edge, "", nullptr, 0);
+    for (int k = 0; k < n; ++k) {
+        Intersection in;
+        rs.scene->intersection(Line(Point(starts + 3 * k), Point(ends + 3 * k)), Point(0.0, 0.0, 0.0), in);
+        hit[k] = in.intersects() ? 1 : 0;
+        mat[k] = -1;
+        for (int q = 0; q < 12; ++q) out12[12 * k + q] = 0.0;
+        if (hit[k]) {
+            Point p = in.point(), nn = in.normal(), e = in.reflectedRay().endPoint();
+            Point t = in.transmittedRay().endPoint();
+            double* o = out12 + 12 * k;
+            o[0] = p.x(); o[1] = p.y(); o[2] = p.z();
+            o[3] = nn.x(); o[4] = nn.y(); o[5] = nn.z();
+            o[6] = e.x(); o[7] = e.y(); o[8] = e.z();
+            o[9] = t.x(); o[10] = t.y(); o[11] = t.z();
+            mat[k] = material_id(in.material());
+        }
+    }
+    delete rs.scene;
+    return 0;
+}
+
+// ref_trace_rays / ref_intersect on a scene whose spheres are given by scene-local centre (build_at).
+int ref_trace_rays_at(const double* centres, const double* radii, int n_spheres, const char* light_sq,
+                      const double* light_col, int n_lights, const double* starts, const double* ends, int n,
+                      int depth, double* rgb) {
+    RefScene rs = build_at(centres, radii, n_spheres, light_sq, light_col, n_lights);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int k = 0; k < n; ++k) {
+        Point color(0.0, 0.0, 0.0);
+        rayTraceRay(*rs.scene, rs.lights, Line(Point(starts + 3 * k), Point(ends + 3 * k)), color,
+                    (unsigned)depth);
+        rgb[3 * k] = color.x(); rgb[3 * k + 1] = color.y(); rgb[3 * k + 2] = color.z();
+    }
+    delete rs.scene;
+    return 0;
+}
+
+int ref_intersect_at(const double* centres, const double* radii, int n_spheres, const double* starts,
+                     const double* ends, int n, double* out12, int32_t* hit, int32_t* mat) {
+    RefScene rs = build_at(centres, radii, n_spheres, "", nullptr, 0);
     for (int k = 0; k < n; ++k) {
         Intersection in;
         rs.scene->intersection(Line(Point(starts + 3 * k), Point(ends + 3 * k)), Point(0.0, 0.0, 0.0), in);
