@@ -11,12 +11,6 @@
 
 #include "rt_layout.hpp"
 
-#ifdef __HIP__
-#define RT_HD __host__ __device__ __forceinline__
-#else
-#define RT_HD inline
-#endif
-
 // FP32 square root and reciprocal of the wave-culling tests (RT_FAST_MASK = 1): the hardware instructions
 // (v_sqrt_f32, v_rcp_f32, 1 ulp: relative error < 2^-22 on normal operands) instead of the correctly rounded
 // sequences (scaling, Newton and fixup steps around them: ~10 instructions each).  The culling tests only need

@@ -21,9 +21,9 @@ __global__ __launch_bounds__(kThreads) void rt_scene_init_kernel(DevScene* __res
     const int k = blockIdx.x * kThreads + threadIdx.x;
     if (k == 0) g->rsquare = rcp_core(g->square);
     if (k < 2) g->tri[k].rden = g->tri[k].fast ? rcp_core(g->tri[k].den) : 0.0;
-    const SceneView V = view_of(g, g, g->n_padded, g->n_stride, g->n_lights);
+    const SceneArrays A = scene_arrays(g);
     if (k < g->n_tris) {
-        DevTri* t = const_cast<DevTri*>(V.tri) + k;
+        DevTri* t = const_cast<DevTri*>(A.tri) + k;          // (this kernel writes the triangles)
         t->rden = t->fast ? rcp_core(t->den) : 0.0;
     }
 }

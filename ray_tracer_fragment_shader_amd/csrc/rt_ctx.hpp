@@ -14,6 +14,10 @@
 //   rt_rays.hip     the ray-list entry points (rt_intersect_kernel, rt_probe_math_kernel)
 //   rt_gather.hip   multi-GPU: gathered row bands -> image order (rt_unshuffle_kernel, rt_unpack_kernel); no context
 //
+// The two records the kernels read — the scene record d_scene and the motion record d_motion — are built on the host
+// (rt_host.cpp rt_build_dev_scene, rt_build_motion) and laid out by rt_layout.hpp alone: every unit above takes their
+// array pointers from its scene_arrays() / motion_arrays() (the kernels through rt_device.hpp view_of).
+//
 // Each member struct of rt_ctx is written by one unit (named beside it); rt_context.hip creates and destroys them all.
 #pragma once
 
@@ -57,7 +61,7 @@ struct rt_ctx {
         std::vector<unsigned char> blob;       // host image of d_scene (rt_set_scene skips an unchanged scene)
         uint64_t gen = 0;
         uint64_t hash = 0;                     // FNV-1a of `blob` (rt_ctx_scene_id)
-        // Motion blur (rt_set_motion, rt_render_motion_dev): the record d_motion (rt_layout.hpp DevMotion) always
+        // Motion blur (rt_set_motion, rt_render_motion_dev): the record d_motion (rt_layout.hpp motion_arrays) always
         // describes the uploaded scene — rt_set_scene builds it with no motion — from the scene-local centres the scene
         // was set with.
         rt::DevMotion* d_motion = nullptr;

@@ -324,16 +324,10 @@ __device__ __forceinline__ d3 unit(d3 a) {
     } while (0)
 #define RT_COUNT_LANES(S, slot) RT_COUNT_BALLOT(S, slot, 1)
 
-struct SceneView {
+// A kernel's view of the scene record: the header it reads, the record's arrays (rt_layout.hpp scene_arrays: sph and
+// prim beside that header, the others — wave-uniform reads — in the global record) and the counts that index them.
+struct SceneView : SceneArrays {
     const DevScene* S;
-    const DevSphere* sph;
-    const DevSpherePrim* prim;
-    const DevSphereF* sphf;
-    const DevSpherePrimF* primf;
-    const DevSphereCone* cone;       // [np] primary-ray cones (per eye)
-    const DevSphereLightF* lightf;   // [nl][np] shadow-ray cone filter
-    const DevMesh* mesh;             // global, wave-uniform reads
-    const DevTri* tri;
     int np;                          // padded sphere count (wave-uniform)
     int ns;                          // stride of the per-sphere arrays (a constant in the fast kernels)
     int nl;                          // light count (wave-uniform)
@@ -350,26 +344,16 @@ __device__ __forceinline__ int hits_ok_from(const DevScene* S, d3 p0) {
     return (S->hits_inside != 0) & (dx * dx + dy * dy + dz * dz <= S->hits_lim2);
 }
 
-// hdr: header copy the kernel reads (LDS or global); g: the global record (for the filter images).  ns: the
-// arrays' stride (DevScene::n_stride; the fast kernels pass the constant kFastStride, so every record address is
-// the scene pointer plus a constant).
+// hdr: header copy the kernel reads (LDS or global); g: the global record; ns: the arrays' stride — scene_arrays'
+// arguments (rt_layout.hpp), which has the layout.
 __device__ __forceinline__ SceneView view_of(const DevScene* hdr, const DevScene* g, int np, int ns, int nl) {
     SceneView v;
+    static_cast<SceneArrays&>(v) = scene_arrays(hdr, g, ns, nl);
     v.S = hdr;
     v.np = np;
     v.ns = ns;
     v.nl = nl;
-    v.sph = reinterpret_cast<const DevSphere*>(hdr + 1);
-    v.prim = reinterpret_cast<const DevSpherePrim*>(v.sph + ns);
-    const DevSphere* gsph = reinterpret_cast<const DevSphere*>(g + 1);
-    const DevSpherePrim* gprim = reinterpret_cast<const DevSpherePrim*>(gsph + ns);
-    v.sphf = reinterpret_cast<const DevSphereF*>(gprim + ns);
-    v.primf = reinterpret_cast<const DevSpherePrimF*>(v.sphf + ns);
-    v.cone = reinterpret_cast<const DevSphereCone*>(v.primf + ns);
-    v.lightf = reinterpret_cast<const DevSphereLightF*>(v.cone + ns);
-    v.mesh = reinterpret_cast<const DevMesh*>(v.lightf + (size_t)nl * ns);
     v.nm = g->n_meshes;
-    v.tri = reinterpret_cast<const DevTri*>(v.mesh + v.nm);
     v.hits_ok = hdr->hits_ok;        // for the camera eye (rt_prepare_kernel); ray lists set it per ray
     return v;
 }
@@ -415,12 +399,12 @@ struct Motion {
 };
 
 __device__ __forceinline__ d3 motion_centre(const Motion& mo, int k) {
-    const DevMotionSphere& ms = reinterpret_cast<const DevMotionSphere*>(mo.M + 1)[k];
+    const DevMotionSphere& ms = motion_arrays(mo.M, mo.M->n_stride).ms[k];
     return add(add(ld3(ms.cl), scl(mo.sigma, ld3(ms.d))), ld3(mo.M->pos));
 }
 
 __device__ __forceinline__ const DevSphereF* motion_filter(const Motion& mo) {
-    return reinterpret_cast<const DevSphereF*>(reinterpret_cast<const DevMotionSphere*>(mo.M + 1) + mo.M->n_stride);
+    return motion_arrays(mo.M, mo.M->n_stride).sphf;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -334,7 +334,17 @@ void rt_camera_basis(const rt_camera* cam, double right[3], double upp[3]) {
     put(upp, u);
 }
 
-int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
+// ---- the scene record and the motion record (rt_layout.hpp): rt_build_dev_scene's steps, in its order ------------------
+namespace {
+
+const double kInf = std::numeric_limits<double>::infinity();
+
+// The builders fill the arrays rt_layout.hpp's layout functions hand out as const.
+template <class T>
+T* writable(const T* p) { return const_cast<T*>(p); }
+
+// The checks on an rt_scene.  n_tris: the triangles its meshes flatten to.
+int check_scene(const rt_scene* s, int* n_tris) {
     if (!s) return rt_fail(RT_EINVAL, "rt_set_scene: null scene");
     if (s->n_spheres < 0 || s->n_spheres > RT_MAX_SPHERES)
         return rt_fail(RT_EINVAL, "rt_set_scene: n_spheres out of range [0, " + std::to_string(RT_MAX_SPHERES) + "]");
@@ -350,66 +360,27 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
         return rt_fail(RT_EUNSUPPORTED, "rt_set_scene: square_edge_size outside [2^-400, 2^400]");
     if (s->n_meshes < 0 || s->n_meshes > RT_MAX_MESHES || (s->n_meshes > 0 && !s->meshes))
         return rt_fail(RT_EINVAL, "rt_set_scene: bad meshes");
-    int n_tris = 0;
+    *n_tris = 0;
     for (int m = 0; m < s->n_meshes; ++m) {
         const rt_mesh& M = s->meshes[m];
         if (M.kind != RT_MESH_TETRAHEDRON && M.kind != RT_MESH_CUBE) return rt_fail(RT_EINVAL, "rt_set_scene: bad mesh kind");
         if (M.after_spheres < 0 || M.after_spheres > s->n_spheres || (m > 0 && M.after_spheres < s->meshes[m - 1].after_spheres))
             return rt_fail(RT_EINVAL, "rt_set_scene: mesh after_spheres must be non-decreasing in [0, n_spheres]");
-        n_tris += M.kind == RT_MESH_TETRAHEDRON ? 4 : 12;
+        *n_tris += M.kind == RT_MESH_TETRAHEDRON ? 4 : 12;
     }
-    const rt_material* mats[5] = {&s->white_square, &s->black_square, &s->sphere_material, &s->tetrahedron_material,
-                                  &s->cube_material};
-    // rayTraceRay (:1230-1247) spawns a transmitted ray when transparency != 0 and |transparency| > eps, a
-    // reflected ray when opacity = 1 - transparency != 0.  A material that does both makes every hit on it
-    // a branch of a ray tree: such scenes run the trace_tree kernels (depth-first, per-lane node stack);
-    // the others follow one continuation per hit.
-    bool used[5] = {true, true, s->n_spheres > 0, false, false};
-    for (int m = 0; m < s->n_meshes; ++m) used[s->meshes[m].kind == RT_MESH_TETRAHEDRON ? 3 : 4] = true;
-    bool any_transparent = false, tree = false;
-    rt::DevMat dm[5];
-    memset(dm, 0, sizeof(dm));
-    for (int m = 0; m < 5; ++m) {
-        const rt_material* M = mats[m];
-        HP T = hp(M->transparency);
-        HP opacity = hp(1.0, 1.0, 1.0) - T;                                     // :1236
-        bool zeroT = T.x == 0 && T.y == 0 && T.z == 0;
-        bool transmit = !zeroT && length(T) > s->small_number;                  // :1238
-        bool reflect = !(opacity.x == 0 && opacity.y == 0 && opacity.z == 0);   // :1243
-        if (used[m] && transmit && reflect) tree = true;
-        if (used[m] && !zeroT) any_transparent = true;
-        for (int q = 0; q < 3; ++q) {
-            dm[m].amb[q] = M->ambient[q];
-            dm[m].diff[q] = M->diffuse[q];
-            dm[m].spec[q] = M->specular[q];
-        }
-        put(dm[m].w, transmit ? T : opacity);
-        put(dm[m].wt, T);
-        put(dm[m].wo, opacity);
-        dm[m].refr = M->refraction;
-        dm[m].transmit = transmit ? 1 : 0;
-        dm[m].transparent = zeroT ? 0 : 1;
-        dm[m].reflect = reflect ? 1 : 0;
-    }
+    return RT_OK;
+}
 
-    // (rounded up to 16 B: kernels may copy the whole record into LDS in 4- or 16-byte words)
-    const size_t bytes = ((size_t)rt::scene_bytes_for(s->n_spheres, s->n_meshes, n_tris, s->n_lights) + 15) & ~(size_t)15;
-    const int np = rt::padded_spheres(s->n_spheres);
-    const int ns = rt::sphere_stride(np);            // array stride (rt_layout.hpp)
-    blob->assign(bytes, 0);
-    rt::DevScene* d = reinterpret_cast<rt::DevScene*>(blob->data());
-    rt::DevSphere* sph = reinterpret_cast<rt::DevSphere*>(d + 1);
-    rt::DevSpherePrim* prim = reinterpret_cast<rt::DevSpherePrim*>(sph + ns);
-    rt::DevSphereF* sphf = reinterpret_cast<rt::DevSphereF*>(prim + ns);
-    (void)prim;                                      // per-eye data: filled on the device (rt_prepare_kernel)
-    d->n_padded = np;
-    d->n_stride = ns;
+// The header's constants: counts, bounding sphere, the reference's constants, lights, and the fields later steps or
+// the device decide at their "not yet" values.  bc: g_scene's _position + offset (:739).
+void put_header(const rt_scene* s, HP bc, int n_tris, rt::DevScene* d) {
+    d->n_spheres = s->n_spheres;
+    d->n_padded = rt::padded_spheres(s->n_spheres);
+    d->n_stride = rt::sphere_stride(d->n_padded);    // array stride (rt_layout.hpp)
     d->lds_bytes = rt::lds_bytes_for(s->n_spheres);
-    const double inf = std::numeric_limits<double>::infinity();
+    d->n_meshes = s->n_meshes;
+    d->n_tris = n_tris;
     d->eye[0] = d->eye[1] = d->eye[2] = std::numeric_limits<double>::quiet_NaN();
-
-    const HP zero = hp(0.0, 0.0, 0.0);
-    const HP bc = hp(s->position) + zero;                                       // g_scene: _position + offset (:739)
     put(d->bc, bc);
     d->br2 = s->radius * s->radius;                                             // :750
     d->bound_on = s->radius > 0;                                                // :747 (g_scene is not _amSphere)
@@ -421,7 +392,86 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
     put(d->coff, bc);                                                           // CheckerBoard's positionOffset
     d->half = s->board_half_size;
     d->square = s->square_edge_size;
+    d->self_eps2 = 0.25 * s->small_number * s->small_number;
+    d->hits_inside = 0;                  // prove_hits_inside, once every object's extent is known
+    d->hits_lim2 = -1.0;
+    d->counters = nullptr;
+    d->hits_ok = 0;                      // per eye, rt_prepare_kernel
+    d->n_lights = s->n_lights;
+    for (int k = 0; k < s->n_lights; ++k) {
+        for (int q = 0; q < 3; ++q) {
+            d->light[k].pos[q] = s->lights[k].position[q];
+            d->light[k].col[q] = s->lights[k].color[q];
+        }
+    }
+}
 
+// The five DevMat records, and the two verdicts that choose the kernel variant.
+void put_materials(const rt_scene* s, rt::DevScene* d) {
+    const rt_material* mats[5] = {&s->white_square, &s->black_square, &s->sphere_material, &s->tetrahedron_material,
+                                  &s->cube_material};
+    // rayTraceRay (:1230-1247) spawns a transmitted ray when transparency != 0 and |transparency| > eps, a
+    // reflected ray when opacity = 1 - transparency != 0.  A material that does both makes every hit on it
+    // a branch of a ray tree: such scenes run the trace_tree kernels (depth-first, per-lane node stack);
+    // the others follow one continuation per hit.
+    bool used[5] = {true, true, s->n_spheres > 0, false, false};
+    for (int m = 0; m < s->n_meshes; ++m) used[s->meshes[m].kind == RT_MESH_TETRAHEDRON ? 3 : 4] = true;
+    bool any_transparent = false, tree = false;
+    for (int m = 0; m < 5; ++m) {
+        const rt_material* M = mats[m];
+        rt::DevMat& dm = d->mat[m];
+        HP T = hp(M->transparency);
+        HP opacity = hp(1.0, 1.0, 1.0) - T;                                     // :1236
+        bool zeroT = T.x == 0 && T.y == 0 && T.z == 0;
+        bool transmit = !zeroT && length(T) > s->small_number;                  // :1238
+        bool reflect = !(opacity.x == 0 && opacity.y == 0 && opacity.z == 0);   // :1243
+        if (used[m] && transmit && reflect) tree = true;
+        if (used[m] && !zeroT) any_transparent = true;
+        for (int q = 0; q < 3; ++q) {
+            dm.amb[q] = M->ambient[q];
+            dm.diff[q] = M->diffuse[q];
+            dm.spec[q] = M->specular[q];
+        }
+        put(dm.w, transmit ? T : opacity);
+        put(dm.wt, T);
+        put(dm.wo, opacity);
+        dm.refr = M->refraction;
+        dm.transmit = transmit ? 1 : 0;
+        dm.transparent = zeroT ? 0 : 1;
+        dm.reflect = reflect ? 1 : 0;
+    }
+    d->transparent = any_transparent ? 1 : 0;
+    d->tree = tree ? 1 : 0;
+}
+
+// The record of Triangle(pos, m, v0, v1, v2) after its ctor (:406-433), world vertex 0 = pos + v0, in *T, whose
+// `degenerate` is left to the caller (the board keeps it 0.0 and decides by the return values of its two triangles;
+// the meshes store it).  Returns whether the ctor found the triangle degenerate: it then never intersects (:633-637).
+bool tri_record(HP pos, HP v0, HP v1, HP v2, double eps, rt::DevTri* T) {
+    HP u = v1 - v0, v = v2 - v0;                                                // :413-414
+    HP n = cross(u, v);                                                         // :415
+    bool degenerate = length(n) < eps;                                          // :418
+    n = normalize(n);                                                           // :422
+    double uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);                     // :424-426
+    double den = uv * uv - uu * vv;                                             // :428
+    if (std::fabs(den) < eps) degenerate = true;                                // :430
+    put(T->v0, pos + v0);                                                       // :640-641
+    put(T->u, u);
+    put(T->v, v);
+    put(T->n, n);
+    T->uv = uv;
+    T->uu = uu;
+    T->vv = vv;
+    T->den = den;
+    // den < 0: A > |den| 2^-1070 proves A/den < 0 (nonzero), so the kernel may skip the division.
+    // Otherwise disable the shortcut.
+    T->thr = (den < 0 && std::fabs(den) >= 1024.0) ? std::ldexp(std::fabs(den), -1070) : kInf;
+    T->fast = const_quotient_ok(den);
+    return degenerate;
+}
+
+// The board: its two triangles, the shared-plane check, and the two shortcuts with their proofs.
+int put_board(const rt_scene* s, HP bc, rt::DevScene* d) {
     d->has_board = 0;
     if (s->has_board) {
         // CheckerBoard(p) -> _boundingSquare = Quad(p, Material(), P1..P4) (:1064-1069) ->
@@ -430,32 +480,10 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
         const HP P[4] = {hp(-h, 0, -h), hp(h, 0, -h), hp(h, 0, h), hp(-h, 0, h)};
         const int idx[2][3] = {{0, 1, 2}, {0, 2, 3}};
         const HP quad_pos = hp(s->board_position) + bc;                         // Quad: _position + offset
-        const HP tri_pos = zero + quad_pos;                                     // Triangle: zero + offset (:640)
+        const HP tri_pos = hp(0.0, 0.0, 0.0) + quad_pos;                        // Triangle: zero + offset (:640)
         bool degenerate[2];
-        for (int t = 0; t < 2; ++t) {
-            HP v0 = P[idx[t][0]], v1 = P[idx[t][1]], v2 = P[idx[t][2]];
-            HP u = v1 - v0, v = v2 - v0;                                        // :413-414
-            HP n = cross(u, v);                                                 // :415
-            degenerate[t] = length(n) < s->small_number;                        // :418
-            n = normalize(n);                                                   // :422
-            double uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);             // :424-426
-            double den = uv * uv - uu * vv;                                     // :428
-            if (std::fabs(den) < s->small_number) degenerate[t] = true;         // :430
-            rt::DevTri& T = d->tri[t];
-            put(T.v0, tri_pos + v0);                                            // :641
-            put(T.u, u);
-            put(T.v, v);
-            put(T.n, n);
-            T.uv = uv;
-            T.uu = uu;
-            T.vv = vv;
-            T.den = den;
-            // den < 0: A > |den| 2^-1070 proves A/den < 0 (nonzero), so the kernel may skip the division.
-            // Otherwise disable the shortcut.
-            T.thr = (den < 0 && std::fabs(den) >= 1024.0) ? std::ldexp(std::fabs(den), -1070)
-                                                          : std::numeric_limits<double>::infinity();
-            T.fast = const_quotient_ok(den);
-        }
+        for (int t = 0; t < 2; ++t)
+            degenerate[t] = tri_record(tri_pos, P[idx[t][0]], P[idx[t][1]], P[idx[t][2]], s->small_number, &d->tri[t]);
         // The kernel shares the plane step of the two triangles; the reference board always satisfies
         // this (same vertex 0, same normal).  A degenerate board never intersects (:633-637).
         if (!degenerate[0] && !degenerate[1]) {
@@ -471,7 +499,6 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
     // starts at a board hit point q has |n . (v0 - q)| <= 2^-50 (3 |p0.y| + 5 |v0.y| + 1), p0 the origin of
     // the ray that hit; below eps^2 / 2 its m = num / nd (|nd| >= eps) is below eps: a certain miss.
     d->board_skip_y = -1.0;
-    d->self_eps2 = 0.25 * s->small_number * s->small_number;
     if (d->has_board && d->tri[0].n[0] == 0.0 && d->tri[0].n[2] == 0.0 && std::fabs(d->tri[0].n[1]) == 1.0 &&
         s->small_number > 0) {
         const double eps2 = s->small_number * s->small_number;
@@ -483,7 +510,7 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
     // integer side L <= 2^12, so uu, uv, vv and den are exact.  Margin delta = L 2^-19, range far = 2^24 L (proof at
     // board_hit).
     d->board_fast = 0;
-    d->board_lo = d->board_hi = d->board_out = inf;
+    d->board_lo = d->board_hi = d->board_out = kInf;
     d->board_far = -1.0;
     if (d->has_board) {
         const rt::DevTri &T1 = d->tri[0], &T2 = d->tri[1];
@@ -503,49 +530,45 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
             d->board_far = std::ldexp(L, 24);
         }
     }
-    for (int m = 0; m < 5; ++m) d->mat[m] = dm[m];
-    d->transparent = any_transparent ? 1 : 0;
-    d->tree = tree ? 1 : 0;
-    d->hits_inside = 0;                  // set below, once every object's extent is known
-    d->hits_lim2 = -1.0;
-    d->counters = nullptr;
-    d->hits_ok = 0;                      // per eye, rt_prepare_kernel
-    d->n_lights = s->n_lights;
-    for (int k = 0; k < s->n_lights; ++k) {
-        for (int q = 0; q < 3; ++q) {
-            d->light[k].pos[q] = s->lights[k].position[q];
-            d->light[k].col[q] = s->lights[k].color[q];
-        }
-    }
-    d->n_spheres = s->n_spheres;
+    return RT_OK;
+}
+
+// FP32 filter image of a sphere (rt_device.hpp sphere_reject32): centre relative to bc, and
+// rm = r2 + 4K sC^2 + K r2 rounded up, sC = max|c_i - bc_i|.  rel: centre - bound centre; r2: the squared radius the
+// filter is to cover (the sphere's own, or its swept sphere's in the motion record).
+rt::DevSphereF filter_record(HP rel, double r2) {
+    const double sC = std::max(std::fabs(rel.x), std::max(std::fabs(rel.y), std::fabs(rel.z)));
+    const double K = (double)rt::kFilterK;
+    const double rm = r2 + 4 * K * sC * sC + K * r2;
+    rt::DevSphereF f;
+    f.cx = (float)rel.x;
+    f.cy = (float)rel.y;
+    f.cz = (float)rel.z;
+    f.rm = (float)rm;
+    if ((double)f.rm < rm) f.rm = std::nextafter(f.rm, std::numeric_limits<float>::infinity());
+    return f;
+}
+
+// The spheres and their filter records, then the padding up to the stride.
+void put_spheres(const rt_scene* s, HP bc, int ns, rt::DevSphere* sph, rt::DevSphereF* sphf) {
     for (int k = 0; k < s->n_spheres; ++k) {
         HP c = hp(s->spheres[k].center) + bc;                                   // sphere: _position + offset
         put(sph[k].c, c);
         sph[k].r2 = s->spheres[k].radius * s->spheres[k].radius;                // :750
-        // FP32 filter image (rt_device.hpp sphere_reject32): centre relative to bc, and
-        // rm = r2 + 4K sC^2 + K r2 rounded up, sC = max|c_i - bc_i|.
-        HP rel = c - bc;
-        double sC = std::max(std::fabs(rel.x), std::max(std::fabs(rel.y), std::fabs(rel.z)));
-        double K = (double)rt::kFilterK;
-        double rm = sph[k].r2 + 4 * K * sC * sC + K * sph[k].r2;
-        sphf[k].cx = (float)rel.x;
-        sphf[k].cy = (float)rel.y;
-        sphf[k].cz = (float)rel.z;
-        float rmf = (float)rm;
-        if ((double)rmf < rm) rmf = std::nextafter(rmf, std::numeric_limits<float>::infinity());
-        sphf[k].rm = rmf;
+        sphf[k] = filter_record(c - bc, sph[k].r2);
     }
     for (int k = s->n_spheres; k < ns; ++k) {                                   // padding: never a hit
-        sph[k].r2 = -inf;
+        sph[k].r2 = -kInf;
         sphf[k].rm = -std::numeric_limits<float>::infinity();
     }
-    // Shadow-ray cone filter (rt_device.hpp occluded): a shadow ray Line(p, L) lies on a line through the
-    // light L, so it can meet sphere k only if |u . v_k| >= cos(phi_k), v_k = unit(C_k - L),
-    // sin(phi_k) = r / |C_k - L|.  Stored: f32(v_k) and c_k = cos(phi_k) - 2^-16 rounded down; a light
-    // inside or near a sphere (|C - L| <= r (1 + 2^-20) or |C - L| <= 2^-14 (1 + |L| + |C|)) gets c = -inf
-    // (always tested), padding spheres c = +inf (never).
-    rt::DevSphereLightF* lightf = reinterpret_cast<rt::DevSphereLightF*>(
-        reinterpret_cast<rt::DevSphereCone*>(reinterpret_cast<rt::DevSpherePrimF*>(sphf + ns) + ns) + ns);
+}
+
+// Shadow-ray cone filter (rt_device.hpp occluded): a shadow ray Line(p, L) lies on a line through the
+// light L, so it can meet sphere k only if |u . v_k| >= cos(phi_k), v_k = unit(C_k - L),
+// sin(phi_k) = r / |C_k - L|.  Stored: f32(v_k) and c_k = cos(phi_k) - 2^-16 rounded down; a light
+// inside or near a sphere (|C - L| <= r (1 + 2^-20) or |C - L| <= 2^-14 (1 + |L| + |C|)) gets c = -inf
+// (always tested), padding spheres c = +inf (never).
+void put_light_cones(const rt_scene* s, int ns, const rt::DevSphere* sph, rt::DevSphereLightF* lightf) {
     for (int i = 0; i < s->n_lights; ++i) {
         const HP L = hp(s->lights[i].position);
         const double aL = std::max(std::fabs(L.x), std::max(std::fabs(L.y), std::fabs(L.z)));
@@ -556,7 +579,7 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
                 f.c = std::numeric_limits<float>::infinity();
                 continue;
             }
-            const HP C = hp(sph[k].c[0], sph[k].c[1], sph[k].c[2]);
+            const HP C = hp(sph[k].c);
             const HP v = C - L;
             const double D = length(v), r = std::fabs(s->spheres[k].radius);
             const double aC = std::max(std::fabs(C.x), std::max(std::fabs(C.y), std::fabs(C.z)));
@@ -574,13 +597,13 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
             f.c = cf;
         }
     }
-    // Meshes (Tetrahedron :863-900, Cube :903-950): Shape(p, m, sqrt(3)*edge/2, false) with Triangle /
-    // Quad sub-objects at zero position.  World vertex 0 of a triangle: tetrahedron (zero + (p + bc)) + v0,
-    // cube (zero + (zero + (p + bc))) + v0 — the chain of `_position + positionOffset` additions (:739, :640).
-    rt::DevMesh* dmesh = reinterpret_cast<rt::DevMesh*>(lightf + (size_t)s->n_lights * ns);
-    rt::DevTri* dtri = reinterpret_cast<rt::DevTri*>(dmesh + s->n_meshes);
-    d->n_meshes = s->n_meshes;
-    d->n_tris = n_tris;
+}
+
+// Meshes (Tetrahedron :863-900, Cube :903-950): Shape(p, m, sqrt(3)*edge/2, false) with Triangle /
+// Quad sub-objects at zero position.  World vertex 0 of a triangle: tetrahedron (zero + (p + bc)) + v0,
+// cube (zero + (zero + (p + bc))) + v0 — the chain of `_position + positionOffset` additions (:739, :640).
+void put_meshes(const rt_scene* s, HP bc, rt::DevMesh* dmesh, rt::DevTri* dtri) {
+    const HP zero = hp(0.0, 0.0, 0.0);
     int t_next = 0;
     for (int m = 0; m < s->n_meshes; ++m) {
         const rt_mesh& M = s->meshes[m];
@@ -622,62 +645,73 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
         }
         for (const auto& tv : tris) {
             rt::DevTri& T = dtri[t_next++];
-            HP u = tv[1] - tv[0], v = tv[2] - tv[0];                            // :413-414
-            HP n = cross(u, v);                                                 // :415
-            bool degenerate = length(n) < s->small_number;                      // :418
-            n = normalize(n);                                                   // :422
-            double uv = dot(u, v), uu = dot(u, u), vv = dot(v, v);             // :424-426
-            double den = uv * uv - uu * vv;                                     // :428
-            if (std::fabs(den) < s->small_number) degenerate = true;            // :430
-            put(T.v0, tpos + tv[0]);                                            // :640-641
-            put(T.u, u);
-            put(T.v, v);
-            put(T.n, n);
-            T.uv = uv;
-            T.uu = uu;
-            T.vv = vv;
-            T.den = den;
-            T.thr = (den < 0 && std::fabs(den) >= 1024.0) ? std::ldexp(std::fabs(den), -1070) : inf;
-            T.fast = const_quotient_ok(den);
-            T.degenerate = degenerate ? 1.0 : 0.0;
+            T.degenerate = tri_record(tpos, tv[0], tv[1], tv[2], s->small_number, &T) ? 1.0 : 0.0;
         }
     }
-    // Rays that start at a hit point pass g_scene's bounding-sphere cull when every hit point lies within
-    // R - 1 of its centre (the kernel's bound_pass shortcut, rt_device.hpp): an upper bound of |q - bc| over
-    // the spheres (|C - bc| + r), the board's corners and the meshes' bounding spheres, with a margin far
-    // above the rounding of the hit points, lets the kernel skip the test for them (hits_inside).
-    if (d->bound_on && d->inner2 > 0) {
-        double far = 0.0;
-        for (int k = 0; k < s->n_spheres; ++k)
-            far = std::max(far, length(hp(sph[k].c[0], sph[k].c[1], sph[k].c[2]) - bc) + std::fabs(s->spheres[k].radius));
-        if (d->has_board) {
-            const double h = s->board_half_size;
-            const HP quad = hp(s->board_position) + bc;
-            for (int cx = -1; cx <= 1; cx += 2)
-                for (int cz = -1; cz <= 1; cz += 2) far = std::max(far, length(quad + hp(cx * h, 0, cz * h) - bc));
-        }
-        for (int m = 0; m < s->n_meshes; ++m)
-            far = std::max(far, length(hp(dmesh[m].bc[0], dmesh[m].bc[1], dmesh[m].bc[2]) - bc) + std::sqrt(dmesh[m].br2));
-        // Hit points carry rounding that grows with their ray's origin o (D = |o - bc|): a sphere hit's
-        // |q - C|^2 = r^2 + err(disc), err(disc) <= 2^-49 D^2 (the sqrt keeps it below 2^-50 D^2 / r in |q - C|),
-        // and p0 + s u or p0 + m d adds <= 2^-51 (D + |bc| + far).  dev(D) = 2^-44 (D + |bc| + far + 1 + D^2 / rmin)
-        // bounds both with room; the shortcut is kept for origins with dev(D) <= slack / 2 (hits_lim2, checked per
-        // ray on the device: the camera eye per render, every start of a ray list), and only when that covers the
-        // hit points themselves (D = R: the origins of later levels).
-        const double Rin = std::sqrt(d->inner2) * (1.0 - 1e-9);
-        const double slack = Rin - far - 1e-6 * (1.0 + far);
-        double rmin = std::numeric_limits<double>::infinity();
-        for (int k = 0; k < s->n_spheres; ++k) rmin = std::min(rmin, std::fabs(s->spheres[k].radius));
-        const double absbc = length(bc);
-        const double e = 0x1p-44, a = rmin > 0 ? e / rmin : inf, c = e * (absbc + far + 1.0) - slack / 2;
-        double dlim = -1.0;                                  // largest D with a D^2 + e D + c <= 0
-        if (std::isfinite(far) && std::isfinite(absbc) && slack > 0 && c < 0)
-            dlim = std::isfinite(a) ? (-e + std::sqrt(e * e - 4 * a * c)) / (2 * a) : -c / e;
-        if (dlim >= Rin) {
-            d->hits_inside = 1;
-            d->hits_lim2 = dlim * dlim * (1.0 - 1e-9);
-        }
+}
+
+// The hits_inside limit.  Hit points carry rounding that grows with their ray's origin o (D = |o - bc|): a sphere hit's
+// |q - C|^2 = r^2 + err(disc), err(disc) <= 2^-49 D^2 (the sqrt keeps it below 2^-50 D^2 / r in |q - C|),
+// and p0 + s u or p0 + m d adds <= 2^-51 (D + |bc| + far).  dev(D) = 2^-44 (D + |bc| + far + 1 + D^2 / rmin)
+// bounds both with room; the shortcut is kept for origins with dev(D) <= slack / 2 (hits_lim2, checked per
+// ray on the device: the camera eye per render, every start of a ray list), and only when that covers the
+// hit points themselves (D = R: the origins of later levels).
+// inner2 > 0: DevScene::inner2; far: an upper bound of |q - bc| over every hit point q; rmin: the smallest sphere
+// radius; absbc: |bc|.  Returns whether the shortcut holds, and then *lim2 = the square of the largest such D.
+bool hits_limit(double inner2, double far, double rmin, double absbc, double* lim2) {
+    const double Rin = std::sqrt(inner2) * (1.0 - 1e-9);
+    const double slack = Rin - far - 1e-6 * (1.0 + far);
+    const double e = 0x1p-44, a = rmin > 0 ? e / rmin : kInf, c = e * (absbc + far + 1.0) - slack / 2;
+    double dlim = -1.0;                                  // largest D with a D^2 + e D + c <= 0
+    if (std::isfinite(far) && std::isfinite(absbc) && slack > 0 && c < 0)
+        dlim = std::isfinite(a) ? (-e + std::sqrt(e * e - 4 * a * c)) / (2 * a) : -c / e;
+    if (!(dlim >= Rin)) return false;
+    *lim2 = dlim * dlim * (1.0 - 1e-9);
+    return true;
+}
+
+// Rays that start at a hit point pass g_scene's bounding-sphere cull when every hit point lies within
+// R - 1 of its centre (the kernel's bound_pass shortcut, rt_device.hpp): an upper bound of |q - bc| over
+// the spheres (|C - bc| + r), the board's corners and the meshes' bounding spheres, with a margin far
+// above the rounding of the hit points (hits_limit), lets the kernel skip the test for them (hits_inside).
+void prove_hits_inside(const rt_scene* s, HP bc, const rt::DevSphere* sph, const rt::DevMesh* dmesh, rt::DevScene* d) {
+    if (!(d->bound_on && d->inner2 > 0)) return;
+    double far = 0.0;
+    for (int k = 0; k < s->n_spheres; ++k)
+        far = std::max(far, length(hp(sph[k].c) - bc) + std::fabs(s->spheres[k].radius));
+    if (d->has_board) {
+        const double h = s->board_half_size;
+        const HP quad = hp(s->board_position) + bc;
+        for (int cx = -1; cx <= 1; cx += 2)
+            for (int cz = -1; cz <= 1; cz += 2) far = std::max(far, length(quad + hp(cx * h, 0, cz * h) - bc));
     }
+    for (int m = 0; m < s->n_meshes; ++m) far = std::max(far, length(hp(dmesh[m].bc) - bc) + std::sqrt(dmesh[m].br2));
+    double rmin = kInf;
+    for (int k = 0; k < s->n_spheres; ++k) rmin = std::min(rmin, std::fabs(s->spheres[k].radius));
+    if (hits_limit(d->inner2, far, rmin, length(bc), &d->hits_lim2)) d->hits_inside = 1;
+}
+
+}  // namespace
+
+int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
+    int n_tris = 0;
+    if (int rc = check_scene(s, &n_tris)) return rc;
+    // (rounded up to 16 B: kernels may copy the whole record into LDS in 4- or 16-byte words)
+    const size_t bytes = ((size_t)rt::scene_bytes_for(s->n_spheres, s->n_meshes, n_tris, s->n_lights) + 15) & ~(size_t)15;
+    blob->assign(bytes, 0);
+    rt::DevScene* d = reinterpret_cast<rt::DevScene*>(blob->data());
+    const HP bc = hp(s->position) + hp(0.0, 0.0, 0.0);                          // g_scene: _position + offset (:739)
+    put_header(s, bc, n_tris, d);
+    // (the header's counts place the arrays; A.prim, A.primf, A.cone: per-eye data, filled on the device by
+    // rt_prepare_kernel)
+    const rt::SceneArrays A = rt::scene_arrays(d);
+    const int ns = d->n_stride;
+    put_materials(s, d);
+    if (int rc = put_board(s, bc, d)) return rc;
+    put_spheres(s, bc, ns, writable(A.sph), writable(A.sphf));
+    put_light_cones(s, ns, A.sph, writable(A.lightf));
+    put_meshes(s, bc, writable(A.mesh), writable(A.tri));
+    prove_hits_inside(s, bc, A.sph, A.mesh, d);
     return RT_OK;
 }
 
@@ -687,9 +721,9 @@ int rt_build_dev_scene(const rt_scene* s, std::vector<unsigned char>* blob) {
 //     rho - r,   rho = (r + |d|) (1 + 2^-30) + 2^-40 max_i(|cl_i| + |d_i| + |bc_i|)
 // of c0: |sigma d| < |d|, and the three roundings of c and the one of c0 move a component by at most
 // 2^-51 (|cl_i| + |d_i| + |bc_i|).  So the sample's sphere lies inside the SWEPT sphere (c0, rho), and
-//  * the FP32 filter record of sphere k is DevSphereF's formula on (c0, rho): the filter rejects a ray only when its
+//  * the FP32 filter record of sphere k is filter_record on (c0, rho): the filter rejects a ray only when its
 //    line misses the swept sphere, by the margin that DESIGN.md 5h turns into "the exact test on c computes disc < 0";
-//  * hits_inside / hits_lim2 are rt_build_dev_scene's proof with every sphere's extent |c0 - bc| + rho: a hit point of
+//  * hits_inside / hits_lim2 are hits_limit's proof with every sphere's extent |c0 - bc| + rho: a hit point of
 //    a sample lies on a sphere inside the swept one.  The other extents (board corners, meshes' bounding spheres) are
 //    read back from the record; the flag is only ever set where the scene's own is.
 int rt_build_motion(const std::vector<unsigned char>& blob, const double* cl, const double* disp, int n,
@@ -697,68 +731,43 @@ int rt_build_motion(const std::vector<unsigned char>& blob, const double* cl, co
     const rt::DevScene* d = reinterpret_cast<const rt::DevScene*>(blob.data());
     if (n != d->n_spheres) return rt_fail(RT_EINVAL, "rt_set_motion: n_spheres is not the uploaded scene's");
     const int ns = d->n_stride;
-    const rt::DevSphere* sph = reinterpret_cast<const rt::DevSphere*>(d + 1);
-    out->assign(sizeof(rt::DevMotion) + (sizeof(rt::DevMotionSphere) + sizeof(rt::DevSphereF)) * (size_t)ns, 0);
+    const rt::SceneArrays A = rt::scene_arrays(d);
+    out->assign(rt::motion_bytes_for(ns), 0);
     rt::DevMotion* M = reinterpret_cast<rt::DevMotion*>(out->data());
-    rt::DevMotionSphere* ms = reinterpret_cast<rt::DevMotionSphere*>(M + 1);
-    rt::DevSphereF* sphf = reinterpret_cast<rt::DevSphereF*>(ms + ns);
+    rt::DevMotionSphere* ms = writable(rt::motion_arrays(M, ns).ms);
+    rt::DevSphereF* sphf = writable(rt::motion_arrays(M, ns).sphf);
     const HP bc = hp(d->bc);
     put(M->pos, bc);
     M->n_stride = ns;
     M->hits_inside = 0;
     M->hits_lim2 = -1.0;
-    const double K = (double)rt::kFilterK, finf = std::numeric_limits<float>::infinity();
-    double far = 0.0, rmin = std::numeric_limits<double>::infinity();
+    double far = 0.0, rmin = kInf;
     for (int k = 0; k < n; ++k) {
         const HP c = hp(cl + 3 * k), dk = disp ? hp(disp + 3 * k) : hp(0.0, 0.0, 0.0);
         put(ms[k].cl, c);
         put(ms[k].d, dk);
-        const double r = std::sqrt(sph[k].r2) * (1.0 + 0x1p-50);                // >= |radius|
+        const double r = std::sqrt(A.sph[k].r2) * (1.0 + 0x1p-50);              // >= |radius|
         const double m = std::max(std::fabs(c.x) + std::fabs(dk.x) + std::fabs(bc.x),
                                   std::max(std::fabs(c.y) + std::fabs(dk.y) + std::fabs(bc.y),
                                            std::fabs(c.z) + std::fabs(dk.z) + std::fabs(bc.z)));
         const double rho = (r + length(dk)) * (1.0 + 0x1p-30) + 0x1p-40 * m;
-        const HP rel = hp(sph[k].c) - bc;
-        const double sC = std::max(std::fabs(rel.x), std::max(std::fabs(rel.y), std::fabs(rel.z)));
-        const double rm = rho * rho + 4 * K * sC * sC + K * rho * rho;
-        sphf[k].cx = (float)rel.x;
-        sphf[k].cy = (float)rel.y;
-        sphf[k].cz = (float)rel.z;
-        float rmf = (float)rm;
-        if ((double)rmf < rm) rmf = std::nextafter(rmf, (float)finf);
-        sphf[k].rm = rmf;
+        const HP rel = hp(A.sph[k].c) - bc;
+        sphf[k] = filter_record(rel, rho * rho);
         far = std::max(far, length(rel) + rho);
-        rmin = std::min(rmin, std::sqrt(sph[k].r2));
+        rmin = std::min(rmin, std::sqrt(A.sph[k].r2));
     }
-    for (int k = n; k < ns; ++k) sphf[k].rm = -(float)finf;                     // padding: never a hit (cl = d = 0)
+    for (int k = n; k < ns; ++k) sphf[k].rm = -std::numeric_limits<float>::infinity();   // padding: never a hit (cl = d = 0)
     if (d->hits_inside && d->bound_on && d->inner2 > 0) {
         if (d->has_board) {
             const HP p1 = hp(d->tri[0].v0);
             const HP corner[4] = {p1, p1 + hp(d->tri[0].u), p1 + hp(d->tri[0].v), p1 + hp(d->tri[1].v)};
             for (const HP& p : corner) far = std::max(far, length(p - bc));
         }
-        const rt::DevMesh* mesh = reinterpret_cast<const rt::DevMesh*>(
-            reinterpret_cast<const rt::DevSphereLightF*>(
-                reinterpret_cast<const rt::DevSphereCone*>(
-                    reinterpret_cast<const rt::DevSpherePrimF*>(
-                        reinterpret_cast<const rt::DevSphereF*>(reinterpret_cast<const rt::DevSpherePrim*>(sph + ns) + ns) +
-                        ns) +
-                    ns) +
-                ns) +
-            (size_t)d->n_lights * ns);
-        for (int m = 0; m < d->n_meshes; ++m) far = std::max(far, length(hp(mesh[m].bc) - bc) + std::sqrt(mesh[m].br2));
-        // (rt_build_dev_scene's bound, with the swept `far`)
-        const double Rin = std::sqrt(d->inner2) * (1.0 - 1e-9);
-        const double slack = Rin - far - 1e-6 * (1.0 + far);
-        const double absbc = length(bc);
-        const double e = 0x1p-44, a = rmin > 0 ? e / rmin : std::numeric_limits<double>::infinity();
-        const double c = e * (absbc + far + 1.0) - slack / 2;
-        double dlim = -1.0;
-        if (std::isfinite(far) && std::isfinite(absbc) && slack > 0 && c < 0)
-            dlim = std::isfinite(a) ? (-e + std::sqrt(e * e - 4 * a * c)) / (2 * a) : -c / e;
-        if (dlim >= Rin) {
+        for (int m = 0; m < d->n_meshes; ++m) far = std::max(far, length(hp(A.mesh[m].bc) - bc) + std::sqrt(A.mesh[m].br2));
+        double lim2;
+        if (hits_limit(d->inner2, far, rmin, length(bc), &lim2)) {
             M->hits_inside = 1;
-            M->hits_lim2 = std::min(d->hits_lim2, dlim * dlim * (1.0 - 1e-9));
+            M->hits_lim2 = std::min(d->hits_lim2, lim2);
         }
     }
     return RT_OK;
@@ -807,7 +816,7 @@ extern "C" int rt_diag_sky_tiles(const rt_scene* scene, const rt_camera* cam, in
     const int np = d->n_padded;
     // the instances that take the early-out: opaque, mesh-free scenes whose cone mask covers every sphere
     if (d->tree || d->transparent || d->n_meshes > 0 || np < rt::kPrimaryConeMin || np > 64) return RT_OK;
-    const rt::DevSphere* sph = reinterpret_cast<const rt::DevSphere*>(d + 1);
+    const rt::DevSphere* sph = rt::scene_arrays(d).sph;
     const double* eye = cam->eye;
     rt::DevSphereCone cone[64];
     for (int k = 0; k < np; ++k) {

@@ -1,15 +1,18 @@
-// rt_layout.hpp — the device scene record (plain C++, shared by the host builder and the kernels).
+// rt_layout.hpp — the device scene record and the motion record (plain C++, shared by the host builder and the
+// kernels).  This comment is the one description of both layouts; scene_arrays() and motion_arrays() below are their one
+// statement in code, and every reader and writer of a record takes its array pointers from them.
 //
-// Layout in HBM (one allocation per rt_ctx):
+// The scene record in HBM (one allocation per rt_ctx), in the order scene_arrays() walks it:
 //   DevScene header
 //   DevSphere[ns]       FP64 exact data                 ┐ copied into LDS once per workgroup
-//   DevSpherePrim[ns]   primary-ray FP64 data (per eye)  ┘ (lds_bytes)
+//   DevSpherePrim[ns]   primary-ray FP64 data (per eye)  ┘ (lds_bytes_for)
 //   DevSphereF[ns]      FP32 filter image               ┐ read through the scalar cache (SGPR operands),
 //   DevSpherePrimF[ns]  primary-ray FP32 filter (per eye)│ one batch of kChunk records per s_load group
 //   DevSphereCone[ns]   primary-ray cone of each sphere (per eye): per-wave culling
 //   DevSphereLightF[nl][ns]  shadow-ray FP32 cone filter ┘ per light (line through the light)
 //   DevMesh[nm]         tetrahedra / cubes: bounding sphere, triangle range, material, child index
 //   DevTri[nt]          their triangles (world vertex 0, u, v, n, uv, uu, vv, den)
+// and scene_bytes_for() bytes in all (the allocation rounds that up to 16).
 // np = n_spheres rounded up to kChunk; the padding spheres have r2 = -inf and filter terms = -inf, so
 // they are rejected by the filter and can never hit.  ns = the arrays' stride: np, except for scenes the fast
 // (non-culling) kernels render (np < kConeMin), whose arrays all have the fixed stride kFastStride — those kernels
@@ -17,9 +20,23 @@
 // in SGPRs (the SGPR budget of a seventh wave per SIMD).  The two *Prim arrays and DevSphereCone depend on
 // the camera eye and are (re)written on the device by rt_prepare_kernel whenever rt_render_dev sees a
 // new eye, as are the header's per-eye fields (board_num, edge, hits_ok, prim_bound_ok).
+//
+// The motion record (rt_set_motion; an allocation of its own beside the scene record), as motion_arrays() walks it:
+//   DevMotion header
+//   DevMotionSphere[ns] scene-local centre and half-extent of the motion of each sphere
+//   DevSphereF[ns]      FP32 filter image of each sphere's SWEPT sphere
+// with the scene record's stride ns, motion_bytes_for(ns) bytes in all.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
+
+// Functions the kernels and the host share: plain C++ under a host compiler, __host__ __device__ under hipcc.
+#ifdef __HIP__
+#define RT_HD __host__ __device__ __forceinline__
+#else
+#define RT_HD inline
+#endif
 
 namespace rt {
 
@@ -161,9 +178,9 @@ struct alignas(16) DevScene {
     DevBoardEdge edge[4];              // per eye: the board's four edges seen from the camera `eye` (rt_prepare_kernel)
 };
 
-// The motion record of a context (rt_set_motion, rt_render_motion_dev): an allocation of its own beside the scene
-// record, which stays as it is.  DevMotion header, DevMotionSphere[ns], then DevSphereF[ns]: the FP32 filter image of
-// each sphere's SWEPT sphere (every position it takes during the exposure), with the scene record's stride ns.
+// The motion record of a context (rt_set_motion, rt_render_motion_dev; layout at the top): the scene record stays as
+// it is.  The DevSphereF array is the FP32 filter image of each sphere's SWEPT sphere (every position it takes during
+// the exposure).
 struct alignas(16) DevMotionSphere {   // sample centre = (cl + sigma * d) + DevMotion::pos, one IEEE operation each
     double cl[3];                      // scene-local centre (rt_sphere::center)
     double pad0;
@@ -181,6 +198,58 @@ struct alignas(16) DevMotion {
 
 inline constexpr int padded_spheres(int n) { return (n + kChunk - 1) / kChunk * kChunk; }
 
+// The eight arrays of a scene record.  hdr: the copy the first two arrays are read from (LDS in the render kernels,
+// else the record itself); g: the global record the others are read from, whose n_meshes must be set.  ns: the arrays'
+// stride (DevScene::n_stride; the fast kernels pass the constant kFastStride, so every record address is the scene
+// pointer plus a constant), nl: DevScene::n_lights.  A chain of typed pointers on purpose, and n_meshes read here, after
+// the other seven, and not passed in: stated as byte offsets from the base, or with that load moved in front of the
+// chain, some kernels compile to other code (the same instructions in another order, with other registers).
+// The writers of a record (the host builder, rt_scene_init_kernel, rt_prepare_kernel) cast the constness of the arrays
+// they fill away.
+struct SceneArrays {
+    const DevSphere* sph;
+    const DevSpherePrim* prim;
+    const DevSphereF* sphf;
+    const DevSpherePrimF* primf;
+    const DevSphereCone* cone;       // [ns] primary-ray cones (per eye)
+    const DevSphereLightF* lightf;   // [nl][ns] shadow-ray cone filter
+    const DevMesh* mesh;
+    const DevTri* tri;
+};
+
+RT_HD SceneArrays scene_arrays(const DevScene* hdr, const DevScene* g, int ns, int nl) {
+    SceneArrays a;
+    a.sph = reinterpret_cast<const DevSphere*>(hdr + 1);
+    a.prim = reinterpret_cast<const DevSpherePrim*>(a.sph + ns);
+    const DevSphere* gsph = reinterpret_cast<const DevSphere*>(g + 1);
+    const DevSpherePrim* gprim = reinterpret_cast<const DevSpherePrim*>(gsph + ns);
+    a.sphf = reinterpret_cast<const DevSphereF*>(gprim + ns);
+    a.primf = reinterpret_cast<const DevSpherePrimF*>(a.sphf + ns);
+    a.cone = reinterpret_cast<const DevSphereCone*>(a.primf + ns);
+    a.lightf = reinterpret_cast<const DevSphereLightF*>(a.cone + ns);
+    a.mesh = reinterpret_cast<const DevMesh*>(a.lightf + (size_t)nl * ns);
+    a.tri = reinterpret_cast<const DevTri*>(a.mesh + g->n_meshes);
+    return a;
+}
+
+// The arrays of a record read in place, with the counts of its own header.
+RT_HD SceneArrays scene_arrays(const DevScene* g) { return scene_arrays(g, g, g->n_stride, g->n_lights); }
+
+// The two arrays of a motion record built for the stride ns (DevMotion::n_stride).
+struct MotionArrays {
+    const DevMotionSphere* ms;
+    const DevSphereF* sphf;
+};
+
+RT_HD MotionArrays motion_arrays(const DevMotion* M, int ns) {
+    MotionArrays a;
+    a.ms = reinterpret_cast<const DevMotionSphere*>(M + 1);
+    a.sphf = reinterpret_cast<const DevSphereF*>(a.ms + ns);
+    return a;
+}
+
+// The sizes scene_arrays() and motion_arrays() imply, as constants (the kernels' LDS and the frame slots are sized at
+// compile time); tests/sanitize/san_main.cpp checks them against the two functions.
 inline constexpr int lds_bytes_for(int n) {
     return (int)(sizeof(DevScene) +
                  (sizeof(DevSphere) + sizeof(DevSpherePrim)) * (unsigned)sphere_stride(padded_spheres(n)));
@@ -192,6 +261,10 @@ inline constexpr int scene_bytes_for(int n, int n_meshes = 0, int n_tris = 0, in
                   sizeof(DevSphereLightF) * (unsigned)n_lights) *
                  (unsigned)sphere_stride(padded_spheres(n))) +
            (int)(sizeof(DevMesh) * (unsigned)n_meshes + sizeof(DevTri) * (unsigned)n_tris);
+}
+
+inline constexpr size_t motion_bytes_for(int ns) {
+    return sizeof(DevMotion) + (sizeof(DevMotionSphere) + sizeof(DevSphereF)) * (size_t)ns;
 }
 
 }  // namespace rt

@@ -145,12 +145,12 @@ __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restr
 // r2 = -inf, hence c0 = -inf: always rejected.
 __global__ __launch_bounds__(kThreads) void rt_prepare_kernel(DevScene* __restrict__ g, double ex, double ey,
                                                               double ez) {
-    const int np = g->n_padded, ns = g->n_stride;
-    DevSphere* sph = reinterpret_cast<DevSphere*>(g + 1);
-    DevSpherePrim* prim = reinterpret_cast<DevSpherePrim*>(sph + ns);
-    DevSphereF* sphf = reinterpret_cast<DevSphereF*>(prim + ns);
-    DevSpherePrimF* primf = reinterpret_cast<DevSpherePrimF*>(sphf + ns);
-    DevSphereCone* cone = reinterpret_cast<DevSphereCone*>(primf + ns);
+    const int np = g->n_padded;
+    const SceneArrays A = scene_arrays(g);
+    const DevSphere* sph = A.sph;
+    DevSpherePrim* prim = const_cast<DevSpherePrim*>(A.prim);      // the three per-eye arrays this kernel writes
+    DevSpherePrimF* primf = const_cast<DevSpherePrimF*>(A.primf);
+    DevSphereCone* cone = const_cast<DevSphereCone*>(A.cone);
     const d3 eye = mk(ex, ey, ez);
     const int k = blockIdx.x * kThreads + threadIdx.x;
     if (k == 0) {

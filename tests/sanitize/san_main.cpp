@@ -10,6 +10,7 @@
 
 #include "../../include/rt_api.h"
 #include "../../ray_tracer_fragment_shader_amd/csrc/rt_internal.hpp"
+#include "../../ray_tracer_fragment_shader_amd/csrc/rt_layout.hpp"
 
 extern "C" {
 int oracle_local_rows(int H, const rt_rows* r);
@@ -211,7 +212,119 @@ static void check_screen() {
     rt_ctx_destroy(ctx);
 }
 
-int main() {
+// The scene record and the motion record (csrc/rt_layout.hpp): their layout functions against the constexpr sizes, and
+// both records byte for byte (rt_blob_fingerprint) against the values below.  Those were recorded by compiling this
+// file against the csrc of commit 539ffc4 — the last one whose builders laid the records out by hand — with
+// -DSAN_RECORDS_ONLY (that csrc has no layout functions) and running it with --print-records, which prints the table
+// instead of comparing.
+static const uint64_t kRecords[][5] = {
+    // scene, then its motion record for: no displacement, one mover, every sphere moving, a mover that leaves the bound
+    {0xd2510a24db421f7cull, 0x4fc3bdab18b97be9ull, 0x3d022a6a393a168eull, 0xf97a747c3e93cf9full, 0xa85ec8bef1f9268bull},
+    {0xb6551fdda6d6c2b4ull, 0x5ff6744ce4b22ad0ull, 0x5ff6744ce4b22ad0ull, 0x5ff6744ce4b22ad0ull, 0x5ff6744ce4b22ad0ull},
+    {0xef209234d048534aull, 0x8397ef81c7dc92adull, 0xfd28925ffe0a3510ull, 0x41f308ff194e7ca9ull, 0x6dffabc974a377f4ull},
+    {0x3ab7519bc97e1f9bull, 0xdc0478c1591b8acdull, 0xa1d03c008bc31db8ull, 0x13f41a61d9515b01ull, 0xba8f3503b1bf9660ull},
+    {0xec8d7668027209c1ull, 0x3bd12cfa37368505ull, 0xbae2c24ce8fa1fd1ull, 0xc209ceea3fca46c4ull, 0xf1b16d33d691e2d6ull},
+};
+
+static void grid_scene(rt_scene* s, std::vector<rt_sphere>* sph, int n, std::vector<rt_light>* lts, int nl,
+                       std::vector<rt_mesh>* msh, int nm) {
+    CHECK(rt_scene_init_reference(s) == RT_OK);
+    sph->assign(n > 0 ? n : 1, rt_sphere{});
+    for (int k = 0; k < n; ++k) {
+        (*sph)[k].center[0] = (k % 32) * 9 - 140;
+        (*sph)[k].center[1] = 8 + (k / 32) % 4;
+        (*sph)[k].center[2] = (k / 32) * 8 - 120;
+        (*sph)[k].radius = 2 + k % 3;
+    }
+    lts->assign(nl > 0 ? nl : 1, rt_light{});
+    for (int k = 0; k < nl; ++k) {
+        const double pos[3] = {k * 20 - 150.0, 150.0, 40.0 - k * 10}, col[3] = {1.0, 0.5 + 0.03125 * k, 0.25};
+        std::memcpy((*lts)[k].position, pos, sizeof(pos));
+        std::memcpy((*lts)[k].color, col, sizeof(col));
+    }
+    msh->assign(nm > 0 ? nm : 1, rt_mesh{});
+    for (int k = 0; k < nm; ++k) {                          // a tetrahedron, a cube, ... in the middle of the child list
+        rt_mesh& M = (*msh)[k];
+        M.kind = k % 2 ? RT_MESH_CUBE : RT_MESH_TETRAHEDRON;
+        M.after_spheres = n < 2 * k + 1 ? n : 2 * k + 1;
+        M.position[0] = 120.0 * k - 60;
+        M.position[2] = -100.0 * (k + 1);
+        M.edge = 40;
+    }
+    s->spheres = sph->data();
+    s->n_spheres = n;
+    s->lights = lts->data();
+    s->n_lights = nl;
+    s->meshes = msh->data();
+    s->n_meshes = nm;
+}
+
+static void check_records(bool print) {
+    // spheres (stride 12, 64, np), lights, meshes, board, a sphere outside the bound (no hits_inside)
+    const int shapes[][5] = {{5, 1, 0, 1, 0}, {0, 0, 0, 0, 0}, {17, 2, 2, 1, 0}, {68, 2, 2, 1, 0}, {13, 16, 1, 1, 1}};
+    const int n_shapes = (int)(sizeof(shapes) / sizeof(shapes[0]));
+    CHECK(print || n_shapes == (int)(sizeof(kRecords) / sizeof(kRecords[0])));
+    for (int i = 0; i < n_shapes; ++i) {
+        const int n = shapes[i][0], nl = shapes[i][1], nm = shapes[i][2];
+        rt_scene s;
+        std::vector<rt_sphere> sph;
+        std::vector<rt_light> lts;
+        std::vector<rt_mesh> msh;
+        grid_scene(&s, &sph, n, &lts, nl, &msh, nm);
+        s.has_board = shapes[i][3];
+        if (shapes[i][4]) sph[n - 1].center[0] = 400;
+        std::vector<unsigned char> blob;
+        CHECK(rt_build_dev_scene(&s, &blob) == RT_OK);
+        uint64_t got[5] = {rt_blob_fingerprint(blob), 0, 0, 0, 0};
+        const rt::DevScene* d = reinterpret_cast<const rt::DevScene*>(blob.data());
+        const int ns = d->n_stride;
+#ifndef SAN_RECORDS_ONLY
+        const rt::SceneArrays A = rt::scene_arrays(d);
+        const size_t end = (size_t)(reinterpret_cast<const unsigned char*>(A.tri + d->n_tris) - blob.data());
+        CHECK(d->n_meshes == nm && d->n_lights == nl && ns == rt::sphere_stride(rt::padded_spheres(n)));
+        CHECK(end == (size_t)rt::scene_bytes_for(n, nm, d->n_tris, nl));
+        CHECK(((end + 15) & ~(size_t)15) == blob.size());
+        CHECK(reinterpret_cast<const unsigned char*>(A.sphf) - blob.data() == rt::lds_bytes_for(n));
+        CHECK(d->lds_bytes == rt::lds_bytes_for(n));
+#endif
+        std::vector<double> cl(3 * (size_t)n + 1), disp(3 * (size_t)n + 1);
+        for (int k = 0; k < n; ++k) std::memcpy(&cl[3 * k], sph[k].center, 3 * sizeof(double));
+        for (int mode = 0; mode < 4; ++mode) {
+            std::fill(disp.begin(), disp.end(), 0.0);
+            for (int k = 0; k < n; ++k) {
+                if (mode == 1 && k == n / 2) disp[3 * k + 1] = 3.5;
+                if (mode == 2) disp[3 * k] = 0.25 * (k % 5), disp[3 * k + 2] = -0.5 * (k % 3);
+                if (mode == 3 && k == 0) disp[3 * k] = -300;
+            }
+            std::vector<unsigned char> rec;
+            CHECK(rt_build_motion(blob, cl.data(), mode ? disp.data() : nullptr, n, &rec) == RT_OK);
+            got[1 + mode] = rt_blob_fingerprint(rec);
+            CHECK(rec.size() == sizeof(rt::DevMotion) + (sizeof(rt::DevMotionSphere) + sizeof(rt::DevSphereF)) * (size_t)ns);
+#ifndef SAN_RECORDS_ONLY
+            const rt::DevMotion* M = reinterpret_cast<const rt::DevMotion*>(rec.data());
+            const rt::MotionArrays MA = rt::motion_arrays(M, M->n_stride);
+            CHECK(M->n_stride == ns && rec.size() == rt::motion_bytes_for(ns));
+            CHECK(reinterpret_cast<const unsigned char*>(MA.ms) == rec.data() + sizeof(rt::DevMotion));
+            CHECK(reinterpret_cast<const unsigned char*>(MA.sphf + ns) == rec.data() + rec.size());
+#endif
+        }
+        std::vector<unsigned char> none;
+        CHECK(rt_build_motion(blob, cl.data(), nullptr, n + 1, &none) == RT_EINVAL);
+        if (print)
+            std::printf("    {0x%016llxull, 0x%016llxull, 0x%016llxull, 0x%016llxull, 0x%016llxull},\n",
+                        (unsigned long long)got[0], (unsigned long long)got[1], (unsigned long long)got[2],
+                        (unsigned long long)got[3], (unsigned long long)got[4]);
+        else
+            for (int q = 0; q < 5; ++q) CHECK(got[q] == kRecords[i][q]);
+    }
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "--print-records") {
+        check_records(true);
+        return g_fail ? 1 : 0;
+    }
+    check_records(false);
     check_bands();
     check_squares_and_scenes();
     check_ppm();
