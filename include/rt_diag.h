@@ -56,7 +56,7 @@ int rt_diag_kernel_occupancy(int depth, int variant, int lds_bytes, int* blocks_
  * wg_staging: RT_WG_STAGING, min_waves: RT_MIN_WAVES, 5 by default, achro_off: RT_ACHRO_OFF), the depth (0..7), the
  * output mode (0 RGBA images, 1 packed GRAY / RGB formats, 2 supersampled) and level_mask (1: not the frame itself but
  * the launch that writes a fast scene's level masks behind its calibration render).  out[0..10]: the instance's
- * kernel template (0 rt_render_kernel, 1 rt_render_kernel_sg, 2 rt_render_kernel_sg8) and its template arguments
+ * kernel template (0 rt_render_kernel, 1 rt_render_kernel_sg) and its template arguments
  * LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS; out[11] the launch's dynamic LDS bytes; out[12] the tile
  * width in pixels.  RT_EINVAL for bad arguments, and (out written) when the build has no such instance. */
 int rt_diag_render_route(int tree, int transparent, int n_padded, int n_stride, int achromatic, int lds_bytes,

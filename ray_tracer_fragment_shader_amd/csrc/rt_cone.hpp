@@ -11,7 +11,7 @@
 
 #include "rt_layout.hpp"
 
-// FP32 square root and reciprocal of the wave-culling tests (RT_FAST_MASK = 1): the hardware instructions
+// FP32 square root and reciprocal of the wave-culling tests: on the device the hardware instructions
 // (v_sqrt_f32, v_rcp_f32, 1 ulp: relative error < 2^-22 on normal operands) instead of the correctly rounded
 // sequences (scaling, Newton and fixup steps around them: ~10 instructions each).  The culling tests only need
 // conservative bounds, and their margins (R inflated by 2^-12 relative, chord limits by 2^-14 absolute, shadow
@@ -19,28 +19,25 @@
 // their meaning (sqrt(0) = 0, rcp(+inf) = 0, NaN propagates and fails the `>` compares, i.e. keeps the sphere).
 // The host evaluates the correctly rounded forms: its verdicts are sound for the same reason, and equal the
 // device's except where a test lands within that error of its threshold.
-#ifndef RT_FAST_MASK
-#define RT_FAST_MASK 1                         // same-box A/B: c5 -5.7%, c2/c3 +-1%
-#endif
 
 namespace rt {
 
 RT_HD float msqrt(float x) {
-#if defined(__HIP_DEVICE_COMPILE__) && RT_FAST_MASK
+#ifdef __HIP_DEVICE_COMPILE__
     return __builtin_amdgcn_sqrtf(x);
 #else
     return sqrtf(x);
 #endif
 }
 RT_HD float mrcp(float x) {
-#if defined(__HIP_DEVICE_COMPILE__) && RT_FAST_MASK
+#ifdef __HIP_DEVICE_COMPILE__
     return __builtin_amdgcn_rcpf(x);
 #else
     return 1.0f / x;
 #endif
 }
 RT_HD float mdiv(float a, float b) {
-#if defined(__HIP_DEVICE_COMPILE__) && RT_FAST_MASK
+#ifdef __HIP_DEVICE_COMPILE__
     return a * __builtin_amdgcn_rcpf(b);
 #else
     return a / b;

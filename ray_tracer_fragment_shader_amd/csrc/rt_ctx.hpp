@@ -37,9 +37,6 @@ struct RenderParams;
 }  // namespace rtk
 
 constexpr int kOrderMax = 8192;                // tile rows rt_order_kernel sorts (one workgroup, keys in LDS)
-#ifndef RT_CONE_CACHE_DEFAULT
-#define RT_CONE_CACHE_DEFAULT 1
-#endif
 constexpr int kRecalibrate = 8;                // renders of a moving camera per re-timing of the tile rows
 
 struct rt_ctx {
@@ -73,7 +70,7 @@ struct rt_ctx {
     // The A/B knobs rt_ctx_create reads from the environment (rt_context.hip knobs_from_env; the measurements behind a
     // default stand where the knob is read).  Only order_mode changes later (rt_diag_tile_order).
     struct Knobs {
-        int min_waves = 5;                     // >= 5: the RT_MINW / RT_MINW_CULL launch bounds for depth <= 3 (measured faster
+        int min_waves = 5;                     // >= 5: the launch bounds of depth <= 3, fast_min_waves / cull_min_waves (faster
                                                // than no bound: tools/ab.py); RT_MIN_WAVES=0 disables
         int use_lds = 0;                       // RT_SCENE_IN_LDS=1: header + exact records in LDS (A/B: tools/ab.py)
         int wg_staging = 0;                    // RT_WG_STAGING=1: LDS-staged 32-pixel row stores (A/B)
@@ -87,7 +84,7 @@ struct rt_ctx {
         int order_mode = 0;                    // RT_TILE_ORDER, rt_diag_tile_order: 0 adaptive, 1 bottom-to-top
         int moving_order = 0;                  // RT_MOVING_ORDER=1: a moving camera keeps the last calibrated order ...
         int recalibrate = kRecalibrate;        // ... re-timed every RT_RECALIBRATE-th render (rt_plain.hip render_plan_view)
-        int cone_cache = RT_CONE_CACHE_DEFAULT;    // RT_CONE_CACHE=0: always compute the masks in the kernel (A/B)
+        int cone_cache = 1;                    // RT_CONE_CACHE=0: always compute the masks in the kernel (A/B)
         bool level_masks = true;               // RT_LEVEL_MASKS=0: the level masks computed in every render
         // Sky tiles (rt_render.hpp render_body): waves whose primary rays provably all miss store the miss constants
         // without tracing.  RT_SKY_TILES=0: every wave traces (A/B; the images are the same bytes).

@@ -37,86 +37,13 @@
 #include "rt_cone.hpp"
 #include "rt_layout.hpp"
 
-// 1 (r06): the exact sqrt / quotient fast paths run unconditionally and their rare slow paths sit behind one
-// wave-uniform ballot branch (sqrt_fast, div_const, unit) instead of an exec-mask region per call site — fewer
-// scalar-stream instructions (in-process A/B c2 -4.5%, c3 -3.9%, c5 -5.5%, profiles/r06/ab; r02 measured +-0.8%).
-#ifndef RT_FAST_FALLBACK
-#define RT_FAST_FALLBACK 1
-#endif
-// 1: the exact tests of a filter batch visit its spheres in a loop the whole wave runs (record index
-// wave-uniform: scalar loads, SGPR operands; lanes whose filter rejected a sphere are masked off);
-// 0: each lane walks its own surviving spheres (per-lane index: vector loads).
-#ifndef RT_UNIFORM_PRIMARY
-#define RT_UNIFORM_PRIMARY 1
-#endif
-#ifndef RT_UNIFORM_SECONDARY
-#define RT_UNIFORM_SECONDARY 1
-#endif
-#ifndef RT_UNIFORM_SHADOW
-#define RT_UNIFORM_SHADOW 0
-#endif
-// 1: the fast (non-CULL) bounce loop keeps the continuation's unit direction live through the light loop;
-// 0: it is recomputed after it (fewer live registers).
-#ifndef RT_KEEP_NU
-#define RT_KEEP_NU 0
-#endif
-// 1: the fast loop also parks the continuation's unit direction (computed before the light loop) in the
-// next level's LDS slot instead of recomputing it after the light loop (RT_KEEP_NU without the registers).
-#ifndef RT_PARK_NU
-#define RT_PARK_NU 1
-#endif
-// The same for the CULL variant's levels (and its end - start, in this level's slot).
-#ifndef RT_PARK_NU_CULL
-#define RT_PARK_NU_CULL 1
-#endif
-// The fast loop parks the continuation's end - start in the level's (still empty) LDS colour slot while
-// the light loop runs (fewer live registers) and reloads it for the next ray: at depth >= RT_PARK_ND_MIN_B.
-#ifndef RT_PARK_ND_MIN_B
-#define RT_PARK_ND_MIN_B RT_SKIP_FAST_MIN_B
-#endif
-// 1: rays that start at a hit point skip the bounding-sphere cull when the host proved every hit point
-// lies inside its shortcut radius (DevScene::hits_inside).
-#ifndef RT_HITS_INSIDE
-#define RT_HITS_INSIDE 1
-#endif
-// 1: the bounce loop of trace() is unrolled (one copy of the level code per level); 0: a loop (one copy).
-#ifndef RT_UNROLL_LEVELS
-#define RT_UNROLL_LEVELS 1
-#endif
-// A/B only: 0 reads the per-eye flag from the scene header at each use (wrong for ray lists)
-#ifndef RT_HITS_VIEW
-#define RT_HITS_VIEW 1
-#endif
-// 1: rays that start at a board hit skip the board test, rays that start at a sphere hit that sphere's test
-// (certain misses, origin_skip).
-#ifndef RT_BOARD_SKIP
-#define RT_BOARD_SKIP 1
-#endif
-#ifndef RT_SELF_SKIP
-#define RT_SELF_SKIP 1
-#endif
-// The skips in the fast (non-CULL) bounce loop from this depth on (they always run in the CULL variant).
-// There they come with the continuation parked in LDS across the light loop (RT_PARK_ND): without it the
+// The origin skips (origin_skip: rays that start at a board hit skip the board test, rays that start at a sphere hit
+// skip that sphere's test — certain misses) run in the fast (non-CULL) bounce loop from this depth on; they always run
+// in the CULL variant.  There they come with the continuation parked in LDS across the light loop: without it the
 // extra live state spilled 12 B/lane at 6 waves/SIMD (c2 HBM writes 1.01x -> 1.22x); with it no spills,
 // c3 (depth 2) -1.2 to -1.9%, c2 (depth 1) +0.7 to +1.1% (r02, in-process A/B) — hence depth >= 2 until r04.  The
 // 7-wave depth-1 kernel (94 SGPRs, 65 VGPRs, no scratch) gains from them: c2 -1.9% serial, -0.5% with 3 frames
 // in flight (r04, in-process A/B; the skips alone -1.4%, the parking alone +0.8%) — hence depth >= 1.
-// 1: closest-hit distances are computed only when two candidates meet (take_closer).
-#ifndef RT_LAZY_DIST
-#define RT_LAZY_DIST 1
-#endif
-// 1: primary rays that hit an object skip the bounding-sphere cull when the eye's per-eye flag proves they pass it.
-#ifndef RT_PRIM_BOUND_SKIP
-#define RT_PRIM_BOUND_SKIP 1
-#endif
-// 1: the reference's board is decided by the hit point's position in its square where that is certain (board_hit).
-#ifndef RT_BOARD_POS
-#define RT_BOARD_POS 1
-#endif
-// 1: primary rays of waves whose cone mask keeps no sphere normalise their direction only where they hit the board.
-#ifndef RT_LAZY_PRIMARY_U
-#define RT_LAZY_PRIMARY_U 1
-#endif
 #ifndef RT_SKIP_FAST_MIN_B
 #define RT_SKIP_FAST_MIN_B 1
 #endif
@@ -186,8 +113,9 @@ __device__ __forceinline__ double sqrt_core(double x) {
 }
 
 // The range checks are evaluated without short-circuits (& and | on bools: compares combined in SGPR
-// masks, no exec-mask branches), and the rare fallback is one wave-uniform branch taken only when some lane
-// needs it (RT_FAST_FALLBACK).
+// masks, no exec-mask branches).  The fast paths run unconditionally and their rare slow paths sit behind one
+// wave-uniform ballot branch, taken only when some lane needs it (sqrt_fast, div_const, unit), instead of an
+// exec-mask region per call site: fewer scalar-stream instructions.
 __device__ __forceinline__ bool sqrt_fast_ok(double x) { return (x >= 0x1p-700) & (x <= 0x1p+700); }
 
 // True when some active lane of the wave has `bad` set (the fast paths' fallback branch).
@@ -215,33 +143,20 @@ __device__ __forceinline__ bool num_fast_ok(double a) { return (a == 0.0) | (fab
 // and div_core is the IEEE quotient bit for bit (fast paths above); other operands (zero, tiny, huge,
 // NaN) take the compiler's division.
 __device__ __forceinline__ double div_const(double a, double b, double r, int32_t fast) {
-#if RT_FAST_FALLBACK
     const double aa = fabs(a);
     const bool ok = (fast != 0) & (aa >= 0x1p-500) & (aa <= 0x1p+500);
     double q = div_core(a, b, r);
     if (any_lane(!ok)) q = ok ? q : a / b;
     return q;
-#else
-    const double aa = fabs(a);
-    if (fast && aa >= 0x1p-500 && aa <= 0x1p+500) return div_core(a, b, r);
-    return a / b;
-#endif
 }
 
 // The compiler's IEEE sqrt sequence on gfx950, restated op for op (same bits for every input): x below 2^-767
 // is scaled by 2^256, sqrt_core, the result scaled by 2^-128, and +-0 / +inf return the (scaled) input.  Its
 // constants (256, -128, the class mask) come from opaque SGPR moves: the compiler's own expansion hoisted them
 // out of the bounce loop into three VGPRs held across the whole kernel for this rarely taken path, which cost
-// the register headroom of a seventh wave per SIMD at c2.
-// RT_SQRT_IEEE_ASM=0 (experiment builds): the compiler's sqrt() instead; the c5 culling kernel then needs
-// 83 VGPRs (5 waves per SIMD) and runs +6% (same-box A/B).
-#ifndef RT_SQRT_IEEE_ASM
-#define RT_SQRT_IEEE_ASM 1
-#endif
+// the register headroom of a seventh wave per SIMD at c2 (and, with the compiler's sqrt() here, the c5 culling
+// kernel needs 83 VGPRs: 5 waves per SIMD).
 __device__ __forceinline__ double sqrt_ieee(double x) {
-#if !RT_SQRT_IEEE_ASM
-    return sqrt(x);
-#endif
     int up, down, cls;
     asm volatile("s_mov_b32 %0, 0x100" : "=s"(up));
     asm volatile("s_mov_b32 %0, 0xffffff80" : "=s"(down));
@@ -254,14 +169,10 @@ __device__ __forceinline__ double sqrt_ieee(double x) {
 
 // sqrt(x), bit-identical, with the fast sequence when it applies.
 __device__ __forceinline__ double sqrt_fast(double x) {
-#if RT_FAST_FALLBACK
     const bool ok = sqrt_fast_ok(x);
     double y = sqrt_core(x);
     if (any_lane(!ok)) y = ok ? y : sqrt_ieee(x);
     return y;
-#else
-    return sqrt_fast_ok(x) ? sqrt_core(x) : sqrt_ieee(x);
-#endif
 }
 
 // |a| (= len(a), :174).
@@ -270,7 +181,6 @@ __device__ __forceinline__ double len_fast(d3 a) { return sqrt_fast(a.x * a.x + 
 // u = a / |a| component-wise (= divs(a, len(a)), :174-175, Line::direction :258-263); *l = |a|.
 __device__ __forceinline__ d3 unit(d3 a, double* l) {
     double s = a.x * a.x + a.y * a.y + a.z * a.z;
-#if RT_FAST_FALLBACK
     const bool ok = sqrt_fast_ok(s) & num_fast_ok(a.x) & num_fast_ok(a.y) & num_fast_ok(a.z);
     double L = sqrt_core(s);
     double r = rcp_core(L);
@@ -284,18 +194,6 @@ __device__ __forceinline__ d3 unit(d3 a, double* l) {
     }
     *l = L;
     return u;
-#else
-    if (sqrt_fast_ok(s) && num_fast_ok(a.x) && num_fast_ok(a.y) && num_fast_ok(a.z)) {
-        double L = sqrt_core(s);
-        double r = rcp_core(L);
-        *l = L;
-        return mk(copysign(div_core(a.x, L, r), a.x), copysign(div_core(a.y, L, r), a.y),
-                  copysign(div_core(a.z, L, r), a.z));
-    }
-    double L = sqrt_ieee(s);
-    *l = L;
-    return divs(a, L);
-#endif
 }
 
 __device__ __forceinline__ d3 unit(d3 a) {
@@ -431,13 +329,9 @@ __device__ __forceinline__ bool bound_pass(const DevScene* S, d3 p0, d3 u) {
 // CheckerBoard -> Quad -> Triangle T1 then T2, first hit wins (:1097, :817, :611-707).
 // d = end - start (unnormalised, :647).  Returns the hit point in *p.  PRIMARY: p0 is the camera eye and
 // the numerator n . (v0 - eye) was computed for it by rt_prepare_kernel with the same operations.
-// RT_BOARD_FLAT=1: the same decisions with one divergent region per outcome instead of one per early return (the
-// sign tests and the numerator evaluated for every lane, the position decision and the exact triangles folded into
-// one hit flag): fewer exec-mask save / restore pairs in the scalar stream (DESIGN.md §9, c2 SALU attribution).
-#ifndef RT_BOARD_FLAT
-#define RT_BOARD_FLAT 1
-#endif
-#if RT_BOARD_FLAT
+// One divergent region per outcome instead of one per early return (the sign tests and the numerator evaluated for
+// every lane, the position decision and the exact triangles folded into one hit flag): fewer exec-mask save / restore
+// pairs in the scalar stream (DESIGN.md §9, c2 SALU attribution).
 template <bool PRIMARY = false>
 __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p) {
     const DevTri& T = S->tri[0];
@@ -445,23 +339,31 @@ __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p)
     double nd = dot(n, d);                                  // :648
     d3 v0 = ld3(T.v0);
     double num = PRIMARY ? S->board_num : dot(n, sub(v0, p0));   // :657 numerator
-    // :651 and the sign half of :659 (m = num / nd <= 0 misses), as in the branchy version below
+    // :651 and the sign half of :659: m = num / nd is <= 0 (hence < eps, a miss at :659) when num == 0 or the signs
+    // differ.  NaNs fall through to the division and miss there, as in the reference.
     const bool live = !(fabs(nd) < S->eps) & !((num == 0.0) | ((num < 0.0) != (nd < 0.0)));
     bool hit = false;
     if (live) {
         double m = num / nd;                                // :657
-#if RT_BOARD_FLAT >= 2
-        // (:659's m < eps folded into the decision below: one region less; the hit point of such a lane is unused)
-        const bool far_enough = !(m < S->eps);
-        {
-#else
         if (!(m < S->eps)) {                                // :659
-#endif
             d3 q = add(p0, scl(m, d));                      // :665
             d3 w = sub(q, v0);                              // :667
             bool decided = false;
-#if RT_BOARD_POS
-            if (S->board_fast) {                            // (the position decision of the branchy version)
+            // The reference's board (host: board_fast) decided by the position of w in its square, where that is certain.
+            // With L the side, T1 = (P1, P2, P3) and T2 = (P1, P3, P4) give, in exact arithmetic on the computed w,
+            //   T1: s = (wx - wz) / L, t = wz / L;   T2: s = wx / L, t = (wz - wx) / L
+            // (uu, uv, vv, den are exact for an integer L <= 2^12, the products with u's and v's zero components vanish),
+            // and the reference's rounded s, t (:670-674) err by less than E = 64 u (|wx| + |wz|) / L + 4 u (u = 2^-53:
+            // two roundings per dot product, three in A and B, one quotient).  For |wx|, |wz| <= far = 2^24 L,
+            // E < 2^-22 + 2^-51; the margin delta = L 2^-19 keeps every decision below at least delta / (2L) = 2^-20 >
+            // 2E + u |s + t| away:
+            //  * delta <= wx, wz <= L - delta and |wx - wz| >= delta: the triangle on w's side of the diagonal has
+            //    s, t >= delta / L and s + t <= 1 - delta / L — it passes (:676), a hit at q;
+            //  * wx <= -delta, wz <= -delta, wx >= L + delta or wz >= L + delta: each triangle fails one of its three
+            //    tests by >= delta / (2L) (e.g. wx <= -delta: T2's s < 0, and T1's s + t = wx / L < 0 puts s or t below
+            //    -delta / (2L)).
+            // Everything else — within delta of an edge or the diagonal, |w| beyond `far`, NaN — takes the exact tests.
+            if (S->board_fast) {
                 const double wx = w.x, wz = w.z, lo = S->board_lo, hi = S->board_hi, diag = fabs(wx - wz);
                 const double far = S->board_far, out = S->board_out, ax = fabs(wx), az = fabs(wz);
                 const bool in = (wx >= lo) & (wz >= lo) & (wx <= hi) & (wz <= hi) & (diag >= lo);
@@ -469,11 +371,6 @@ __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p)
                 hit = in;
                 decided = in | outside;
             }
-#endif
-#if RT_BOARD_FLAT >= 2
-            hit &= far_enough;
-            decided |= !far_enough;
-#endif
             if (!decided) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -482,6 +379,8 @@ __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p)
                     double wv = dot(w, ld3(Tt.v));          // :671
                     double A = Tt.uv * wv - Tt.vv * wu;
                     double B = Tt.uv * wu - Tt.uu * wv;
+                    // den < 0 (host-checked, else thr = +inf): A > thr = |den| 2^-1070 makes A/den negative and
+                    // nonzero, so s >= 0 fails without dividing; likewise B for t.
                     if (!hit & !(A > Tt.thr || B > Tt.thr)) {
                         double s = div_const(A, Tt.den, Tt.rden, Tt.fast);   // :673
                         double tt = div_const(B, Tt.den, Tt.rden, Tt.fast);  // :674
@@ -494,66 +393,6 @@ __device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p)
     }
     return hit;
 }
-#else
-template <bool PRIMARY = false>
-__device__ __forceinline__ bool board_hit(const DevScene* S, d3 p0, d3 d, d3* p) {
-    const DevTri& T = S->tri[0];
-    d3 n = ld3(T.n);
-    double nd = dot(n, d);                                  // :648
-    if (fabs(nd) < S->eps) return false;                    // :651
-    d3 v0 = ld3(T.v0);
-    double num = PRIMARY ? S->board_num : dot(n, sub(v0, p0));   // :657 numerator
-    // m = num / nd is <= 0 (hence < eps, a miss at :659) when num == 0 or the signs differ.  NaNs fall
-    // through to the division and miss there, as in the reference.
-    if (num == 0.0 || ((num < 0.0) != (nd < 0.0))) return false;
-    double m = num / nd;                                    // :657 (its denominator recomputed: same value)
-    if (m < S->eps) return false;                           // :659
-    d3 q = add(p0, scl(m, d));                              // :665
-    d3 w = sub(q, v0);                                      // :667
-#if RT_BOARD_POS
-    // The reference's board (host: board_fast) decided by the position of w in its square, where that is certain.
-    // With L the side, T1 = (P1, P2, P3) and T2 = (P1, P3, P4) give, in exact arithmetic on the computed w,
-    //   T1: s = (wx - wz) / L, t = wz / L;   T2: s = wx / L, t = (wz - wx) / L
-    // (uu, uv, vv, den are exact for an integer L <= 2^12, the products with u's and v's zero components vanish),
-    // and the reference's rounded s, t (:670-674) err by less than E = 64 u (|wx| + |wz|) / L + 4 u (u = 2^-53: two
-    // roundings per dot product, three in A and B, one quotient).  For |wx|, |wz| <= far = 2^24 L, E < 2^-22 + 2^-51;
-    // the margin delta = L 2^-19 keeps every decision below at least delta / (2L) = 2^-20 > 2E + u |s + t| away:
-    //  * delta <= wx, wz <= L - delta and |wx - wz| >= delta: the triangle on w's side of the diagonal has
-    //    s, t >= delta / L and s + t <= 1 - delta / L — it passes (:676), a hit at q;
-    //  * wx <= -delta, wz <= -delta, wx >= L + delta or wz >= L + delta: each triangle fails one of its three tests
-    //    by >= delta / (2L) (e.g. wx <= -delta: T2's s < 0, and T1's s + t = wx / L < 0 puts s or t below -delta/(2L)).
-    // Everything else — within delta of an edge or the diagonal, |w| beyond `far`, NaN — takes the exact tests.
-    if (S->board_fast) {
-        const double wx = w.x, wz = w.z, lo = S->board_lo, hi = S->board_hi, diag = fabs(wx - wz);
-        if ((wx >= lo) & (wz >= lo) & (wx <= hi) & (wz <= hi) & (diag >= lo)) {
-            *p = q;
-            return true;
-        }
-        const double far = S->board_far, out = S->board_out, ax = fabs(wx), az = fabs(wz);
-        if ((ax <= far) & (az <= far) & ((wx <= -lo) | (wz <= -lo) | (wx >= out) | (wz >= out))) return false;
-    }
-#endif
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const DevTri& Tt = S->tri[t];
-        double wu = dot(w, ld3(Tt.u));                      // :670
-        double wv = dot(w, ld3(Tt.v));                      // :671
-        double A = Tt.uv * wv - Tt.vv * wu;
-        double B = Tt.uv * wu - Tt.uu * wv;
-        // den < 0 (host-checked, else thr = +inf): A > thr = |den| 2^-1070 makes A/den negative and nonzero,
-        // so s >= 0 fails without dividing; likewise B for t.
-        if (A > Tt.thr || B > Tt.thr) continue;
-        double s = div_const(A, Tt.den, Tt.rden, Tt.fast);  // :673
-        double tt = div_const(B, Tt.den, Tt.rden, Tt.fast); // :674
-        if (s >= 0 && tt >= 0 && s + tt <= 1) {             // :676
-            *p = q;
-            return true;
-        }
-    }
-    return false;
-}
-
-#endif
 
 // Tests that a ray starting at the hit point q of the previous level certainly misses (exact skips):
 //  * the board, when q is a board hit of a ray from p0.  The board normal is exactly (0, -1, 0) (host-
@@ -573,8 +412,8 @@ template <bool MOTION = false>
 __device__ __forceinline__ int origin_skip(const SceneView& V, int kind, d3 p0, d3 q,
                                            const Motion* mo = nullptr) {
     const DevScene* S = V.S;
-    if (RT_BOARD_SKIP && kind == 0) return fabs(p0.y) <= S->board_skip_y ? 0 : -1;
-    if (RT_SELF_SKIP && kind >= 1 && kind < kMeshKind) {
+    if (kind == 0) return fabs(p0.y) <= S->board_skip_y ? 0 : -1;
+    if (kind >= 1 && kind < kMeshKind) {
         const DevSphere& sp = V.sph[kind - 1];
         d3 dP = sub(ld3(sp.c), q);
         if constexpr (MOTION) dP = sub(motion_centre(*mo, kind - 1), q);
@@ -678,7 +517,7 @@ __device__ __forceinline__ void meshes_closest(const SceneView& V, const Ray& r,
         int t = mesh_closest_tri(V, M, r.p0, r.d, eps, &mbest, &mq);
         if (t < 0) continue;
         // (a deferred distance of the current candidate, take_closer, is computed here)
-        if (RT_LAZY_DIST && *kind >= 0 && *best < 0.0) *best = len_fast(sub(*hp, r.p0));
+        if (*kind >= 0 && *best < 0.0) *best = len_fast(sub(*hp, r.p0));
         if (mbest < *best || *kind < 0 || (mbest == *best && M.child < child_of(V, *kind))) {
             *best = mbest;
             *kind = kMeshKind + 16 * m + (t - M.tri0);
@@ -732,12 +571,11 @@ __device__ __forceinline__ uint64_t sphere_bits(int np) { return np >= 64 ? ~0ul
 
 // The closest-hit update (:811-818) for candidate q of kind k: the reference keeps the first candidate and then
 // one with a strictly smaller Euclidean distance |q - p0|.  Distances are compared only when two candidates meet,
-// so they are computed only then (RT_LAZY_DIST): the first candidate's is deferred — *best < 0 with *kind >= 0
+// so they are computed only then: the first candidate's is deferred — *best < 0 with *kind >= 0
 // means "not computed yet" — and a ray with a single candidate (most board and sphere hits) computes none.  The
 // same comparisons on the same values: kind and hit point are unchanged, bit for bit (a NaN distance compares false
 // either way, and a computed NaN best is never recomputed: NaN < 0 is false).
 __device__ __forceinline__ void take_closer(d3 p0, d3 q, int k, int* kind, double* best, d3* hp) {
-#if RT_LAZY_DIST
     if (*kind < 0) {
         *kind = k;
         *hp = q;
@@ -750,38 +588,20 @@ __device__ __forceinline__ void take_closer(d3 p0, d3 q, int k, int* kind, doubl
         *kind = k;
         *hp = q;
     }
-#else
-    const double dist = len_fast(sub(q, p0));
-    if (dist < *best || *best < 0.0) {
-        *best = dist;
-        *kind = k;
-        *hp = q;
-    }
-#endif
 }
 
 // Closest hit of g_scene (:796-821): Euclidean distance |p - p0|, strict <, board (child 0) first.
 // kind: -1 miss, 0 board, 1 + k sphere k.
 // Spheres go in batches of kChunk: the FP32 filter of the whole batch is evaluated branch-free (records
-// in SGPRs), then each lane runs the exact FP64 test only on its own surviving spheres, in increasing k,
+// in SGPRs), then the exact FP64 tests visit the batch's spheres in a loop the whole wave runs (record index
+// wave-uniform: scalar loads, SGPR operands; lanes whose filter rejected a sphere are masked off), in increasing k,
 // so the strict-< closest-hit order of the reference is unchanged.  Padding spheres never survive.
-#ifndef RT_SEC_PREFETCH
-#define RT_SEC_PREFETCH 0
-#endif
 // MOTION: the filter records of the swept spheres, the exact test on the lane's centres (struct Motion).
 template <bool MOTION = false>
 __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const Ray& r, int k0, double eps,
                                                      int* kind, double* best, d3* hp, int self = -1,
                                                      const Motion* mo = nullptr) {
-    static_assert(!(MOTION && RT_SEC_PREFETCH), "the prefetched records hold the stored centres");
     uint32_t pass = 0;
-#if RT_SEC_PREFETCH
-    // the batch's exact-test records requested with its filter records (one wait for all)
-    DevSphere sp4[kChunk];
-#pragma unroll
-    for (int j = 0; j < kChunk; ++j) sp4[j] = V.sph[k0 + j];
-    asm volatile("" ::"s"(sp4[0].r2), "s"(sp4[1].r2), "s"(sp4[2].r2), "s"(sp4[3].r2));
-#endif
 #pragma unroll
     for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(V.sphf[k0 + j], r) ? 0u : 1u) << j;
     if constexpr (MOTION) {                                 // (the static records' bits are dead code then)
@@ -790,23 +610,10 @@ __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const R
         for (int j = 0; j < kChunk; ++j) pass |= (sphere_reject32(motion_filter(*mo)[k0 + j], r) ? 0u : 1u) << j;
     }
     pass = drop_self(pass, self, k0);                       // r starts on sphere `self`: a certain miss
-#if RT_UNIFORM_SECONDARY
 #pragma unroll
     for (int j = 0; j < kChunk; ++j) {
         if (!(pass & (1u << j))) continue;                  // skipped by the wave when no lane needs it
         const int k = k0 + j;
-#if RT_SEC_PREFETCH
-        {
-            d3 q;
-            if (sphere_hit(sp4[j], r.p0, r.u, eps, &q)) take_closer(r.p0, q, 1 + k, kind, best, hp);
-            continue;
-        }
-#endif
-#else
-    while (pass) {
-        const int k = k0 + __builtin_ctz(pass);
-        pass &= pass - 1;
-#endif
         d3 q;
         if constexpr (MOTION) {
             if (sphere_hit_at(motion_centre(*mo, k), V.sph[k].r2, r.p0, r.u, eps, &q))
@@ -826,7 +633,7 @@ __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3*
                                            int skip = -1, bool from_hit = false, const Motion* mo = nullptr) {
     static_assert(!(MOTION && CULL), "moving spheres take the generic path");
     const DevScene* S = V.S;
-    if (!(RT_HITS_INSIDE && from_hit && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return -1;
+    if (!(from_hit && V.hits_ok) && !bound_pass(S, r.p0, r.u)) return -1;
     int kind = -1;
     double best = -1.0;
     if (S->has_board && skip != 0) {
@@ -840,16 +647,8 @@ __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3*
             const int k = __builtin_ctzll(m);
             RT_COUNT(S, kCntFilterRay, 1);
             RT_COUNT_LANES(S, kCntLanesFilterRay);
-#if RT_PRIM_PREFETCH
-            // the exact test's record with the filter's (one wait for both, as in primary_sphere)
-            const DevSphereF sf = V.sphf[k];
-            const DevSphere sp = V.sph[k];
-            asm volatile("" ::"s"(sf.rm), "s"(sp.r2));
-            if (k == skip - 1 || sphere_reject32(sf, r)) continue;
-#else
             if (k == skip - 1 || sphere_reject32(V.sphf[k], r)) continue;
             const DevSphere& sp = V.sph[k];
-#endif
             RT_COUNT(S, kCntExactRay, 1);
             RT_COUNT_LANES(S, kCntLanesExactRay);
             d3 q;
@@ -867,32 +666,17 @@ __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3*
     return kind;
 }
 
-// Closest hit of a primary ray Line(eye, sp): deltaP and |deltaP|^2 per sphere were computed for this
-// eye by rt_prepare_kernel with the reference's operations (:740, :750).  A miss of the bounding-sphere
-// cull makes the whole g_scene a miss, whatever the children say, so it can be tested after them.
 // One sphere of a primary ray: FP32 filter on the per-eye image, then the exact test (:747-772) and the
 // strict-< closest-hit update (:811-813).
-#ifndef RT_PRIM_PREFETCH
-#define RT_PRIM_PREFETCH 0
-#endif
 __device__ __forceinline__ void primary_sphere(const SceneView& V, const Ray& r, int k, double eps, int* kind,
                                                double* best, d3* hp) {
     const DevSpherePrimF f = V.primf[k];
-#if RT_PRIM_PREFETCH
-    // The exact test's records are requested with the filter's (scalar loads, one wait for all): a sphere that
-    // passes the filter then costs no second round trip to memory.
-    const DevSpherePrim pp = V.prim[k];
-    const double r2 = V.sph[k].r2;
-    asm volatile("" ::"s"(f.c0), "s"(pp.dd), "s"(r2));
-#endif
     float uD = r.ux * f.dx;
     uD = fmaf(r.uy, f.dy, uD);
     uD = fmaf(r.uz, f.dz, uD);
     if (fmaf(uD, uD, f.c0) < 0.0f) return;                  // certain disc < 0
-#if !RT_PRIM_PREFETCH
     const DevSpherePrim& pp = V.prim[k];
     const double r2 = V.sph[k].r2;
-#endif
     d3 q;
     RT_COUNT(V.S, kCntExactPrimary, 1);
     if (sphere_hit_dp(ld3(pp.dP), pp.dd, r2, r.p0, r.u, eps, &q)) take_closer(r.p0, q, 1 + k, kind, best, hp);
@@ -934,16 +718,10 @@ __device__ __forceinline__ int closest_hit_primary(const SceneView& V, Ray& r, u
             uD = fmaf(r.uz, f.dz, uD);
             pass |= (fmaf(uD, uD, f.c0) < 0.0f ? 0u : 1u) << j;   // < 0: certain disc < 0
         }
-#if RT_UNIFORM_PRIMARY
 #pragma unroll
-        for (int j = 0; j < kChunk; ++j) {
+        for (int j = 0; j < kChunk; ++j) {                  // (a loop the whole wave runs, as sphere_batch_closest's)
             if (!(pass & (1u << j))) continue;
             const int k = k0 + j;
-#else
-        while (pass) {
-            const int k = k0 + __builtin_ctz(pass);
-            pass &= pass - 1;
-#endif
             const DevSpherePrim& pp = V.prim[k];
             d3 q;
             if (sphere_hit_dp(ld3(pp.dP), pp.dd, V.sph[k].r2, r.p0, r.u, eps, &q)) take_closer(r.p0, q, 1 + k, &kind, &best, hp);
@@ -955,7 +733,7 @@ __device__ __forceinline__ int closest_hit_primary(const SceneView& V, Ray& r, u
     // for rays that hit something: waves of background rays skip it.
     // (deltaP = bc - eye, computed here for the waves that need it rather than held from the kernel's start)
     // (prim_bound_ok, per eye: every primary hit passes it — proof at rt_prepare_kernel)
-    if (kind >= 0 && !(RT_PRIM_BOUND_SKIP && S->prim_bound_ok)) {
+    if (kind >= 0 && !S->prim_bound_ok) {
         const d3 bdP = sub(ld3(S->bc), r.p0);               // :740 with p0 = camera
         if (!bound_pass_dp(S, bdP, dot(bdP, bdP), r.u)) kind = -1;
     }
@@ -967,8 +745,8 @@ __device__ __host__ __forceinline__ float chord_of_sin(float s) {
     return s * sqrtf(2.0f / (1.0f + sqrtf(fmaxf(0.0f, 1.0f - s * s))));
 }
 
-// (msqrt, mrcp, mdiv, mchord_of_sin — the FP32 square root and reciprocal of the wave-culling tests, RT_FAST_MASK —
-// are in rt_cone.hpp, with the primary cone's tests.)
+// (msqrt, mrcp, mdiv, mchord_of_sin — the FP32 square root and reciprocal of the wave-culling tests — are in
+// rt_cone.hpp, with the primary cone's tests.)
 
 // Per-wave culling of primary rays (V.np >= kPrimaryConeMin; all 64 lanes must be active).  The wave's rays lie
 // within chord distance rho of the block's axis a (rt_cone.hpp wave_axis).  A ray that hits sphere k has
@@ -1026,9 +804,6 @@ __device__ __forceinline__ float inf_if_nan(float v) { return v >= 0.0f ? v : __
 // and v = unit(C_k - o) is at most asin(R / |C_k - o|), i.e. |a - v| <= rho_d + chord(R / |C_k - o|).
 // FP32 coordinates carry < 2^-20 relative error; R gets 2^-12 (|o| + |C| + 1) absolute and the chord
 // test 2^-14 of slack.
-#ifndef RT_CHEAP_BUNDLE
-#define RT_CHEAP_BUNDLE 0
-#endif
 __device__ __forceinline__ uint64_t ray_bundle_part(const SceneView& V, bool on, const Ray& r, int f) {
     const int lane = __lane_id();
     const float ox = lane_f32(r.px, f), oy = lane_f32(r.py, f), oz = lane_f32(r.pz, f);
@@ -1056,22 +831,6 @@ __device__ __forceinline__ uint64_t ray_bundle_part(const SceneView& V, bool on,
                                 fmaxf(fabsf(c.cx), fmaxf(fabsf(c.cy), fabsf(c.cz))) + 1.0f;
             const float R = (msqrt(fmaf(c.rm, 1.0f + 0x1p-20f, Dm * Dm * 0x1p-46f)) + rho_o) * (1.0f + 0x1p-12f) +
                             0x1p-12f * scale;
-#if RT_CHEAP_BUNDLE
-            // The same cone test without the chord's two square roots and the reciprocal of D: for s = R / D <= 0.9,
-            // chord(asin s) = s sqrt(2 / (1 + sqrt(1 - s^2))) <= s (1 + s^2 / 4) (equal at s = 0, 1.2% above the
-            // chord at s = 0.9; the gap only grows towards 0.9), so |a - v / D| <= rho_d + chord + 2^-14 follows from
-            // |a D - v| <= rho_d D + R (1 + s^2 / 4) + 2^-14 D (both sides times D > 0).  s > 0.9 (D < R / 0.9):
-            // kept, as D <= R is.  FP32 errors of a D - v (< 2^-21 D) and of s^2 (mrcp: 2^-22 relative) stay far
-            // inside the 2^-14 D slack.
-            if (!(D * 0.9f > R)) {
-                keep = true;
-            } else {
-                const float s2 = (R * R) * mrcp(D2);
-                const float limD = fmaf(rho_d + 0x1p-14f, D, R * fmaf(0.25f, s2, 1.0f));
-                const float ex = fmaf(ax, D, -vx), ey = fmaf(ay, D, -vy), ez = fmaf(az, D, -vz);
-                keep = !(fmaf(ex, ex, fmaf(ey, ey, ez * ez)) > limD * limD);
-            }
-#else
             if (!(D > R)) {
                 keep = true;
             } else {
@@ -1080,7 +839,6 @@ __device__ __forceinline__ uint64_t ray_bundle_part(const SceneView& V, bool on,
                 const float ex = ax - vx * iD, ey = ay - vy * iD, ez = az - vz * iD;
                 keep = !(fmaf(ex, ex, fmaf(ey, ey, ez * ez)) > lim * lim);
             }
-#endif
         }
     }
     const uint64_t kept = __ballot(keep);
@@ -1089,18 +847,14 @@ __device__ __forceinline__ uint64_t ray_bundle_part(const SceneView& V, bool on,
     return kept;
 }
 
-// 1: a wave whose rays fan out (a sphere's silhouette: mirror rays off the board beside grazing reflections
+// A wave whose rays fan out (a sphere's silhouette: mirror rays off the board beside grazing reflections
 // off the sphere) is covered by two bundles — the lanes within chord 0.9 of the first lane's direction (always
 // narrow enough to cull) and the rest — and the mask is their union (each part is conservative for its lanes);
-// 0: one bundle, no culling once the directions spread past chord 1.
-#ifndef RT_BUNDLE_SPLIT
-#define RT_BUNDLE_SPLIT 1
-#endif
+// one bundle would stop culling once the directions spread past chord 1.
 __device__ __forceinline__ uint64_t ray_bundle_mask(const SceneView& V, bool on, const Ray& r) {
     const uint64_t onm = __ballot(on);
     if (!onm) return 0;
     const int f = __builtin_ctzll(onm);
-#if RT_BUNDLE_SPLIT
     const float ax = lane_f32(r.ux, f), ay = lane_f32(r.uy, f), az = lane_f32(r.uz, f);
     const float ux = r.ux - ax, uy = r.uy - ay, uz = r.uz - az;
     const bool near = on && fmaf(ux, ux, fmaf(uy, uy, uz * uz)) < 0.81f;     // NaN: not near
@@ -1109,9 +863,6 @@ __device__ __forceinline__ uint64_t ray_bundle_mask(const SceneView& V, bool on,
     const uint64_t restm = __ballot(rest);
     if (restm) m |= ray_bundle_part(V, rest, r, __builtin_ctzll(restm));
     return m;
-#else
-    return ray_bundle_part(V, on, r, f);
-#endif
 }
 
 // Shadow rays to light li: every ray lies on a line through the light, with direction w_l = u_l.
@@ -1155,18 +906,15 @@ __device__ __forceinline__ uint64_t shadow_bundle_mask(const SceneView& V, bool 
 // far inside the 2^-16 folded into c_k; the FP64 hit test's own rounding moves the line by ~1e-13
 // relative, likewise covered.  A NaN direction is not rejected (it compares false), as the FP64 test
 // reports NaN rays as hits.
-// RT_OCCL_FLAT=1: the same any-hit test with a per-lane flag instead of returns from inside the sphere loops (a lane
-// that found a blocker leaves the loops; the board is tested by the lanes still unblocked).  occluded<.., FLAT> picks
-// the form per instance (shade: the three-channel culling kernels keep the returns — the flag form spills 32 VGPRs
-// to scratch in their depth-3 instance).
-#ifndef RT_OCCL_FLAT
-#define RT_OCCL_FLAT 1
-#endif
+// Two forms.  occluded_flag: the any-hit test with a per-lane flag instead of returns from inside the sphere loops (a
+// lane that found a blocker leaves the loops; the board is tested by the lanes still unblocked).  occluded_ret: the
+// returns.  occluded<.., FLAT> picks the form per instance (shade: the three-channel culling kernels keep the returns —
+// the flag form spills 32 VGPRs to scratch in their depth-3 instance).
 template <bool FULL, bool CULL = false>
 __device__ __forceinline__ bool occluded_flag(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                               int skip = -1) {
     const DevScene* S = V.S;
-    if (!(RT_HITS_INSIDE && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return false;   // shadow rays start at hits
+    if (!V.hits_ok && !bound_pass(S, r.p0, r.u)) return false;   // shadow rays start at hits
     const double eps = S->eps;
     const DevSphereLightF* lf = V.lightf + li * V.ns;
     bool blocked = false;
@@ -1227,7 +975,7 @@ template <bool FULL, bool CULL = false>
 __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                              int skip = -1) {
     const DevScene* S = V.S;
-    if (!(RT_HITS_INSIDE && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return false;   // shadow rays start at hits
+    if (!V.hits_ok && !bound_pass(S, r.p0, r.u)) return false;   // shadow rays start at hits
     const double eps = S->eps;
     const DevSphereLightF* lf = V.lightf + li * V.ns;
     int k0 = 0;
@@ -1260,16 +1008,9 @@ __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, i
             pass |= (fabsf(t) < f.c ? 0u : 1u) << j;
         }
         pass = drop_self(pass, skip - 1, k0);
-#if RT_UNIFORM_SHADOW
-#pragma unroll
-        for (int j = 0; j < kChunk; ++j) {
-            if (!(pass & (1u << j))) continue;
-            const int k = k0 + j;
-#else
-        while (pass) {
+        while (pass) {                                      // (each lane walks its own surviving spheres)
             const int k = k0 + __builtin_ctz(pass);
             pass &= pass - 1;
-#endif
             d3 q;
             if (sphere_hit(V.sph[k], r.p0, r.u, eps, &q)) return true;
         }
@@ -1290,7 +1031,7 @@ __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, i
     return false;
 }
 
-template <bool FULL, bool CULL = false, bool FLAT = RT_OCCL_FLAT>
+template <bool FULL, bool CULL, bool FLAT>
 __device__ __forceinline__ bool occluded(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                          int skip = -1) {
     if constexpr (FLAT) return occluded_flag<FULL, CULL>(V, r, li, mask, skip);
@@ -1309,7 +1050,7 @@ template <bool MOTION = false>
 __device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray& r, int skip = -1,
                                                   const Motion* mo = nullptr) {
     const DevScene* S = V.S;
-    if (!(RT_HITS_INSIDE && (RT_HITS_VIEW ? V.hits_ok : S->hits_ok)) && !bound_pass(S, r.p0, r.u)) return false;
+    if (!V.hits_ok && !bound_pass(S, r.p0, r.u)) return false;
     const double eps = S->eps;
     bool blocked = false;
     if (S->has_board && skip != 0) {
@@ -1343,10 +1084,7 @@ __device__ __forceinline__ bool occluded_anywhere(const SceneView& V, const Ray&
 // quotient bit for bit (fast paths above); below that the quotient is < 2^-400 and truncates to 0 either
 // way, hit points on the board never exceed it, and NaN stays NaN (converted to 0 either way).
 // MESH = false: the caller's closest hits never name a mesh triangle (the opaque kernels' closest_hit<false> tests no
-// meshes), so that branch is compiled out (RT_MESH_STATIC).
-#ifndef RT_MESH_STATIC
-#define RT_MESH_STATIC 1
-#endif
+// meshes), so that branch is compiled out.
 template <bool MESH = true>
 __device__ __forceinline__ int material_of(const SceneView& V, int kind, d3 p) {
     const DevScene* S = V.S;
@@ -1385,13 +1123,9 @@ __device__ __forceinline__ d3 transmitted_end(const SceneView& V, int kind, int 
 }
 
 // Surface data of a hit: normal, material id, reflected end point p + r (:679-683, :774-778, :1101-1111).
-#ifndef RT_CENTER_UNIFORM
-#define RT_CENTER_UNIFORM 0
-#endif
 template <bool MESH = true, bool MOTION = false>
 __device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u, d3* n, int* mat, d3* pe,
                                         const Motion* mo = nullptr) {
-    static_assert(!(MOTION && RT_CENTER_UNIFORM), "the lane's centre is not wave-uniform");
     const DevScene* S = V.S;
     if (kind == 0) {
         *n = ld3(S->tri[0].n);
@@ -1399,23 +1133,7 @@ __device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u
         const DevMesh& M = V.mesh[(kind - kMeshKind) >> 4];
         *n = ld3(V.tri[M.tri0 + ((kind - kMeshKind) & 15)].n);
     } else {
-#if RT_CENTER_UNIFORM
-        // the centres of the spheres this wave hit, one scalar load per distinct sphere (the first remaining
-        // lane's), instead of a per-lane vector load
-        d3 c = mk(0.0, 0.0, 0.0);
-        bool todo = true;
-        for (;;) {
-            const uint64_t m = __ballot(todo);
-            if (m == 0) break;
-            const int k = __builtin_amdgcn_readlane(kind, (int)__builtin_ctzll(m));
-            if (todo && kind == k) {
-                c = ld3(V.sph[k - 1].c);
-                todo = false;
-            }
-        }
-#else
         d3 c = ld3(V.sph[kind - 1].c);
-#endif
         if constexpr (MOTION) c = motion_centre(*mo, kind - 1);   // the centre this lane's ray hit
         d3 dp = sub(p, c);                                  // directionP0 (:763)
         *n = unit(dp);                                      // :774-775
@@ -1425,7 +1143,7 @@ __device__ __forceinline__ void surface(const SceneView& V, int kind, d3 p, d3 u
     *pe = add(p, r);                                        // Line(p, p + r)
 }
 
-// Per-tile cache of the culling masks of every level (r06, RT_LEVEL_MASKS): a static view's rays are the same bits in
+// Per-tile cache of the culling masks of every level (r06): a static view's rays are the same bits in
 // every frame, so the wave-uniform masks ray_bundle_mask and shadow_bundle_mask compute from them are a pure function
 // of the view, like the primary cone mask of the dispatch record.  The view's calibration render stores them per tile
 // (`out`, lane 0), later renders of exactly that view read them (`in`) instead of computing them: slot l - 1 holds
@@ -1446,9 +1164,6 @@ __device__ __forceinline__ uint64_t* level_masks_out();
 // FULL: meshes may be present and materials may be transparent (closest-hit shadows, :1219-1221).
 // ACC: the colour is accumulated in LDS at acc[0], acc[SS], acc[2 SS] (starting at 0, the same additions in the
 // same order) instead of in registers live across every light's shadow test; the return value is then unused.
-#ifndef RT_MAT_UNIFORM
-#define RT_MAT_UNIFORM 0
-#endif
 // ACHRO (an achromatic scene, rt_scene_achromatic: every light colour and every material term an object uses has
 // R = G = B): the three channels are the same operations on equal values, so only R is computed and the colour is
 // (R, R, R) — bit for bit the reference's (G and B are R's operations repeated).  Not with FULL (transparency weights).
@@ -1513,7 +1228,7 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         if (hit)
             lit = !(FULL ? occluded_transparent<MOTION>(V, sr, mo)
                     : AREA ? occluded_anywhere<MOTION>(V, sr, skip, mo)
-                           : occluded<false, CULL, RT_OCCL_FLAT && (ACHRO || !CULL)>(V, sr, i, m, skip));
+                           : occluded<false, CULL, ACHRO || !CULL>(V, sr, i, m, skip));
         if (lit && ACHRO) {                                 // R only (same operations as below, channel x)
             const double a = S->att / (S->att + dl * dl);   // attenuation (:1181)
             const double lc = a * S->light[i].col[0];       // :1223
@@ -1524,32 +1239,8 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         } else if (lit) {
             double a = S->att / (S->att + dl * dl);         // attenuation (:1181)
             d3 lC = scl(a, ld3(S->light[i].col));           // :1223
-#if RT_MAT_UNIFORM
-            // Opaque scenes use materials 0-2 (board squares, spheres): each one some lit lane needs is read with
-            // scalar loads (wave-uniform address) and selected per lane, instead of a per-lane vector load.
-            d3 amb = mk(0.0, 0.0, 0.0), dif = amb, spc = amb;
-            if (!FULL) {
-#pragma unroll
-                for (int m = 0; m < 3; ++m) {
-                    if (__ballot(mat == m) == 0) continue;
-                    const DevMat& M = S->mat[m];
-                    if (mat == m) {
-                        amb = ld3(M.amb);
-                        dif = ld3(M.diff);
-                        spc = ld3(M.spec);
-                    }
-                }
-            } else {
-                const DevMat& M = S->mat[mat];
-                amb = ld3(M.amb);
-                dif = ld3(M.diff);
-                spc = ld3(M.spec);
-            }
-            d3 term = add(add(had(amb, lC), scl(kd, had(dif, lC))), scl(ks, had(spc, lC)));
-#else
             const DevMat& M = S->mat[mat];                  // material terms loaded only when lit
             d3 term = add(add(had(ld3(M.amb), lC), scl(kd, had(ld3(M.diff), lC))), scl(ks, had(ld3(M.spec), lC)));
-#endif
             if (ACC) {                                      // :1224-1226, in LDS
                 acc[0] = acc[0] + term.x;
                 acc[SS] = acc[SS] + term.y;
@@ -1570,15 +1261,18 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
 #define RT_ACC_LDS_MAX_B 1
 #endif
 __host__ __device__ constexpr bool acc_lds(int B, bool transp) { return !transp && B >= 1 && B <= RT_ACC_LDS_MAX_B; }
-// The culling variant keeps its last level's colour in registers (RT_CULL_LAST_REG): B colour slots instead of
+// The opaque culling variant keeps its last level's colour in registers: B colour slots instead of
 // B + 1, so depth 3 needs 4.5 KB of LDS per one-wave workgroup instead of 6 KB — 35 workgroups per CU instead of
 // 26, i.e. room for a seventh wave per SIMD.
-#ifndef RT_CULL_LAST_REG
-#define RT_CULL_LAST_REG 1
-#endif
 __host__ __device__ constexpr int colour_slots(int B, bool transp, bool cull = false) {
-    return cull && RT_CULL_LAST_REG && !transp ? B : B + 1 + (acc_lds(B, transp) ? 1 : 0);
+    return cull && !transp ? B : B + 1 + (acc_lds(B, transp) ? 1 : 0);
 }
+// (these size the launches' LDS: one case per distinct branch)
+static_assert(colour_slots(3, false, true) == 3 && colour_slots(0, false, true) == 0, "opaque culling: B slots");
+static_assert(colour_slots(3, true, true) == 4 && colour_slots(3, true) == 4, "transparent: B + 1 slots, culling or not");
+static_assert(colour_slots(0, false) == 1 && colour_slots(1, false) == 2 + (acc_lds(1, false) ? 1 : 0) &&
+                  colour_slots(7, false) == 8 + (acc_lds(7, false) ? 1 : 0),
+              "opaque fast: B + 1 slots, one more where the colour accumulates in LDS");
 
 // rayTraceRay(g_scene, lights, Line(p0, p1), color, B) with color starting at 0 (:1184-1249), as a loop.
 // Every hit of a non-tree scene spawns exactly one continuation (host-checked; ray trees: trace_tree): the
@@ -1618,8 +1312,9 @@ __device__ __forceinline__ void park_level(int lvl, int mat, d3 c, double* slot,
 // The next level's ray for EVERY lane: Line(p, p + nd) for lanes that hit; lanes that did not get a zero
 // ray (they are not alive at the next level and never trace it).  Assigning it unconditionally ends the
 // live range of the previous ray at the hit test, so it is not carried through the light loop (the
-// compiler cannot see that a lane which did not hit never reads its ray again).  u = unit(nd) is
-// recomputed here (same operations, same bits) rather than kept live through the light loop.
+// compiler cannot see that a lane which did not hit never reads its ray again).  Two forms.  This one (the culling
+// levels of depth < 3) recomputes u = unit(nd) here (same operations, same bits) rather than keeping it live through
+// the light loop.
 __device__ __forceinline__ void next_ray(bool hit, d3 p, d3 nd, Ray* r) {
     d3 nu = nd;
     if (hit) nu = unit(nd);                                 // not for the zero rays: unit(0) is the slow path
@@ -1627,7 +1322,8 @@ __device__ __forceinline__ void next_ray(bool hit, d3 p, d3 nd, Ray* r) {
     set_dir(r, nd, nu);
 }
 
-// As above with the continuation's unit direction kept from before the light loop (RT_KEEP_NU).
+// ... and this one (the fast loop, the culling levels of depth >= 3) takes the unit direction the caller computed
+// before the light loop and parked in LDS across it: no recomputation, no live registers.
 __device__ __forceinline__ void next_ray(d3 p, d3 nd, d3 nu, Ray* r) {
     r->p0 = p;
     set_dir(r, nd, nu);
@@ -1639,9 +1335,9 @@ template <int B, bool TRANSP, int SS = kSlotStride, bool ACHRO = false>
 __device__ __forceinline__ bool cull_level(const SceneView& V, int lvl, bool first, bool alive, uint64_t cone, Ray* r, int* levels,
                                            double* slot, int* mslot, int* skip, bool lazy_u, d3* last,
                                            const LevelMasks& lm) {
-    // the last level's colour stays in registers (RT_CULL_LAST_REG): slot B does not exist, so the continuation
+    // the last level's colour stays in registers (colour_slots): slot B does not exist, so the continuation
     // of level B - 1 parks only its end - start and recomputes its unit direction after the light loop
-    constexpr bool kLastReg = RT_CULL_LAST_REG && !TRANSP;
+    constexpr bool kLastReg = !TRANSP;
     uint64_t smask = ~0ull;
     RT_COUNT(V.S, kCntLevels, 1);
     if (!first) {
@@ -1672,11 +1368,11 @@ __device__ __forceinline__ bool cull_level(const SceneView& V, int lvl, bool fir
     int mat = 0;
     double ks = 0.0;
     // (depth >= 3 only: at depth 2 the register allocation of this variant came out worse, 96 VGPRs + spills)
-    constexpr bool kParkCull = RT_PARK_NU_CULL && B >= 3;
+    constexpr bool kParkCull = B >= 3;
     double* psl = slot + 3 * lvl * SS;                      // this level's colour slot, written after shade
     if (hit) {
         d3 pe;
-        surface<TRANSP || !RT_MESH_STATIC>(V, kind, p, r->u, &n, &mat, &pe);
+        surface<TRANSP>(V, kind, p, r->u, &n, &mat, &pe);
         const d3 rd = sub(pe, p);                           // reflectedRay = Line(p, p + r)
         const d3 rdir = unit(rd);                           // reflectedRay.direction()
         ks = fabs(dot(r->u, rdir));                         // |u . reflectedRay.direction()|
@@ -1735,21 +1431,17 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
     // A primary ray of a wave whose cone mask keeps no sphere can only hit the board: its direction is computed
     // by closest_hit_primary for the lanes that hit (sky waves skip the normalisation).
     // (spheres past the first 64 are not in the mask: scenes with more always normalise)
-    const bool lazy_u = RT_LAZY_PRIMARY_U && PRIMARY && !TRANSP && V.np >= kPrimaryConeMin && V.np <= 64 &&
+    const bool lazy_u = PRIMARY && !TRANSP && V.np >= kPrimaryConeMin && V.np <= 64 &&
                         (cone & sphere_bits(V.np)) == 0;
     if (lazy_u) r.d = d;
     else set_dir(&r, d, unit(d));
     // rays traced (seg, shadow) follow from `levels`: every lane traces levels 0 .. min(levels, B), nl shadow rays per hit
     int skip = -1;                                          // origin_skip of r's origin
-    d3 last = mk(0.0, 0.0, 0.0);                            // CULL, RT_CULL_LAST_REG: level B's colour
-    constexpr bool kLastReg = CULL && RT_CULL_LAST_REG && !TRANSP;
+    d3 last = mk(0.0, 0.0, 0.0);                            // opaque CULL: level B's colour (colour_slots)
+    constexpr bool kLastReg = CULL && !TRANSP;
     constexpr bool kSkip = !TRANSP && B >= RT_SKIP_FAST_MIN_B;  // fast loop: origin skips from this depth
-    constexpr bool kPark = B >= RT_PARK_ND_MIN_B;
-#if RT_UNROLL_LEVELS
+    // (unrolled: one copy of the level code per level)
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
     for (int lvl = 0; lvl <= B; ++lvl) {
         const bool alive = lvl == 0 || levels == lvl;
         if (!__any(alive)) break;                           // the whole wave has missed: early out
@@ -1777,36 +1469,28 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
             const bool hit = kind >= 0;
             skip = kSkip ? origin_skip<MOTION>(V, kind, r.p0, p, mo) : -1;   // this hit's rays start at p
             d3 nd = mk(0.0, 0.0, 0.0);
-#if RT_KEEP_NU || RT_PARK_NU
             d3 nu = nd;
-#endif
             if (hit) {
                 d3 n, pe;
                 int mat;
-                surface<TRANSP || !RT_MESH_STATIC, MOTION>(V, kind, p, r.u, &n, &mat, &pe, mo);
+                surface<TRANSP, MOTION>(V, kind, p, r.u, &n, &mat, &pe, mo);
                 const d3 rd = sub(pe, p);                   // reflectedRay = Line(p, p + r)
                 const d3 rdir = unit(rd);                   // reflectedRay.direction()
                 const double ks = fabs(dot(r.u, rdir));     // |u . reflectedRay.direction()|
                 nd = continuation<TRANSP>(V, kind, mat, p, n, r.u, rd);
-#if RT_KEEP_NU && !RT_PARK_NU
-                nu = (TRANSP && V.S->mat[mat].transmit) ? unit(nd) : rdir;
-#endif
                 double* psl = slot + 3 * lvl * SS;          // this level's colour slot, written after shade
-#if RT_PARK_NU
-                // ... and the continuation's unit direction in the next level's slot (written after that
-                // level's shade): no recomputation of unit(nd) after the light loop, no live registers
-                if (lvl < B) {
-                    const d3 nu = (TRANSP && V.S->mat[mat].transmit) ? unit(nd) : rdir;
-                    double* nsl = psl + 3 * SS;
-                    nsl[0] = nu.x;
-                    nsl[SS] = nu.y;
-                    nsl[2 * SS] = nu.z;
-                }
-#endif
                 // with the colour accumulated in this level's slot (kAcc), the end - start waits in slot lvl + 2
                 constexpr bool kAcc = acc_lds(B, TRANSP);
                 double* ndsl = kAcc ? psl + 6 * SS : psl;
-                if ((kPark || RT_PARK_NU) && lvl < B) {
+                if (lvl < B) {
+                    // The continuation waits in LDS across the light loop: its unit direction in the next level's
+                    // slot (written after that level's shade) and its end - start in this level's (still empty)
+                    // slot: no recomputation of unit(nd) after the light loop, no live registers.
+                    const d3 cu = (TRANSP && V.S->mat[mat].transmit) ? unit(nd) : rdir;
+                    double* nsl = psl + 3 * SS;
+                    nsl[0] = cu.x;
+                    nsl[SS] = cu.y;
+                    nsl[2 * SS] = cu.z;
                     ndsl[0] = nd.x;
                     ndsl[SS] = nd.y;
                     ndsl[2 * SS] = nd.z;
@@ -1814,21 +1498,15 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
                 }
                 const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA, MOTION>(V, true, p, n, mat, ks, skip, psl, &lm,
                                                                                  B + lvl * V.nl, ls, mo);
-                if ((kPark || RT_PARK_NU) && lvl < B) {
+                if (lvl < B) {
                     asm volatile("" ::: "memory");
                     nd = mk(ndsl[0], ndsl[SS], ndsl[2 * SS]);
-#if RT_PARK_NU
                     nu = mk(psl[3 * SS], psl[4 * SS], psl[5 * SS]);
-#endif
                 }
                 if (!kAcc) park_level<TRANSP, SS, ACHRO>(lvl, mat, c, slot, mslot);
                 levels = lvl + 1;
             }
-#if RT_KEEP_NU || RT_PARK_NU
             if (lvl < B) next_ray(p, nd, nu, &r);
-#else
-            if (lvl < B) next_ray(hit, p, nd, &r);
-#endif
         }
     }
     d3 acc = mk(0.0, 0.0, 0.0);
@@ -1836,7 +1514,7 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
     for (int lvl = levels - 1; lvl >= 0; --lvl) {
         const double* sl = slot + 3 * lvl * SS;
         d3 c;
-        if (kLastReg && lvl == B) c = last;             // (RT_CULL_LAST_REG: level B's colour in registers)
+        if (kLastReg && lvl == B) c = last;             // (level B's colour in registers)
         else if (ACHRO) c = mk(sl[0], sl[0], sl[0]);
         else c = mk(sl[0], sl[SS], sl[2 * SS]);
         if (lvl == levels - 1) acc = c;

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void rt_iota_kernel(int32_t* __restrict__ v, i
 
 // The dispatch table of a calibrated view: position L (linear workgroup id, L = gy * tiles_x + bx) traces tile
 // by_pos[L] (tile order: tile indices by decreasing calibrated time) or, row order (by_pos = nullptr), tile column
-// tile_col(bx, gy) of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
+// bx of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
 // `cone` (else 0), and their sky verdicts (cone[n + tile], n the tile count).  Stored at cone_slot(L): grouped by the
 // XCD workgroup L runs on.
 __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict__ row_order,
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     } else {
         const int gy = (int)(k / tiles_x), bx = (int)(k - (size_t)gy * tiles_x);
         ty = row_order[gy];
-        tx = tile_col(bx, gy, tiles_x);
+        tx = bx;
     }
     const uint64_t m = cone ? cone[(size_t)ty * tiles_x + tx] : 0;
     DispRec r;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256) void rt_run_plan_kernel(const int32_t* __restr
     extern __shared__ uint8_t row_sky[];
     const int gy = (int)blockIdx.x;
     const uint64_t* v = sky + (size_t)row_order[gy] * tiles_x;
-    for (int x = threadIdx.x; x < tiles_x; x += 256) row_sky[x] = v[tile_col(x, gy, tiles_x)] != 0;
+    for (int x = threadIdx.x; x < tiles_x; x += 256) row_sky[x] = v[x] != 0;
     __syncthreads();
     for (int x = threadIdx.x; x < tiles_x; x += 256)
         code[(size_t)gy * tiles_x + x] =
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restr
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
     if (k >= n || code[k] == 0) return;
     const int gy = (int)(k / tiles_x), bx = (int)(k - (size_t)gy * tiles_x);
-    const int ty = row_order[gy], tx = tile_col(bx, gy, tiles_x);
+    const int ty = row_order[gy], tx = bx;
     const uint64_t m = cone[(size_t)ty * tiles_x + tx];
     DispRec r;
     r.cone_lo = (uint32_t)m;
@@ -666,10 +666,10 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
                            v.d_disp);
         // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
         // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
-        // plan runs along dispatch columns and the kernel stores image columns tx .. tx + r - 1: the same thing only
-        // while tile_col() is the identity, so an RT_XCD_SWIZZLE build (columns rotated per row) builds no run table.
+        // plan runs along dispatch columns and the kernel stores image columns tx .. tx + r - 1: the same thing because
+        // dispatch column bx traces image column bx in every row.
         const int run_max = c->knobs.sky_run_max == 0 ? 65535 : c->knobs.sky_run_max;
-        if (!RT_XCD_SWIZZLE && J.cone_calib && c->knobs.sky_tiles && run_max > 1 && v.d_disp_run && J.mode != kModeSS) {
+        if (J.cone_calib && c->knobs.sky_tiles && run_max > 1 && v.d_disp_run && J.mode != kModeSS) {
             const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.d_run_code, RunHead{});
             size_t tmp = v.run_tmp_bytes;
             hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, v.d_tile_rows,

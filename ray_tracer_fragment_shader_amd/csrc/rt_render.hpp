@@ -39,34 +39,11 @@
 #ifndef RT_ABLATE
 #define RT_ABLATE 0                            // instruction-count ablation builds (tools/ablate.sh): 1 prologue, 2 no stores
 #endif
-// __launch_bounds__ minimum waves per EU of the depth <= 3 render kernels.  0 (default): 6 for depth <= 2
-// (<= 80 VGPRs, no spills since the bounce loop stopped carrying the previous ray through the light loop),
-// 5 for depth 3 (<= 96 VGPRs; 6 would spill 8 B/lane).
-#ifndef RT_MINW
-#define RT_MINW 0
-#endif
-#ifndef RT_NT_STORES
-#define RT_NT_STORES 1                         // non-temporal RGBA32F/RGBA8 stores (0: A/B)
-#endif
-// A run of sky tiles (render_body) stores eight tiles at a time as whole rows of 64 pixels (0: tile by tile only; A/B)
-#ifndef RT_RUN_ROW_STORES
-#define RT_RUN_ROW_STORES 1
-#endif
 #ifndef RT_WG_FAST
 #define RT_WG_FAST 64                          // workgroup of the default render kernels: 64 (8 x 8) or 128 (16 x 8)
 #endif
-// RT_PIX_RECOMPUTE=1: the store recomputes the pixel position from an opaque copy of the thread index instead of
-// keeping it live through trace(): 2 VGPRs fewer in the culling kernels, but c3 +2.9% (same-box A/B), so off.
-#ifndef RT_PIX_RECOMPUTE
-#define RT_PIX_RECOMPUTE 0
-#endif
-// ... but in the 7-wave culling kernels it is what keeps the pixel position out of scratch (12 B/lane spilled at
-// the prologue and reloaded for the stores otherwise): on for them.
-#ifndef RT_PIX_RECOMPUTE_CULL
-#define RT_PIX_RECOMPUTE_CULL 1
-#endif
 // The culling variant (>= kConeMin spheres): 7 waves per SIMD (72 VGPRs, 94 SGPRs with 30 spilled to VGPR lanes,
-// 12 B/lane of scratch), which its LDS allows since the last level's colour stays in registers (RT_CULL_LAST_REG:
+// 12 B/lane of scratch), which its LDS allows since the last level's colour stays in registers (colour_slots:
 // 4.5 KB per workgroup at depth 3).  c5 -2.6% serial, -3.9% with 3 frames in flight against the same code at 6
 // waves (77 VGPRs, no scratch; in-process A/B).
 #ifndef RT_MINW_CULL
@@ -74,19 +51,16 @@
 #endif
 // (depth 2 spills 12 B/lane at 7 waves even with the store position recomputed: 6 waves there, 75 VGPRs, no scratch)
 __host__ __device__ constexpr int cull_min_waves(int B) { return B == 2 && RT_MINW_CULL > 6 ? 6 : RT_MINW_CULL; }
-// Default launch-bound waves per SIMD of the fast kernels by depth: 6 up to depth 2, 5 from depth 3.  The bound
-// is a floor: the depth 1 and 2 kernels come out at 63 / 67 VGPRs under it (8 / 7 waves by VGPRs; the c2 kernel
+// Launch-bound waves per SIMD of the bounded fast instances of depth B (the culling ones': cull_min_waves): 6 up to
+// depth 2 (<= 80 VGPRs, no spills since the bounce loop stopped carrying the previous ray through the light loop), 5
+// from depth 3 (<= 96 VGPRs; 6 would spill 8 B/lane).  The bound is a floor: the depth 1 and 2 kernels come out at 63 / 67 VGPRs under it (8 / 7 waves by VGPRs; the c2 kernel
 // accumulates its colour in LDS, shade ACC) and their SGPR cap (rt_render_kernel_sg, 96) gives them 7 waves per
 // SIMD on the hardware; r03's bound of 7 made the compiler trade SGPR spills (v_writelane) for the same VGPRs and
 // ran c2 +2.3% slower (same-box A/B).
-__host__ __device__ constexpr int kDefaultMinWaves(int B) { return B <= 2 ? 6 : 5; }
+__host__ __device__ constexpr int fast_min_waves(int B) { return B <= 2 ? 6 : 5; }
 // RT_MAX_B < 7 (experiment builds only, tools/variants.sh): deeper kernels are not instantiated.
 #ifndef RT_MAX_B
 #define RT_MAX_B 7
-#endif
-// Per-tile cache of the culling kernels' level masks (rt_device.hpp LevelMasks); 0: always computed (A/B builds).
-#ifndef RT_LEVEL_MASKS
-#define RT_LEVEL_MASKS 1
 #endif
 // The most mask slots per tile the cache holds (B ray masks + (B + 1) nl shadow masks); beyond it the masks are computed.
 constexpr int kLevelMaskSlotsMax = 24;
@@ -110,34 +84,13 @@ constexpr int kFmt8_RGBA = 0, kFmt8_RGB = 1, kFmt8_GRAY = 2;  // byte image
 __host__ __device__ constexpr int slot_bytes(int B, bool transp, int wg = kSlotStride, bool cull = false) {
     return (colour_slots(B, transp, cull) * 3 * 8 + (transp ? (B + 1) * 4 : 0)) * wg;
 }
-
-// Image tile column traced at grid column bx of dispatch row gy.  The dispatcher sends workgroup L = gy * tiles_x + bx
-// to XCD L mod 8; with tiles_x a multiple of 8 (every benchmark width) XCD j would trace the same image columns
-// (j mod 8) in every row — a fixed vertical stripe set whose cost depends on the scene (c2: XCDs ending 31.9 to
-// 35.7 us into a 35.7-us launch, wave trace).  RT_XCD_SWIZZLE=1 rotates the columns by gy mod 8, handing each XCD
-// every column class over 8 rows: the XCDs then end within 1.5 us of each other, but c2 runs +1.3% serial, +0.6% in
-// flight (c3, c5 within 0.6%; in-process A/B) — the stripes were not what held the launch's end.  Off.
-#ifndef RT_XCD_SWIZZLE
-#define RT_XCD_SWIZZLE 0
-#endif
-__host__ __device__ __forceinline__ int tile_col(int bx, int gy, int tiles_x) {
-#if RT_XCD_SWIZZLE
-    const int rot = (gy & 7) < tiles_x ? (gy & 7) : 0;
-    const int c = bx + rot;
-    return c >= tiles_x ? c - tiles_x : c;
-#else
-    (void)gy;
-    (void)tiles_x;
-    return bx;
-#endif
-}
+static_assert(slot_bytes(3, false, 64, true) == 4608 && slot_bytes(3, true, 64, true) == slot_bytes(3, true, 64) &&
+                  slot_bytes(3, true, 64) == 7168 && slot_bytes(0, false) == 6144,
+              "the launches' LDS: 3 B doubles per work-item for opaque culling, 3 (B + 1) and B + 1 ints for transparent");
 
 // Slot of dispatch position L (linear workgroup id) in the dispatch table of n positions: grouped by L mod 8, the XCD
 // the round-robin dispatcher sends workgroup L to (up to a per-launch rotation), so each XCD reads a contiguous run
 // of the table and no L2 line is fetched by more than one XCD.
-#ifndef RT_DISP32
-#define RT_DISP32 0
-#endif
 __host__ __device__ __forceinline__ size_t cone_slot(size_t L, size_t n) { return (L & 7) * ((n + 7) >> 3) + (L >> 3); }
 __host__ __device__ __forceinline__ size_t cone_slots(size_t n) { return ((n + 7) >> 3) << 3; }
 
@@ -298,15 +251,11 @@ __device__ __forceinline__ void store_pixel_fmt(int fmt_f, int fmt_8, size_t k, 
         if (PACKED && fmt_f == kFmtF_GRAY) {
             reinterpret_cast<float*>(out32)[k] = (float)col.x;
         } else {
-#if RT_NT_STORES
-            float* o = reinterpret_cast<float*>(out32) + 4 * k;
+            float* o = reinterpret_cast<float*>(out32) + 4 * k;   // (non-temporal: the frame is not read back here)
             __builtin_nontemporal_store((float)col.x, o);
             __builtin_nontemporal_store((float)col.y, o + 1);
             __builtin_nontemporal_store((float)col.z, o + 2);
             __builtin_nontemporal_store(1.0f, o + 3);
-#else
-            reinterpret_cast<float4*>(out32)[k] = make_float4((float)col.x, (float)col.y, (float)col.z, 1.0f);
-#endif
         }
     }
     if (out8) {
@@ -318,13 +267,9 @@ __device__ __forceinline__ void store_pixel_fmt(int fmt_f, int fmt_8, size_t k, 
             o[1] = to_u8(col.y);
             o[2] = to_u8(col.z);
         } else {
-#if RT_NT_STORES
             const uint32_t px = (uint32_t)to_u8(col.x) | ((uint32_t)to_u8(col.y) << 8) |
                                 ((uint32_t)to_u8(col.z) << 16) | (255u << 24);
             __builtin_nontemporal_store(px, reinterpret_cast<uint32_t*>(out8) + k);
-#else
-            reinterpret_cast<uchar4*>(out8)[k] = make_uchar4(to_u8(col.x), to_u8(col.y), to_u8(col.z), 255);
-#endif
         }
     }
 }
@@ -473,20 +418,12 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     // dispatch table (a const __restrict__ kernel argument: a scalar load issued beside the other argument loads),
     // or the identity order.  Padding positions of the last grid.z slice trace a clamped tile and store nothing (no
     // early return: a branch here kept the compiler from issuing the scene loads until the tile had arrived).
-    int tx = tile_col(bxd, gy, P.tiles_x), ty_raw = gy;
+    int tx = bxd, ty_raw = gy;
     uint64_t cone_cached = 0;
     uint32_t sky_cached = 0;
     if (disp) {
-#if RT_DISP32
-        // (32-bit index arithmetic: a frame's dispatch positions number < 2^31; cone_slot's value, fewer scalar ops
-        // on the chain to the wave's first dependent load)
-        const uint32_t n = (uint32_t)geom.n, Lp = (uint32_t)gy * (uint32_t)geom.tiles_x + (uint32_t)bxd;
-        const uint32_t Lc = Lp < n ? Lp : n - 1;
-        const DispRec rec = disp[(Lc & 7u) * ((n + 7u) >> 3) + (Lc >> 3)];   // (padding positions: in bounds, unused)
-#else
         const size_t n = (size_t)geom.n, Lp = (size_t)gy * geom.tiles_x + bxd;
         const DispRec rec = disp[cone_slot(Lp < n ? Lp : n - 1, n)];   // (padding positions: in bounds, unused)
-#endif
         asm volatile("" ::"s"(rec.cone_lo), "s"(rec.cone_hi), "s"(rec.tile), "s"(rec.sky));
         cone_cached = (uint64_t)rec.cone_lo | ((uint64_t)rec.cone_hi << 32);
         sky_cached = rec.sky;
@@ -589,10 +526,10 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
             const uint64_t t_run = __builtin_amdgcn_s_memrealtime();   // the run is known; its stores next
 #endif
             if constexpr (CULL)
-                store_sky_run_call<PACKED, RT_RUN_ROW_STORES != 0>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
+                store_sky_run_call<PACKED, true>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
                                                                    ty_st, run, lane);
             else
-                store_sky_run<PACKED, RT_RUN_ROW_STORES != 0>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
+                store_sky_run<PACKED, true>(late_outputs(), P.width, P.local_rows, P.fmt_f, P.fmt_8, tx,
                                                               ty_st, run, lane);
 #if RT_WAVE_TRACE
             wave_trace(t_run, t_run);
@@ -620,7 +557,7 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
         return;
 #endif
         LevelMasks lm{-1};
-        if (RT_LEVEL_MASKS && !TRANSP && !TREE && P.lmask_stride > 0 && !pad)
+        if (!TRANSP && !TREE && P.lmask_stride > 0 && !pad)
             lm.tile = (ty * P.tiles_x + tx) * P.lmask_stride;
         if constexpr (TREE)
             col = trace_tree<B>(V, eye, sp, &seg, &sh);
@@ -639,12 +576,11 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     if (WG != kThreads || !P.wg_staging) {
         // Direct stores: each wave writes its 8 x 8 block as 8 row segments (128 B of RGBA32F each) and
         // retires without waiting at a workgroup barrier for slower waves of the tile.
+        // The culling kernels recompute the pixel position for the stores from an opaque copy of the thread index
+        // instead of keeping it live through trace(): in their 7-wave instances that is what keeps it out of scratch
+        // (12 B/lane spilled at the prologue and reloaded for the stores otherwise).  The fast kernels keep it live.
         int tid_e = tid;
-#if RT_PIX_RECOMPUTE
-        asm volatile("" : "+v"(tid_e));
-#else
-        if constexpr (CULL && RT_PIX_RECOMPUTE_CULL) asm volatile("" : "+v"(tid_e));
-#endif
+        if constexpr (CULL) asm volatile("" : "+v"(tid_e));
         const int lane_e = tid_e & 63;
         const int i_e = tx * TW + (tid_e >> 6) * bw + (lane_e & 7), lr_e = ty_st * kTileH + (lane_e >> 3);
         if constexpr (SS) {
@@ -742,32 +678,6 @@ void rt_render_kernel_sg(const DispRec* __restrict__ disp, int32_t tiles_x, int3
     render_body<B, 0, MINW, false, CULL, RT_WG_FAST, false, PACKED, false, ACHRO>(gscene, P, disp, DispGeom{tiles_x, n_disp});
 }
 
-// r05: the achromatic depth-2 fast kernel (c3) fits 63 VGPRs, so a cap of 78 SGPRs gives it 8 waves per SIMD (58
-// SGPRs spilled to VGPR lanes): c3 -1.2% against the 96-SGPR instance (tools/ab_libs.py, 9 rounds, same frames); the
-// same cap on the depth-1 kernel (c2) ran +2.5%, so only depth RT_SG8_B takes it.
-#ifndef RT_FAST8_SGPRS
-#define RT_FAST8_SGPRS 78
-#endif
-// r06: off (-1).  After the r06 scalar-stream cuts the plain depth-2 instance needs 94 SGPRs and 64 VGPRs with no
-// spills — 7 waves per SIMD on the hardware (8 need <= 78 SGPRs, above; the compiler reports 8) — and measured c3
-// -0.9% serial, -3.1% in flight against the capped 8-wave one with its 58 spilled SGPRs
-// (profiles/r06/ab/ab_libs_nosg8*.jsonl).
-#ifndef RT_SG8_B
-#define RT_SG8_B -1
-#endif
-#ifndef RT_SG8_MINW
-#define RT_SG8_MINW 8                          // r06: the 8-wave kernel asks for 8 waves (<= 64 VGPRs) explicitly
-#endif
-template <int B, int MINW, bool CULL, bool PACKED, bool ACHRO = true>
-__global__ __launch_bounds__(RT_WG_FAST, (RT_SG8_MINW > MINW ? RT_SG8_MINW : MINW)) __attribute__((amdgpu_num_sgpr(RT_FAST8_SGPRS)))
-void rt_render_kernel_sg8(const DispRec* __restrict__ disp, int32_t tiles_x, int32_t n_disp,
-                          const DevScene* __restrict__ gscene, RenderParams P, void* out32, void* out8, double* out64,
-                          uint32_t* outrc) {
-    render_body<B, 0, MINW, false, CULL, RT_WG_FAST, false, PACKED, false, ACHRO>(gscene, P, disp, DispGeom{tiles_x, n_disp});
-}
-template <int B, bool ACHRO>
-constexpr bool use_sg8() { return ACHRO && B == RT_SG8_B && RT_FAST8_SGPRS > 0; }
-
 // late_outputs() reads the output pointers at offsetof(RenderArgs, ...) of the kernel-argument segment, which lays the
 // kernels' parameters out in order, each at its natural alignment.  The offsets of both kernels' actual parameter
 // lists are computed here from their types and compared with RenderArgs: adding, reordering or re-typing a parameter
@@ -799,8 +709,6 @@ static_assert(kernarg_offsets_match(decltype(&rt_render_kernel<1, 0, 1, false, f
               "rt_render_kernel's parameters must lay out as RenderArgs (late_outputs)");
 static_assert(kernarg_offsets_match(decltype(&rt_render_kernel_sg<1, 1, false, false>){}),
               "rt_render_kernel_sg's parameters must lay out as RenderArgs (late_outputs)");
-static_assert(kernarg_offsets_match(decltype(&rt_render_kernel_sg8<1, 1, false, false>){}),
-              "rt_render_kernel_sg8's parameters must lay out as RenderArgs (late_outputs)");
 
 // rayTraceRay on a list of rays Line(starts[k], ends[k]).  Rays from arbitrary starts: whether their hit
 // points may skip the bounding-sphere cull is decided per ray (hits_ok_from).
@@ -881,9 +789,6 @@ struct ScreenArgs {
 #define RT_SG_MAX_B 2
 #endif
 // The achromatic (one-channel, rt_device.hpp shade ACHRO) instances: the benchmark depths' fast and culling kernels.
-#ifndef RT_ACHRO
-#define RT_ACHRO 1
-#endif
 #ifndef RT_ACHRO_MAX_B
 #define RT_ACHRO_MAX_B 3
 #endif
@@ -891,14 +796,12 @@ struct ScreenArgs {
 #ifndef RT_SS
 #define RT_SS (RT_WG_FAST == 64)
 #endif
-// Launch-bound waves per SIMD of the bounded fast instances of depth B (the culling ones': cull_min_waves).
-constexpr int fast_min_waves(int B) { return RT_MINW != 0 ? RT_MINW : kDefaultMinWaves(B); }
 
 // ---- Which instance of the render kernels a frame runs: the key, the selector (here), the list (below) ----
 
 // An instance's key: the kernel template and exactly its template arguments after the depth B.  (The SGPR-capped
-// templates take MINW, CULL, PACKED and ACHRO; their bodies fix the other fields, RenderRow checks which values.)
-enum RenderTemplate { kKernel = 0, kKernelSg = 1, kKernelSg8 = 2 };   // rt_render_kernel, .._sg, .._sg8
+// template takes MINW, CULL, PACKED and ACHRO; its body fixes the other fields, RenderRow checks which values.)
+enum RenderTemplate { kKernel = 0, kKernelSg = 1 };   // rt_render_kernel, rt_render_kernel_sg
 struct RenderKey {
     int kernel;                                // RenderTemplate
     int LDS, MINW;
@@ -931,7 +834,7 @@ inline RenderRoute render_route(const RouteScene& s, const RouteKnobs& k, int de
     const bool plain = mode == kModePlain, ss = mode == kModeSS;
     // bounded (MINW > 1): depth <= 3; plain frames and the level-mask launch only with RT_MIN_WAVES >= 5
     const bool bounded = depth <= 3 && (k.min_waves >= 5 || !(plain || level_mask));
-    const bool achro = RT_ACHRO && s.achromatic && !s.transparent && !s.tree && !k.achro_off && !ss &&
+    const bool achro = s.achromatic && !s.transparent && !s.tree && !k.achro_off && !ss &&
                        depth <= RT_ACHRO_MAX_B && bounded;
     const bool frame = !level_mask, knobs = plain && frame;   // (packed and supersampled frames take no A/B knob)
     RenderKey K{kKernel, 0, 1, false, false, 64, false, mode == kModePacked && frame, false, false, ss && frame};
@@ -953,10 +856,9 @@ inline RenderRoute render_route(const RouteScene& s, const RouteKnobs& k, int de
         K.CULL = level_mask || s.n_padded >= kConeMin;
         K.WG = RT_WG_FAST;
         K.MINW = !bounded ? 1 : K.CULL ? cull_min_waves(depth) : fast_min_waves(depth);
-        K.FIX64 = K.CULL && RT_CULL_FIX64 && s.n_stride == kCullStride;
+        K.FIX64 = K.CULL && s.n_stride == kCullStride;
         K.ACHRO = achro;
-        if (!K.CULL && !ss && bounded && depth <= RT_SG_MAX_B && RT_FAST_SGPRS > 0)   // the SGPR-capped templates
-            K.kernel = achro && depth == RT_SG8_B && RT_FAST8_SGPRS > 0 ? kKernelSg8 : kKernelSg;
+        if (!K.CULL && !ss && bounded && depth <= RT_SG_MAX_B && RT_FAST_SGPRS > 0) K.kernel = kKernelSg;   // the SGPR cap
         lds = slot_bytes(depth, false, RT_WG_FAST, K.CULL);
     }
     return RenderRoute{K, lds, K.WG == kThreads ? kTileW : RT_WG_FAST / 8};
@@ -1019,7 +921,7 @@ inline int trace_variant(bool tree, bool transparent) { return tree ? 2 : transp
 
 // ---- The per-depth instance files' bodies ----
 
-// The three kernel templates share one parameter list (RenderArgs), so one pointer type holds any instance.
+// The two kernel templates share one parameter list (RenderArgs), so one pointer type holds any instance.
 using RenderKernelFn = void (*)(const DispRec*, int32_t, int32_t, const DevScene*, RenderParams, void*, void*, double*,
                                 uint32_t*);
 
@@ -1031,12 +933,11 @@ struct RenderRow {
     static constexpr bool on = ON;
     static constexpr RenderKey key{KERNEL, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS};
     static_assert(KERNEL == kKernel || (LDS == 0 && !TRANSP && WG == RT_WG_FAST && !TREE && !FIX64 && !SS),
-                  "the SGPR-capped kernels' bodies fix these fields");
+                  "the SGPR-capped kernel's body fixes these fields");
     template <int B>
     static RenderKernelFn kernel() {
         if constexpr (!ON) return nullptr;
         else if constexpr (KERNEL == kKernelSg) return rt_render_kernel_sg<B, MINW, CULL, PACKED, ACHRO>;
-        else if constexpr (KERNEL == kKernelSg8) return rt_render_kernel_sg8<B, MINW, CULL, PACKED, ACHRO>;
         else return rt_render_kernel<B, LDS, MINW, TRANSP, CULL, WG, TREE, PACKED, FIX64, ACHRO, SS>;
     }
 };
@@ -1051,12 +952,11 @@ template <int B>
 struct RenderInstances {
     static constexpr bool kAll = B <= RT_MAX_B;                               // (experiment builds stop earlier)
     static constexpr bool kSg = kAll && B <= RT_SG_MAX_B && RT_FAST_SGPRS > 0;
-    static constexpr bool kAc = kAll && RT_ACHRO && B <= RT_ACHRO_MAX_B;
+    static constexpr bool kAc = kAll && B <= RT_ACHRO_MAX_B;
     static constexpr bool kSs = kAll && RT_SS;
     static constexpr int F = RT_WG_FAST, T = kThreads;
     static constexpr int MW = fast_min_waves(B), MC = cull_min_waves(B);     // bounded: plain and achromatic rows
     static constexpr int PW = B <= 3 ? MW : 1, PC = B <= 3 ? MC : 1;          // packed and supersampled rows
-    static constexpr int SGA = use_sg8<B, true>() ? kKernelSg8 : kKernelSg;   // the achromatic rows' capped template
     using rows = RenderRows<
         //        ON    template   LDS MINW TRANSP CULL WG TREE PACKED FIX64 ACHRO SS
         RenderRow<kSg,  kKernelSg,  0,  MW,  0,    0,   F>,                             // fast, bounded, SGPR cap
@@ -1072,7 +972,7 @@ struct RenderInstances {
         RenderRow<kAll, kKernel,    0,  MW,  0,    0,   T>,                             // A/B: staged stores, bounded *
         RenderRow<kAll, kKernel,    0,  1,   0,    0,   T>,                             // A/B: staged stores, any waves
         // achromatic (one channel)
-        RenderRow<kSg && kAc, SGA,  0,  MW,  0,    0,   F,  0,   0,     0,    1>,       // fast, SGPR cap
+        RenderRow<kSg && kAc, kKernelSg, 0,  MW,  0,    0,   F,  0,   0,     0,    1>,       // fast, SGPR cap
         RenderRow<kAc,  kKernel,    0,  MW,  0,    0,   F,  0,   0,     0,    1>,       // fast *
         RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   0,     1,    1>,       // culling, stride 64
         RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   0,     0,    1>,       // culling
@@ -1083,7 +983,7 @@ struct RenderInstances {
         RenderRow<kAll, kKernel,    0,  PC,  0,    1,   F,  0,   1>,                    // culling
         RenderRow<kAll, kKernel,    0,  1,   1,    0,   64, 0,   1>,                    // transparent
         RenderRow<kAll, kKernel,    0,  1,   1,    0,   64, 1,   1>,                    // ray tree
-        RenderRow<kSg && kAc, SGA,  0,  MW,  0,    0,   F,  0,   1,     0,    1>,       // achromatic fast, SGPR cap
+        RenderRow<kSg && kAc, kKernelSg, 0,  MW,  0,    0,   F,  0,   1,     0,    1>,       // achromatic fast, SGPR cap
         RenderRow<kAc,  kKernel,    0,  MW,  0,    0,   F,  0,   1,     0,    1>,       // achromatic fast *
         RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   1,     1,    1>,       // achromatic culling, stride 64
         RenderRow<kAc,  kKernel,    0,  MC,  0,    1,   F,  0,   1,     0,    1>,       // achromatic culling

@@ -135,7 +135,7 @@ def _board_edge_rays():
 
 @pytest.mark.parametrize("name", ["c3", "c5"])
 def test_board_position_shortcut_edges(tr, name):
-    """The board decided by its hit point's position (board_hit, RT_BOARD_POS) equals the reference's barycentric
+    """The board decided by its hit point's position (board_hit) equals the reference's barycentric
     tests on both sides of the margin, on the diagonal and far away: hits, points and colours, bit for bit."""
     cfg = scenes.CONFIGS[name]
     tr.set_scene(cfg.scene())
