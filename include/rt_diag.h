@@ -99,6 +99,26 @@ int rt_diag_sky_count(rt_ctx* ctx, int* tiles, int* sky);
 int rt_diag_sky_run_plan(const uint8_t* sky, int tiles_x, int tiles_y, int run_max, int32_t* run, int* positions);
 int rt_diag_disp_count(rt_ctx* ctx, int* positions, int* tiles, int* run_max);
 
+/* Tile classes: the calibration of a static view of a fast-kernel scene (8 .. 15 padded spheres, opaque, no meshes) with
+ * level masks marks every tracing tile whose primary cone mask and level masks keep no sphere as sphere-free, and the
+ * cached renders of that view trace such a tile without the sphere code (RT_TILE_CLASSES=0 in the environment of
+ * rt_ctx_create leaves every dispatch record unmarked; the images are the same bytes either way).
+ * rt_diag_tile_class_plan evaluates the decision on the host, no device needed, with the function the device runs: for
+ * `tiles` tiles with the cone masks cone[t], the sky verdicts sky[t] (nonzero: sky; null: none) and `slots` level masks
+ * each, masks[t * slots + k] (null when slots = 0), of a scene of n_spheres <= 64 (padded) spheres, out[t] = 1 when
+ * tile t is sphere-free — not sky, and no bit below n_spheres set in its cone mask or in any of its slots — else 0.
+ * RT_EINVAL for bad arguments (null cone or out, tiles < 0, slots < 0, slots > 0 without masks, n_spheres outside
+ * 0 .. 64).
+ * rt_diag_tile_classes: the classes of this context's last calibrated view as its calibration decided them (whatever
+ * RT_TILE_CLASSES says about carrying them in the records) — *tiles the view's tile count, *sky and *sphere_free how
+ * many are in each class.  All 0 when the calibrated view holds no classes (culling-kernel scenes, views without level
+ * masks, no calibrated view).  rt_diag_tile_class_grid copies the grid out, out[ty * tiles_x + tx] = 0 a tracing tile,
+ * 1 sky, 2 sphere-free; RT_EINVAL unless n is that tile count.  Both wait for the device. */
+int rt_diag_tile_class_plan(const uint64_t* cone, const uint8_t* sky, const uint64_t* masks, int tiles, int slots,
+                            int n_spheres, uint8_t* out);
+int rt_diag_tile_classes(rt_ctx* ctx, int* tiles, int* sky, int* sphere_free);
+int rt_diag_tile_class_grid(rt_ctx* ctx, uint8_t* out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,10 +217,14 @@ SIGNATURES = {
     "rt_diag_sky_count": (c_int, [c_void_p, _P(c_int), _P(c_int)]),
     "rt_diag_sky_run_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _P(c_int)]),
     "rt_diag_disp_count": (c_int, [c_void_p, _P(c_int), _P(c_int), _P(c_int)]),
+    "rt_diag_tile_class_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "rt_diag_tile_classes": (c_int, [c_void_p, _P(c_int), _P(c_int), _P(c_int)]),
+    "rt_diag_tile_class_grid": (c_int, [c_void_p, c_void_p, ctypes.c_size_t]),
 }
 
 _DIAG = {"rt_diag_tile_order", "rt_diag_kernel_resources", "rt_diag_kernel_occupancy", "rt_diag_copy_path",
-         "rt_diag_render_route", "rt_diag_sky_tiles", "rt_diag_sky_count", "rt_diag_sky_run_plan", "rt_diag_disp_count"}
+         "rt_diag_render_route", "rt_diag_sky_tiles", "rt_diag_sky_count", "rt_diag_sky_run_plan", "rt_diag_disp_count",
+         "rt_diag_tile_class_plan", "rt_diag_tile_classes", "rt_diag_tile_class_grid"}
 _lib = None
 
 

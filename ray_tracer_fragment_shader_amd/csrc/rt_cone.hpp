@@ -228,4 +228,19 @@ RT_HD int sky_run_at(int n, int run_max, int x, Sky sky) {
     return len;
 }
 
+// The class of one tile of a calibrated view, decided where its dispatch record is built (rt_plain.hip rt_class_kernel on
+// the device, rt_diag_tile_class_plan on the host): the tile is sphere-free when it traces (not sky) and neither its
+// primary cone mask nor any of its `slots` level masks (rt_device.hpp LevelMasks: the ray masks of levels 1 .. B, the
+// shadow masks of every light at every level; a slot no wave reached reads 0) keeps one of the scene's np <= 64 (padded)
+// spheres.  Every mask is conservative — a clear bit proves that no ray of the tile's wave at that level can meet the
+// sphere — so no primary, reflected or shadow ray of such a tile touches a sphere, and the fast kernels trace it without
+// the sphere code (rt_render.hpp render_body).  Bits at or above np are ignored.
+RT_HD bool tile_sphere_free(uint64_t cone, bool sky, const uint64_t* masks, int slots, int np) {
+    if (sky || np > 64) return false;
+    uint64_t any = cone;
+    for (int k = 0; k < slots; ++k) any |= masks[k];
+    const uint64_t bits = np >= 64 ? ~0ull : ((1ull << (np < 0 ? 0 : np)) - 1);
+    return (any & bits) == 0;
+}
+
 }  // namespace rt

@@ -38,6 +38,7 @@ struct RenderParams;
 
 constexpr int kOrderMax = 8192;                // tile rows rt_order_kernel sorts (one workgroup, keys in LDS)
 constexpr int kRecalibrate = 8;                // renders of a moving camera per re-timing of the tile rows
+constexpr uint8_t kClassTrace = 0, kClassSky = 1, kClassSphereFree = 2;   // rt_ctx::View::d_tile_class
 
 struct rt_ctx {
     int device = 0;
@@ -90,6 +91,10 @@ struct rt_ctx {
         // without tracing.  RT_SKY_TILES=0: every wave traces (A/B; the images are the same bytes).
         bool sky_tiles = true;
         int sky_run_max = 16;                  // RT_SKY_RUN_MAX: adjacent sky tiles per run (1: no run table, 0: whole streaks)
+        // Sphere-free tiles (rt_cone.hpp tile_sphere_free): a fast-kernel view's calibration marks them in its dispatch
+        // records and cached renders trace them without the sphere code.  RT_TILE_CLASSES=0: no record is marked (A/B;
+        // the images are the same bytes).
+        bool tile_classes = true;
         bool achro_off = false;                // RT_ACHRO_OFF=1: the three-channel kernels for achromatic scenes (A/B)
         int sd_split = 2;                      // RT_SDMA_SPLIT: engines a frame's copy is split over (1, 2)
         int sd_writer_req = 0;                 // RT_SDMA_WRITER (A/B): 1 or 2 forces the writer, 0 tries 2 then 1
@@ -147,6 +152,12 @@ struct rt_ctx {
         // The calibration render leaves its waves' sky verdicts behind the cone masks in d_cone_tile (sky_tiles_n of
         // them: rt_diag_sky_count).
         size_t sky_tiles_n = 0;
+        // The tile classes of view order_key (rt_class_kernel; `cap` bytes): 0 a tracing tile, 1 sky, 2 sphere-free.
+        // View state like the masks they are made from: rebuilt by every calibration (class_tiles_n tiles; 0: the view
+        // has none — a culling-kernel scene, no level masks), read by rt_disp_kernel / rt_run_disp_kernel, which set the
+        // class bit of a sphere-free tile's record unless RT_TILE_CLASSES=0, and by rt_diag_tile_classes.
+        uint8_t* d_tile_class = nullptr;
+        size_t class_tiles_n = 0;
         // Runs of sky tiles (rt_run_plan_kernel): beside d_disp the calibration of a view in tile-row order builds
         // d_disp_run, one position per run of up to Knobs::sky_run_max adjacent sky tiles, from the per-position codes
         // d_run_code and their prefix sum d_run_num (hipcub, d_run_tmp).

@@ -628,10 +628,13 @@ __device__ __forceinline__ void sphere_batch_closest(const SceneView& V, const R
 // skip = origin_skip of r's origin: 0 skips the board test, 1 + k sphere k's (certain misses).
 // from_hit: r starts at a hit point, which passes the cull when S->hits_inside (host-proven).
 // MOTION, mo: the lane's sphere centres (struct Motion); generic path only.
-template <bool FULL, bool CULL = false, bool MOTION = false>
+// NOSPH (sphere-free tiles, trace): at most 64 spheres and `mask` keeps none of them, so every batch below would be
+// skipped: the sphere loop is not compiled.
+template <bool FULL, bool CULL = false, bool MOTION = false, bool NOSPH = false>
 __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3* hp, uint64_t mask = ~0ull,
                                            int skip = -1, bool from_hit = false, const Motion* mo = nullptr) {
     static_assert(!(MOTION && CULL), "moving spheres take the generic path");
+    static_assert(!NOSPH || (!FULL && !CULL && !MOTION), "sphere-free tiles: the fast opaque kernels");
     const DevScene* S = V.S;
     if (!(from_hit && V.hits_ok) && !bound_pass(S, r.p0, r.u)) return -1;
     int kind = -1;
@@ -656,7 +659,7 @@ __device__ __forceinline__ int closest_hit(const SceneView& V, const Ray& r, d3*
         }
         k0 = 64;
     }
-    for (; k0 < V.np; k0 += kChunk) {
+    for (; !NOSPH && k0 < V.np; k0 += kChunk) {
         // (a batch none of whose spheres the mask keeps is missed by every ray of the wave: the cached masks of the
         // fast kernels, LevelMasks; ~0 otherwise)
         if (k0 < 64 && ((mask >> k0) & ((1ull << kChunk) - 1)) == 0) continue;
@@ -691,7 +694,9 @@ __device__ __forceinline__ void primary_sphere(const SceneView& V, const Ray& r,
 // mask) and the scene has no meshes, so only
 // the board can be hit and the direction u = unit(d) (the board test uses d) is computed here for the lanes that
 // hit it — the rest miss and never read it.
-template <bool FULL>
+// NOSPH (sphere-free tiles, trace): lazy_u holds by construction — kPrimaryConeMin .. 64 spheres, none in `cone` — so
+// both sphere loops would run no iteration and are not compiled.
+template <bool FULL, bool NOSPH = false>
 __device__ __forceinline__ int closest_hit_primary(const SceneView& V, Ray& r, uint64_t cone, d3* hp,
                                                    bool lazy_u = false) {
     const DevScene* S = V.S;
@@ -703,12 +708,12 @@ __device__ __forceinline__ int closest_hit_primary(const SceneView& V, Ray& r, u
     }
     const double eps = S->eps;
     int k0 = 0;
-    if (V.np >= kPrimaryConeMin) {
+    if (!NOSPH && V.np >= kPrimaryConeMin) {
         for (uint64_t m = cone & sphere_bits(V.np); m; m &= m - 1)
             primary_sphere(V, r, __builtin_ctzll(m), eps, &kind, &best, hp);
         k0 = 64;
     }
-    for (; k0 < V.np; k0 += kChunk) {
+    for (; !NOSPH && k0 < V.np; k0 += kChunk) {
         uint32_t pass = 0;
 #pragma unroll
         for (int j = 0; j < kChunk; ++j) {
@@ -910,7 +915,8 @@ __device__ __forceinline__ uint64_t shadow_bundle_mask(const SceneView& V, bool 
 // lane that found a blocker leaves the loops; the board is tested by the lanes still unblocked).  occluded_ret: the
 // returns.  occluded<.., FLAT> picks the form per instance (shade: the three-channel culling kernels keep the returns —
 // the flag form spills 32 VGPRs to scratch in their depth-3 instance).
-template <bool FULL, bool CULL = false>
+// NOSPH (sphere-free tiles, trace): at most 64 spheres and `mask` keeps none: the sphere loops are not compiled.
+template <bool FULL, bool CULL = false, bool NOSPH = false>
 __device__ __forceinline__ bool occluded_flag(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                               int skip = -1) {
     const DevScene* S = V.S;
@@ -936,7 +942,7 @@ __device__ __forceinline__ bool occluded_flag(const SceneView& V, const Ray& r, 
         }
         k0 = 64;
     }
-    for (; k0 < V.np; k0 += kChunk) {
+    for (; !NOSPH && k0 < V.np; k0 += kChunk) {
         if (k0 < 64 && ((mask >> k0) & ((1ull << kChunk) - 1)) == 0) continue;   // (cached masks, as closest_hit)
         uint32_t pass = 0;
 #pragma unroll
@@ -971,7 +977,7 @@ __device__ __forceinline__ bool occluded_flag(const SceneView& V, const Ray& r, 
     return blocked;
 }
 
-template <bool FULL, bool CULL = false>
+template <bool FULL, bool CULL = false, bool NOSPH = false>
 __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                              int skip = -1) {
     const DevScene* S = V.S;
@@ -996,7 +1002,7 @@ __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, i
         }
         k0 = 64;
     }
-    for (; k0 < V.np; k0 += kChunk) {
+    for (; !NOSPH && k0 < V.np; k0 += kChunk) {
         if (k0 < 64 && ((mask >> k0) & ((1ull << kChunk) - 1)) == 0) continue;   // (cached masks, as closest_hit)
         uint32_t pass = 0;
 #pragma unroll
@@ -1031,11 +1037,12 @@ __device__ __forceinline__ bool occluded_ret(const SceneView& V, const Ray& r, i
     return false;
 }
 
-template <bool FULL, bool CULL, bool FLAT>
+template <bool FULL, bool CULL, bool FLAT, bool NOSPH = false>
 __device__ __forceinline__ bool occluded(const SceneView& V, const Ray& r, int li, uint64_t mask = ~0ull,
                                          int skip = -1) {
-    if constexpr (FLAT) return occluded_flag<FULL, CULL>(V, r, li, mask, skip);
-    else return occluded_ret<FULL, CULL>(V, r, li, mask, skip);
+    static_assert(!NOSPH || (!FULL && !CULL), "sphere-free tiles: the fast opaque kernels");
+    if constexpr (FLAT) return occluded_flag<FULL, CULL, NOSPH>(V, r, li, mask, skip);
+    else return occluded_ret<FULL, CULL, NOSPH>(V, r, li, mask, skip);
 }
 
 // The same shadow test for a ray whose end is NOT the stored light position (area lights, shade AREA: the light point
@@ -1175,8 +1182,10 @@ struct LightShift {
     double x, z;
 };
 // MOTION, mo (with AREA): the shadow tests run on the lane's sphere centres (struct Motion).
+// NOSPH (sphere-free tiles, trace): every shadow mask of the tile keeps no sphere, so none is read and occluded tests
+// the board alone.
 template <bool FULL, bool CULL, bool ACC = false, int SS = 256, bool ACHRO = false, bool AREA = false,
-          bool MOTION = false>
+          bool MOTION = false, bool NOSPH = false>
 __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, int mat, double ks,
                                     int skip = -1, double* acc = nullptr, const LevelMasks* lm = nullptr,
                                     int lslot = 0, LightShift ls = LightShift{0.0, 0.0},
@@ -1219,7 +1228,7 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
                 uint64_t* out = t >= 0 ? level_masks_out() : nullptr;
                 if (out && __lane_id() == 0) out[t + lslot + i] = m;
             }
-        } else if (!CULL && !FULL && t >= 0) {
+        } else if (!NOSPH && !CULL && !FULL && t >= 0) {
             // fast kernels: the cached mask lets occluded skip the filter batches no ray of the wave can meet
             const uint64_t* in = level_masks_in();
             if (in) m = in[t + lslot + i];
@@ -1228,7 +1237,7 @@ __device__ __forceinline__ d3 shade(const SceneView& V, bool hit, d3 p, d3 n, in
         if (hit)
             lit = !(FULL ? occluded_transparent<MOTION>(V, sr, mo)
                     : AREA ? occluded_anywhere<MOTION>(V, sr, skip, mo)
-                           : occluded<false, CULL, ACHRO || !CULL>(V, sr, i, m, skip));
+                           : occluded<false, CULL, ACHRO || !CULL, NOSPH>(V, sr, i, m, skip));
         if (lit && ACHRO) {                                 // R only (same operations as below, channel x)
             const double a = S->att / (S->att + dl * dl);   // attenuation (:1181)
             const double lc = a * S->light[i].col[0];       // :1223
@@ -1415,14 +1424,20 @@ __device__ __forceinline__ bool cull_level(const SceneView& V, int lvl, bool fir
 
 // AREA: every light displaced by `ls` for this lane (shade AREA); generic path only (no PRIMARY, no CULL, no masks).
 // MOTION: every sphere at this lane's own centre (struct Motion); with AREA only.
+// NOSPH (render_body's sphere-free branch; fast opaque kernels, cached views): the tile's class says that neither `cone`
+// nor any of the tile's level masks keeps a sphere of a scene of kPrimaryConeMin .. 64, so lazy_u holds, every cached
+// mask would read 0 and every sphere loop would run no iteration: the masks are not read and the loops not compiled.
+// Everything else — board tests, surface, shade, origin skips, the bounding-sphere culls, the LDS slots, the ray
+// counts — is the general path's code in its order, on the same values.
 template <int B, bool PRIMARY, bool TRANSP, bool CULL, int SS = kSlotStride, bool ACHRO = false, bool AREA = false,
-          bool MOTION = false>
+          bool MOTION = false, bool NOSPH = false>
 __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t cone,
                                     uint32_t* seg, uint32_t* shadow, double* slot, int* mslot,
                                     LevelMasks lm = LevelMasks{-1}, LightShift ls = LightShift{0.0, 0.0},
                                     const Motion* mo = nullptr) {
     static_assert(!(AREA && (PRIMARY || CULL || ACHRO)), "area lights take the generic path");
     static_assert(!MOTION || AREA, "moving spheres take the generic path, with the area lights' shadow tests");
+    static_assert(!NOSPH || (PRIMARY && !TRANSP && !CULL && !AREA), "sphere-free tiles: the fast opaque kernels");
     const DevScene* S = V.S;
     int levels = 0;
     Ray r;
@@ -1431,8 +1446,8 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
     // A primary ray of a wave whose cone mask keeps no sphere can only hit the board: its direction is computed
     // by closest_hit_primary for the lanes that hit (sky waves skip the normalisation).
     // (spheres past the first 64 are not in the mask: scenes with more always normalise)
-    const bool lazy_u = PRIMARY && !TRANSP && V.np >= kPrimaryConeMin && V.np <= 64 &&
-                        (cone & sphere_bits(V.np)) == 0;
+    const bool lazy_u = NOSPH || (PRIMARY && !TRANSP && V.np >= kPrimaryConeMin && V.np <= 64 &&
+                                  (cone & sphere_bits(V.np)) == 0);
     if (lazy_u) r.d = d;
     else set_dir(&r, d, unit(d));
     // rays traced (seg, shadow) follow from `levels`: every lane traces levels 0 .. min(levels, B), nl shadow rays per hit
@@ -1455,17 +1470,21 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
             int kind = -1;
             if (alive) {
                 if (first) {
-                    kind = closest_hit_primary<TRANSP>(V, r, cone, &p, lazy_u);
+                    kind = closest_hit_primary<TRANSP, NOSPH>(V, r, cone, &p, lazy_u);
                 } else {
                     set_origin_f32(S, &r);
                     uint64_t rm = ~0ull;                    // this tile's cached level-lvl ray mask (LevelMasks)
-                    if (!TRANSP && lm.tile >= 0) {
+                    if (!NOSPH && !TRANSP && lm.tile >= 0) {
                         const uint64_t* in = level_masks_in();
                         if (in) rm = in[lm.tile + lvl - 1];
                     }
-                    kind = closest_hit<TRANSP, false, MOTION>(V, r, &p, rm, TRANSP ? -1 : skip, lvl > 0, mo);
+                    kind = closest_hit<TRANSP, false, MOTION, NOSPH>(V, r, &p, rm, TRANSP ? -1 : skip, lvl > 0, mo);
                 }
             }
+            // (sphere-free: the kind is the board's or none, which the compiler would turn into lane masks — hit, the
+            // origin skip, the level count — held in SGPR pairs across the light loop: 6 SGPR spills and with them a
+            // 65th VGPR in the depth-1 kernel that sits at its 96-SGPR cap; kept the per-lane value of the general path)
+            if constexpr (NOSPH) asm volatile("" : "+v"(kind));
             const bool hit = kind >= 0;
             skip = kSkip ? origin_skip<MOTION>(V, kind, r.p0, p, mo) : -1;   // this hit's rays start at p
             d3 nd = mk(0.0, 0.0, 0.0);
@@ -1496,7 +1515,7 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
                     ndsl[2 * SS] = nd.z;
                     asm volatile("" ::: "memory");          // keep it in LDS across the light loop
                 }
-                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA, MOTION>(V, true, p, n, mat, ks, skip, psl, &lm,
+                const d3 c = shade<TRANSP, false, kAcc, SS, ACHRO, AREA, MOTION, NOSPH>(V, true, p, n, mat, ks, skip, psl, &lm,
                                                                                  B + lvl * V.nl, ls, mo);
                 if (lvl < B) {
                     asm volatile("" ::: "memory");

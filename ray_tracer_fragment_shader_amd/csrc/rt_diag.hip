@@ -39,6 +39,37 @@ extern "C" int rt_diag_sky_count(rt_ctx* c, int* tiles, int* sky) {
     return RT_OK;
 }
 
+// Diagnostics (include/rt_diag.h): the tile classes the last calibration decided (rt_plain.hip rt_class_kernel), copied
+// out and counted on the host.  grid (or nullptr): n bytes for the view's n tiles.
+static int tile_classes(rt_ctx* c, uint8_t* grid, size_t n, bool sized, int* tiles, int* sky, int* sphere_free) {
+    *tiles = *sky = *sphere_free = 0;
+    const size_t have = c->view.order_valid && c->view.cone_valid ? c->view.class_tiles_n : 0;
+    if (sized && n != have) return rt_fail(RT_EINVAL, "rt_diag_tile_class_grid: n is not the calibrated view's tile count");
+    if (have == 0) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipDeviceSynchronize());
+    std::vector<uint8_t> v(have);
+    RT_HIP(hipMemcpy(v.data(), c->view.d_tile_class, have, hipMemcpyDeviceToHost));
+    for (uint8_t x : v) {
+        *sky += x == kClassSky;
+        *sphere_free += x == kClassSphereFree;
+    }
+    *tiles = (int)have;
+    if (grid) memcpy(grid, v.data(), have);
+    return RT_OK;
+}
+
+extern "C" int rt_diag_tile_classes(rt_ctx* c, int* tiles, int* sky, int* sphere_free) {
+    if (!c || !tiles || !sky || !sphere_free) return rt_fail(RT_EINVAL, "rt_diag_tile_classes: bad args");
+    return tile_classes(c, nullptr, 0, false, tiles, sky, sphere_free);
+}
+
+extern "C" int rt_diag_tile_class_grid(rt_ctx* c, uint8_t* out, size_t n) {
+    if (!c || !out) return rt_fail(RT_EINVAL, "rt_diag_tile_class_grid: bad args");
+    int tiles, sky, sphere_free;
+    return tile_classes(c, out, n, true, &tiles, &sky, &sphere_free);
+}
+
 // Diagnostics (include/rt_diag.h): the dispatch positions of the last cached render of the calibrated view.
 extern "C" int rt_diag_disp_count(rt_ctx* c, int* positions, int* tiles, int* run_max) {
     if (!c || !positions || !tiles || !run_max) return rt_fail(RT_EINVAL, "rt_diag_disp_count: bad args");

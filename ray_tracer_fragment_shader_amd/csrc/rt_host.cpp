@@ -868,6 +868,20 @@ extern "C" int rt_diag_sky_run_plan(const uint8_t* sky, int tiles_x, int tiles_y
     return RT_OK;
 }
 
+// The class of every tile (include/rt_diag.h), through the function the device's class kernel runs (rt_cone.hpp
+// tile_sphere_free).
+extern "C" int rt_diag_tile_class_plan(const uint64_t* cone, const uint8_t* sky, const uint64_t* masks, int tiles,
+                                       int slots, int n_spheres, uint8_t* out) {
+    if (!cone || !out || tiles < 0 || slots < 0 || (slots > 0 && !masks) || n_spheres < 0 || n_spheres > 64)
+        return rt_fail(RT_EINVAL, "rt_diag_tile_class_plan: bad arguments");
+    for (int t = 0; t < tiles; ++t)
+        out[t] = rt::tile_sphere_free(cone[t], sky && sky[t] != 0, slots > 0 ? masks + (size_t)t * slots : nullptr, slots,
+                                      n_spheres)
+                     ? 1
+                     : 0;
+    return RT_OK;
+}
+
 extern "C" int rt_write_ppm(const char* path, const uint8_t* px, int W, int H, int channels) {
     // writePpmScreenshot (Hw4/ppm.cpp:15-25): header "P6 W H 255\n", then the bottom-up GL image's rows
     // written top-down (image[3*w*(h-1-i)]).

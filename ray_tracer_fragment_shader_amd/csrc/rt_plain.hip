@@ -71,9 +71,11 @@ __global__ __launch_bounds__(256) void rt_iota_kernel(int32_t* __restrict__ v, i
 // bx of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
 // `cone` (else 0), and their sky verdicts (cone[n + tile], n the tile count).  Stored at cone_slot(L): grouped by the
 // XCD workgroup L runs on.
+// `cls` (or nullptr): the view's tile classes (rt_class_kernel); a sphere-free tile's record carries kDispSphereFree.
 __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict__ row_order,
                                                       const int32_t* __restrict__ by_pos,
-                                                      const uint64_t* __restrict__ cone, int tiles_x, int tiles_y,
+                                                      const uint64_t* __restrict__ cone,
+                                                      const uint8_t* __restrict__ cls, int tiles_x, int tiles_y,
                                                       DispRec* __restrict__ disp) {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
     if (k >= n) return;
@@ -93,7 +95,21 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     r.cone_hi = (uint32_t)(m >> 32);
     r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
     r.sky = cone ? (uint32_t)cone[n + (size_t)ty * tiles_x + tx] : 0;   // (the verdicts follow the n masks)
+    if (cls && cls[(size_t)ty * tiles_x + tx] == kClassSphereFree) r.sky = kDispSphereFree;   // (not sky: sky was 0)
     disp[cone_slot(k, n)] = r;
+}
+
+// The class of every tile of a fast-kernel view (rt_ctx::View::d_tile_class), from what its calibration left: the cone
+// masks and sky verdicts of the calibration render (cone, then n verdicts) and the `slots` level masks per tile of the
+// level-mask launch, whose buffer was zeroed before that launch, so a slot no wave reached reads 0.
+__global__ __launch_bounds__(256) void rt_class_kernel(const uint64_t* __restrict__ cone,
+                                                       const uint64_t* __restrict__ lmask, int slots, int np, int n,
+                                                       uint8_t* __restrict__ cls) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const bool sky = cone[(size_t)n + t] != 0;
+    cls[t] = sky ? kClassSky
+                 : tile_sphere_free(cone[t], false, lmask + (size_t)t * slots, slots, np) ? kClassSphereFree : kClassTrace;
 }
 
 // The run-compacted dispatch table of a calibrated view in tile-row order (include/rt_diag.h; the plain table stays
@@ -122,6 +138,7 @@ struct RunHead {
 
 __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restrict__ row_order,
                                                           const uint64_t* __restrict__ cone,
+                                                          const uint8_t* __restrict__ cls,
                                                           const uint32_t* __restrict__ code,
                                                           const uint32_t* __restrict__ number, int tiles_x, int tiles_y,
                                                           DispRec* __restrict__ disp) {
@@ -135,6 +152,7 @@ __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restr
     r.cone_hi = (uint32_t)(m >> 32);
     r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
     r.sky = code[k] - 1u;
+    if (cls && cls[(size_t)ty * tiles_x + tx] == kClassSphereFree) r.sky = kDispSphereFree;   // (a tracing tile: code 1)
     disp[cone_slot(number[k] - 1u, number[n - 1])] = r;   // (number[n - 1]: the heads' count, at most n)
 }
 
@@ -219,7 +237,8 @@ static void view_free_run_bufs(rt_ctx::View& v) {
 // The per-tile view buffers (dispatch table, tile times, cone masks, sort buffers) of a context.
 void rt_free_view_bufs(rt_ctx* c) {
     rt_ctx::View& v = c->view;
-    void* bufs[] = {v.d_disp, v.d_tile_cost, v.d_cone_tile, v.d_sort_keys, v.d_sort_in, v.d_sort_out, v.d_sort_tmp};
+    void* bufs[] = {v.d_disp, v.d_tile_cost, v.d_cone_tile, v.d_sort_keys, v.d_sort_in, v.d_sort_out, v.d_sort_tmp,
+                    v.d_tile_class};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     view_free_run_bufs(v);
@@ -230,6 +249,8 @@ void rt_free_view_bufs(rt_ctx* c) {
     v.d_disp = nullptr;
     v.d_tile_cost = v.d_sort_keys = nullptr;
     v.d_cone_tile = nullptr;
+    v.d_tile_class = nullptr;
+    v.class_tiles_n = 0;
     v.d_sort_in = v.d_sort_out = nullptr;
     v.d_sort_tmp = nullptr;
     v.sort_tmp_bytes = 0;
@@ -246,6 +267,7 @@ static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
     bool ok = hipMalloc(&v.d_disp, slots * sizeof(DispRec)) == hipSuccess &&
               hipMalloc(&v.d_tile_cost, tiles * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&v.d_cone_tile, 2 * tiles * sizeof(uint64_t)) == hipSuccess &&   // masks, then sky verdicts
+              hipMalloc(&v.d_tile_class, tiles) == hipSuccess &&
               hipMalloc(&v.d_sort_keys, tiles * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&v.d_sort_in, tiles * sizeof(int32_t)) == hipSuccess &&
               hipMalloc(&v.d_sort_out, tiles * sizeof(int32_t)) == hipSuccess;
@@ -580,6 +602,7 @@ static void render_grow_calibration(rt_ctx* c, RenderJob& J) {
     } else {
         J.lm_calib = false;
     }
+    v.class_tiles_n = 0;                            // (the classes fall with the masks they are made from)
 }
 
 // Step 5: the primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
@@ -616,6 +639,12 @@ static int render_launch(rt_ctx* c, const RenderJob& J) {
     L.o8 = J.p8;
     L.o64 = J.o64;
     L.orc = J.orc;
+    // A level-mask slot is written only where a wave reaches that level: the view's masks start as zeros, on the render
+    // stream ahead of the launch that writes them (this one, or the level-mask launch below), so that an unreached slot
+    // reads "keeps no sphere" — no render consumes such a slot, and the tile classes (rt_class_kernel) read them all.
+    if (J.lm_calib &&
+        hipMemsetAsync(c->view.d_lmask, 0, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t), J.st) != hipSuccess)
+        return rt_fail(RT_EHIP, "level masks: hipMemsetAsync failed");
     hipError_t e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
     if (J.lm_calib && !J.cull_kernel) {
@@ -650,19 +679,30 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
     hipError_t e;
     const dim3 tg((unsigned)((J.tiles + 255) / 256));
     const uint64_t* cones = J.cone_calib ? v.d_cone_tile : nullptr;
+    // The tile classes of a fast-kernel view with level masks, after the level-mask launch and ahead of the table
+    // kernels; the records carry them unless RT_TILE_CLASSES=0.  Culling-kernel views and views without masks have none.
+    const uint8_t* cls = nullptr;
+    v.class_tiles_n = 0;
+    if (J.cone_calib && J.lm_calib && !J.cull_kernel && c->scene.n_padded <= 64) {
+        hipLaunchKernelGGL(rt_class_kernel, tg, dim3(256), 0, st, v.d_cone_tile, v.d_lmask, J.lm_stride,
+                           c->scene.n_padded, tiles, v.d_tile_class);
+        v.class_tiles_n = J.tiles;
+        // (only into the records of a view whose kernel instance reads the bit: rt_render.hpp class_instance)
+        if (c->knobs.tile_classes && class_instance(J.mode == kModePacked, J.mode == kModeSS, J.depth)) cls = v.d_tile_class;
+    }
     if (c->knobs.order_policy == 1) {                     // tiles longest first
         hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, v.d_sort_in, (int)tiles);
         size_t tmp = v.sort_tmp_bytes;
         e = hipcub::DeviceRadixSort::SortPairsDescending(v.d_sort_tmp, tmp, v.d_tile_cost, v.d_sort_keys,
                                                          v.d_sort_in, v.d_sort_out, (int)tiles, 0, 32, st);
         if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, tiles_x, tiles_y,
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, cls, tiles_x, tiles_y,
                            v.d_disp);
     } else {                                        // tile rows longest first
         hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, v.d_tile_cost, tiles_x,
                            v.d_row_cost);
         hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, v.d_row_cost, tiles_y, v.d_tile_rows);
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, tiles_x, tiles_y,
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, cls, tiles_x, tiles_y,
                            v.d_disp);
         // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
         // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
@@ -675,8 +715,8 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
             hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, v.d_tile_rows,
                                v.d_cone_tile + J.tiles, tiles_x, run_max, v.d_run_code);
             if (hipcub::DeviceScan::InclusiveSum(v.d_run_tmp, tmp, heads, v.d_run_num, tiles, st) == hipSuccess) {
-                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, v.d_run_code,
-                                   v.d_run_num, tiles_x, tiles_y, v.d_disp_run);
+                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, cls,
+                                   v.d_run_code, v.d_run_num, tiles_x, tiles_y, v.d_disp_run);
                 if (hipMemcpyAsync(v.h_run_n, v.d_run_num + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    st) == hipSuccess &&
                     hipEventRecord(v.run_ev, st) == hipSuccess) {

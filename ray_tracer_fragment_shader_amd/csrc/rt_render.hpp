@@ -99,11 +99,21 @@ __host__ __device__ __forceinline__ size_t cone_slots(size_t n) { return ((n + 7
 // tx .. tx + r - 1 of that tile row hits anything — r = 1 in the plain table, up to the run maximum in the run-compacted
 // one, rt_run_disp_kernel; both valid when RenderParams::cone_use).  The table is indexed by cone_slot(position): one
 // 16-byte scalar load per wave brings all three.
+// The top bit of `sky` (run lengths are at most 65,535) is the tile's class: set for a tracing tile of a fast-kernel view
+// that is sphere-free (rt_cone.hpp tile_sphere_free: neither its cone mask nor any of its level masks keeps a sphere),
+// which the fast kernels then trace without the sphere code (render_body).  Never set in a sky record.
 struct alignas(16) DispRec {
     uint32_t cone_lo, cone_hi;
     uint32_t tile;
     uint32_t sky;
 };
+constexpr uint32_t kDispSphereFree = 0x80000000u;
+// Which fast one-wave opaque instances read the class bit (render_body) — and so which views' records may carry it
+// (rt_plain.hip render_build_dispatch; an instance that does not read it would take the bit for a run length): the RGBA
+// instances of every depth and the packed ones up to depth 1.  Not the packed instances beyond depth 1: the second trace
+// cost the SGPR-capped achromatic packed depth-2 kernel 6 SGPR spills and a 65th VGPR, so its code stays as it was.  Not
+// the supersampled ones: their views keep the plain table and were left alone.
+__host__ __device__ constexpr bool class_instance(bool packed, bool ss, int B) { return !ss && !(packed && B >= 2); }
 
 struct RenderParams {
     double eye[3];
@@ -450,13 +460,17 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     // cone mask's: rt_cone.hpp board_edge_record) and no sphere left in the cone mask, which covers every sphere of a
     // scene of up to 64.  Opaque, mesh-free instances with one-wave tiles (the conditions of trace()'s lazy_u).
     constexpr bool kSkyInst = !TRANSP && !TREE && !LDS && WG == 64;
+    // Sphere-free tiles (DispRec, kDispSphereFree): the fast one-wave opaque instances read the class bit of a cached
+    // view's record; the records of every other instance's views never have it set, and their code is as it was.
+    constexpr bool kClassInst = kSkyInst && !CULL && class_instance(PACKED, SS, B);
+    const uint32_t sky_len = kClassInst ? sky_cached & ~kDispSphereFree : sky_cached;
     bool sky = false;
     RT_COUNT(V.S, kCntWaves, 1);
     if (P.np >= kPrimaryConeMin && P.cone_use) {
         // the mask and the verdict this view's calibration render computed for this tile, in its dispatch record
         // (rt_disp_kernel): no cone phase
         cone = cone_cached;
-        sky = kSkyInst && sky_cached != 0;
+        sky = kSkyInst && sky_len != 0;
     } else if (P.np >= kPrimaryConeMin) {
         // Within one frame global_row_of is increasing, so jb - ja == 7 means 8 consecutive rows.
         const int lr0 = ty * kTileH + by0, ja = global_row_of(P, lr0), jb = global_row_of(P, lr0 + bh - 1);
@@ -515,13 +529,16 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
 #else
         (void)traced;
 #endif
+        // (HW_ID, the XCC id in bits 32 .. 35, and the position's tile — a run's first — as tx | ty << 14 from bit 36,
+        // so that tools/wave_trace.py can split the waves by their tile's class)
         P.wtrace[4 * w + 2] = (uint64_t)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
-                              ((uint64_t)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) << 32);
+                              ((uint64_t)(__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)) & 0xFu) << 32) |
+                              ((uint64_t)((uint32_t)(tx & 0x3fff) | ((uint32_t)(ty & 0x3fff) << 14)) << 36);
     };
 #endif
     if constexpr (kSkyInst && !SS) {
         if (sky && P.cone_use) {
-            const int run = __builtin_amdgcn_readfirstlane((int)sky_cached);
+            const int run = __builtin_amdgcn_readfirstlane((int)sky_len);
 #if RT_WAVE_TRACE
             const uint64_t t_run = __builtin_amdgcn_s_memrealtime();   // the run is known; its stores next
 #endif
@@ -559,10 +576,20 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
         LevelMasks lm{-1};
         if (!TRANSP && !TREE && P.lmask_stride > 0 && !pad)
             lm.tile = (ty * P.tiles_x + tx) * P.lmask_stride;
-        if constexpr (TREE)
+        if constexpr (TREE) {
             col = trace_tree<B>(V, eye, sp, &seg, &sh);
-        else
+        } else if constexpr (kClassInst) {
+            // A sphere-free tile of a cached view (its record's class bit, decided at calibration like the sky verdict;
+            // read once, made a scalar, consumed by this branch — nothing of it lives through a trace): the same trace
+            // compiled without the sphere loops and without the level-mask reads (trace NOSPH).  The prologue above and
+            // the stores below are shared.
+            if (P.cone_use && __builtin_amdgcn_readfirstlane((int)(sky_cached >> 31)) != 0)
+                col = trace<B, true, false, false, WG, ACHRO, false, false, true>(V, eye, sp, 0, &seg, &sh, slot, mslot);
+            else
+                col = trace<B, true, TRANSP, CULL, WG, ACHRO>(V, eye, sp, cone, &seg, &sh, slot, mslot, lm);
+        } else {
             col = trace<B, true, TRANSP, CULL, WG, ACHRO>(V, eye, sp, cone, &seg, &sh, slot, mslot, lm);
+        }
     }
 #if RT_WAVE_TRACE >= 2
     asm volatile("" ::"v"(col.x), "v"(col.y), "v"(col.z));

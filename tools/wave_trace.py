@@ -6,6 +6,9 @@ The traced launch is a cached render of the calibrated view: with runs of sky ti
 has one wave per dispatch position — a tracing tile or a run — and the kernel records waves by position, so the
 positions the launch really had (rt_diag_disp_count) say how many records to read; RT_SKY_RUN_MAX=1 in the environment
 traces the plain table, one wave per tile.
+Every record names its position's tile, and the context's class grid (rt_diag_tile_class_grid: decided at calibration
+whether or not RT_TILE_CLASSES lets the records carry it) splits the per-phase figures into sky positions, sphere-free
+tiles and the other tracing tiles — under RT_TILE_CLASSES=0 the same tiles on the general path.
 usage: wave_trace.py [config]"""
 import ctypes
 import json
@@ -57,6 +60,7 @@ def main():
     dur = en - st
     hwid = hw & 0xFFFFFFFF
     xcc = (hw >> 32) & 0xF
+    tile_x, tile_y = (hw >> 36) & 0x3FFF, (hw >> 50) & 0x3FFF
     cu = (hwid >> 8) & 0xF
     se = (hwid >> 13) & 0x7
     simd = (hwid >> 4) & 0x3
@@ -109,6 +113,28 @@ def main():
         sky = dur <= np.percentile(dur, 50)
         out["trace_us_short_half"] = round(float((t_tr - md)[sky].mean()), 3)
         out["trace_us_long_half"] = round(float((t_tr - md)[~sky].mean()), 3)
+    # the same per-phase means by the class of the position's tile (0 tracing, 1 sky, 2 sphere-free)
+    tx_n, ty_n = (W + 7) // 8, (H + 7) // 8
+    grid = np.zeros((ty_n, tx_n), np.uint8)
+    if hasattr(lib, "rt_diag_tile_class_grid") and lib.rt_diag_tile_class_grid(t._ctx, grid.ctypes.data, grid.size) == 0:
+        cls = grid[np.minimum(tile_y, ty_n - 1), np.minimum(tile_x, tx_n - 1)]
+        out["tile_classes_env"] = os.environ.get("RT_TILE_CLASSES", "")
+        out["by_class"] = {}
+        for name_c, code in (("tracing_other", 0), ("sky", 1), ("sphere_free", 2)):
+            m = cls == code
+            if not m.any():
+                continue
+            e = {"waves": int(m.sum()), "mean_dur_us": round(float(dur[m].mean()), 3),
+                 "sum_dur_us": round(float(dur[m].sum()), 1),
+                 "dur_us": {q: round(float(np.percentile(dur[m], q)), 2) for q in (5, 50, 95)},
+                 "mean_prologue_us": round(float((md - st)[m].mean()), 3)}
+            if b[:, 2].any():
+                e["mean_phase_us"] = {"to_tile_row": round(float((t_ty - st)[m].mean()), 3),
+                                      "tile_row_to_cone": round(float((t_cone - t_ty)[m].mean()), 3),
+                                      "cone_to_ray": round(float((md - t_cone)[m].mean()), 3),
+                                      "trace": round(float((t_tr - md)[m].mean()), 3),
+                                      "stores": round(float((en - t_tr)[m].mean()), 3)}
+            out["by_class"][name_c] = e
     # duration by dispatch row (one wave per tile: rows of tiles_x positions, in the view's dispatch order), or, with
     # runs, by sixteenths of the dispatch positions
     rows = (H + 7) // 8
