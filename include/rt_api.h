@@ -324,7 +324,8 @@ int rt_render_adaptive(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam,
  *  9. RT_EINVAL (rt_last_error names the argument) for `samples` outside {1, 2, 4, 8}, an `aperture` that is
  *     negative, NaN or infinite, a bad frame size (the sample frame S width x S height holds at most 2^31 samples),
  *     and an int32 overflow of the sample-grid camera.
- * 10. The lens is a regular square grid: jittered or disc-shaped lenses are not offered.  rt_render_multi, the
+ * 10. The lens is a regular square grid: jittered (here: rt_render_jitter_dev has them) or disc-shaped lenses are not
+ *     offered.  rt_render_multi, the
  *     packed and asynchronous host paths and the drop-in draw() render through a pinhole.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, A = 8, RGBA32F + RGBA8, tools/bench_dof.py): S = 2 124 us and
  * S = 4 503 us per frame, 1.42 x and 1.44 x rt_render_ss_dev at the same S, and 3.9 x and 3.0 x faster than the same
@@ -370,7 +371,8 @@ int rt_render_dof(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int 
  *     `light_size` that is negative, NaN or infinite, a bad frame size (the sample frame S width x S height holds at
  *     most 2^31 samples), and an int32 overflow of the sample-grid camera.  A rejected call writes no pixel.
  *  8. Not offered: per-light sizes, disc-shaped or jittered panels, and a pairing of light, lens and sub-pixel
- *     points other than by (a, b).  A penumbra is therefore a ramp of at most S * S steps, the same in every pixel.
+ *     points other than by (a, b).  A penumbra is therefore a ramp of at most S * S steps, the same in every pixel
+ *     (rt_render_jitter_dev turns the steps into noise).
  *     rt_render_multi, the packed and asynchronous host paths and the drop-in draw() keep point lights.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, A = 0, RGBA32F + RGBA8, tools/bench_soft.py): S = 2 130 us
  * and S = 4 525 us per frame, 1.07 x and 1.08 x rt_render_dof_dev at the same S and A (the price of a shadow test
@@ -422,7 +424,8 @@ int rt_render_soft(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int
  *     displacement, a wrong n_spheres, a bad frame size, and an int32 overflow of the sample-grid camera.  A rejected
  *     call writes no pixel.
  * 10. Not offered: moving meshes, board, lights or camera; curved or accelerated paths; jittered times; a pairing of
- *     time with (a, b) other than rule 2.  A streak is therefore a sum of at most S S copies, the same in every pixel.
+ *     time with (a, b) other than rule 2.  A streak is therefore a sum of at most S S copies, the same in every pixel
+ *     (rt_render_jitter_dev jitters the times).
  *     rt_render_multi, the packed and asynchronous host paths and the drop-in draw() stay frozen in time.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, one sphere moving by |d| = 40, F = 1, A = R = 0, RGBA32F + RGBA8,
  * tools/bench_motion.py): S = 2 139 us and S = 4 565 us per frame, 1.05 x and 1.06 x rt_render_soft_dev at the same S
@@ -494,6 +497,63 @@ int rt_render_lens_adaptive(rt_ctx* ctx, const rt_scene* scene, const double* di
                             int width, int height, int depth, int samples_lo, int samples_hi, int threshold,
                             double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
                             double* rgb64f, uint8_t* refined, rt_stats* stats, uint64_t* n_refined);
+
+/* ---- jittered sampling of the lens, soft-shadow and motion-blur renders (ABI 10: new symbols only) ------------- */
+/* Stratified jittered sampling: rt_render_motion_dev with each of the S x S samples of a pixel moved, in every one of
+ * its seven dimensions, to one of J sub-positions of its stratum, chosen by a hash of the sample and a seed.  The regular
+ * grid's banding (a penumbra of S S steps, a streak of S S copies, the same in every pixel) becomes noise at the same ray
+ * count.  Jitter is QUANTISED: every jittered position is a point of the regular grid J times finer than the sample
+ * grid, so every quotient below is exact and J = 1 is the existing render.  Deterministic, and defined entirely by
+ * rt_set_scene and rt_trace_rays_dev on scenes and rays this text spells out.  For a full width x height frame,
+ * S = `samples` in {1, 2, 4, 8}, J = `jitter` in {1, 2, 4, 8, 16}, `seed` any uint32, and A, R, F and the displacements as
+ * for rt_render_motion_dev:
+ *  1. Hash.  fmix32(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16, all uint32 and
+ *     wrapping.  Sample (a, b) of pixel (i, j) has the sample-grid coordinates (I, Jr) = (S i + a, S j + b) and the index
+ *     q = Jr * (S * width) + I (below 2^31: the size check); its word is w = fmix32(fmix32(q) ^ seed).
+ *     fmix32(0) = 0, fmix32(1) = 0x514e28b7, fmix32(fmix32(5) ^ 7) = 0xe80274bd.
+ *  2. Levels.  Dimension d in 0 .. 6 takes nibble d of w: k_d = ((w >> 4 d) & 15) >> (4 - log2 J), in 0 .. J - 1.
+ *     d = 0, 1: sub-pixel x, y; 2, 3: lens x, y; 4, 5: light x, z; 6: time.  J = 1 gives k_d = 0 for every d.
+ *  3. Ray end.  The fine camera cam_f has eye, look_at and up of `cam`, pitch_f = cam.pitch / (S J) (exact) and
+ *     bottom_f = S J bottom.  The ray ends at the primary-ray end point of cam_f (the camera comment's formula) for the
+ *     fine pixel (J I + k_0, J Jr + k_1).
+ *  4. Ray start.  e = (eye + (A * t_x) * right) + (A * t_y) * up',  t_x = (double)(2 (J a + k_2) + 1 - S J) / (double)(S J),
+ *     t_y likewise from b and k_3; the operation order of rt_render_dof_dev rule 2.
+ *  5. Lights.  (L.x + (R * g_x), L.y, L.z + (R * g_z)), g_x and g_z by the formula of t_x from (a, k_4) and (b, k_5).
+ *  6. Time.  sigma = F * u,  u = (double)(2 (J n + k_6) + 1 - S S J) / (double)(S S J),  n = a + S b; sphere centres
+ *     follow rt_render_motion_dev rule 3.  |t|, |g|, |u| < 1 as on the regular grid.
+ *  7. Value.  The colour and the counters of a sample are what rt_trace_rays_dev gives its ray after rt_set_scene of the
+ *     scene of rules 5 and 6.  Reduction and outputs follow rt_render_ss_dev rules 3-5 exactly.
+ *  8. Pins that follow, with NO shortcut in the implementation (all run the same kernel): J = 1 with any seed writes
+ *     exactly what rt_render_motion_dev writes, images and counters; with A = R = F = 0, sample (a, b) of pixel (i, j) is
+ *     pixel (J I + k_0, J Jr + k_1) of the S J width x S J height frame rt_render_dev renders with cam_f; equal arguments
+ *     give equal bytes, call after call and under graph replay.
+ *  9. rt_render_jitter_dev: full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host
+ *     synchronisation, so the call may be captured in a hipGraph.  No per-view state; the scene and motion records are
+ *     read, never written.
+ * 10. RT_EINVAL (rt_last_error names the argument) for rt_render_motion_dev's checks, a `jitter` outside
+ *     {1, 2, 4, 8, 16}, and an int32 overflow of the fine camera: of S J bottom_x or S J bottom_y, of S J width or
+ *     S J height, or of a fine pixel's coordinate plus bottom_f.  A rejected call writes no pixel.
+ * 11. Not offered: jitter in rt_render_lens_adaptive_dev, rt_render_adaptive_dev and rt_render_ss_dev; disc lenses;
+ *     blue-noise or low-discrepancy sequences; a seed per effect; the rand()-driven jitter of the app (rt_render_screen
+ *     stays the faithful one).
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, one sphere moving by |d| = 40, F = 1, A = 0, RGBA32F + RGBA8,
+ * tools/bench_jitter.py, profiles/jitter/bench_jitter.json): S = 2 147.5 us at J = 1 and 149.7 us at J = 16 per frame
+ * against 139.6 us for rt_render_motion_dev (1.06 x and 1.07 x); S = 4 600.5 us and 602.7 us against 570.9 us (1.05 x and
+ * 1.06 x).  The cost is the kernel's own per-lane work, present at J = 1; the lanes' separate light points and times at
+ * J = 16 add 1.5 % and 0.4 %.  Other scenes, depths, apertures and motions: not measured. */
+/* Host only: levels[d] = k_d of sample (I, Jr), 0 <= I < S width, of a width-pixel-wide frame, by the functions the
+ * kernel calls.  RT_EINVAL for a null pointer, samples or jitter outside their sets, and a sample outside a frame of at
+ * most 2^31 samples. */
+int rt_jitter_sample(int width, int samples, int jitter, uint32_t seed, int I, int Jr, int32_t levels[7]);
+/* Device pointers, each output nullable, width * height pixels. */
+int rt_render_jitter_dev(rt_ctx* ctx, const rt_camera* cam, int width, int height, int depth, int samples, int jitter,
+                         uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
+                         uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_motion: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the frame.  *stats as rt_render_motion. */
+int rt_render_jitter(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam, int width,
+                     int height, int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                     double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
 /* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

@@ -202,6 +202,12 @@ SIGNATURES = {
     "rt_render_lens_adaptive": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int,
                                         c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                         c_void_p, _P(rt_stats), _P(c_uint64)]),
+    "rt_jitter_sample": (c_int, [c_int, c_int, c_int, ctypes.c_uint32, c_int, c_int, _P(ctypes.c_int32)]),
+    "rt_render_jitter_dev": (c_int, [c_void_p, _P(rt_camera), c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32,
+                                     c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_render_jitter": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int, c_int,
+                                 ctypes.c_uint32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                 _P(rt_stats)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

@@ -42,6 +42,11 @@
 //                                                  4 x 4 only where the 2 x 2 samples' RGBA8 bytes spread by more than 8
 //                                                  or the coarse RGBA8 differs from a 4-neighbour by more than 8
 //                                                  (rt_render_lens_adaptive; threshold in -1 .. 255)
+//   rt_render --config c2 --samples 4 --jitter 16 [--seed 7] [--aperture 8 [--focus 0.8]] [--light-size 40]
+//             [--shutter 1 --move 0:40,0,0 ...] --out c2_jitter.ppm
+//                                                  the frame of the lens, soft-shadow and motion modes with every sample
+//                                                  at one of 16 hashed sub-positions of its stratum in each dimension
+//                                                  (rt_render_jitter; J in 1, 2, 4, 8, 16; the seed defaults to 1)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -83,7 +88,8 @@ struct Options {
     int coarse = 0;                          // --coarse C with --refine T: rt_render_lens_adaptive, C x C samples per pixel
     bool refine = false;                     // ... and --samples x --samples where they disagree by more than T
     int refine_t = 0;
-    std::vector<int> move_k;                 // --move K:DX,DY,DZ (repeatable): sphere K's displacement
+    int jitter = 0;                          // --jitter J: rt_render_jitter with --seed (needs --samples)
+    std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
 
@@ -245,10 +251,11 @@ int main(int argc, char** argv) {
         else if (a == "--move") move_arg(next(), &o);
         else if (a == "--coarse") o.coarse = std::atoi(next().c_str());
         else if (a == "--refine") { o.refine = true; o.refine_t = std::atoi(next().c_str()); }
+        else if (a == "--jitter") { o.jitter = std::atoi(next().c_str()); if (o.jitter == 0) o.jitter = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K]]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
     }
@@ -290,6 +297,15 @@ int main(int argc, char** argv) {
     }
     if (o.focus && (!o.dof || !(o.focus_ratio > 0.0))) {
         std::fprintf(stderr, "rt_render: --focus needs --aperture and a ratio > 0\n");
+        return 2;
+    }
+    if (o.jitter != 0 && (o.samples == 0 || o.adaptive || o.refine || o.coarse != 0 || o.faithful >= 0 || o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --jitter needs --samples, excludes --adaptive, --coarse and --refine and applies "
+                             "to plain frames (not --faithful or --gpus)\n");
+        return 2;
+    }
+    if (o.jitter != 0 && o.jitter != 1 && o.jitter != 2 && o.jitter != 4 && o.jitter != 8 && o.jitter != 16) {
+        std::fprintf(stderr, "rt_render: --jitter must be 1, 2, 4, 8 or 16\n");
         return 2;
     }
     if ((o.coarse != 0) != o.refine) {
@@ -441,6 +457,10 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
+        else if (o.jitter != 0)
+            check(rt_render_jitter(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth, o.samples,
+                                   o.jitter, (uint32_t)o.seed, o.aperture, o.light_size, o.shutter, nullptr, rgba8.data(),
+                                   nullptr, &st), "rt_render_jitter");
         else if (o.motion)
             check(rt_render_motion(ctx, &scene, displacement.data(), &cam, W, H, depth, o.samples, o.aperture,
                                    o.light_size, o.shutter, nullptr, rgba8.data(), nullptr, &st), "rt_render_motion");
@@ -473,6 +493,11 @@ int main(int argc, char** argv) {
                     "%llu of %llu pixels refined from %d x %d to %d x %d samples\n", o.refine_t, o.shutter, o.light_size,
                     o.aperture, (unsigned long long)n_refined, (unsigned long long)W * H, o.coarse, o.coarse, o.samples,
                     o.samples);
+    else if (o.jitter != 0)
+        std::printf("rt_render: jittered, J = %d sub-positions per stratum and axis, seed %u, shutter %g, %d moving "
+                    "spheres, light half-width %g, lens half-width %g: %d x %d samples per pixel, %llu primary rays\n",
+                    o.jitter, o.seed, o.shutter, (int)o.move_k.size(), o.light_size, o.aperture, o.samples, o.samples,
+                    (unsigned long long)st.primary_rays);
     else if (o.motion)
         std::printf("rt_render: motion blur, shutter %g, %d moving spheres, light half-width %g, lens half-width %g: "
                     "%d x %d shutter times per pixel, %llu primary rays\n", o.shutter, (int)o.move_k.size(),

@@ -16,6 +16,7 @@
 #include "../../include/rt_diag.h"
 #include "rt_cone.hpp"
 #include "rt_internal.hpp"
+#include "rt_jitter.hpp"
 #include "rt_layout.hpp"
 
 namespace {
@@ -221,6 +222,23 @@ extern "C" int rt_camera_focus(const rt_camera* cam, double ratio, rt_camera* ou
         c.pitch = ratio * cam->pitch;
     }
     *out = c;
+    return RT_OK;
+}
+
+// The seven levels of sample (I, Jr) of the jittered render's S width-wide sample frame, by the kernel's own functions
+// (rt_jitter.hpp).
+extern "C" int rt_jitter_sample(int width, int samples, int jitter, uint32_t seed, int I, int Jr, int32_t levels[7]) {
+    if (!levels) return rt_fail(RT_EINVAL, "rt_jitter_sample: null pointer");
+    if (samples != 1 && samples != 2 && samples != 4 && samples != 8)
+        return rt_fail(RT_EINVAL, "rt_jitter_sample: samples must be 1, 2, 4 or 8");
+    const int jl = rtj::jitter_log2_of(jitter);
+    if (jl < 0) return rt_fail(RT_EINVAL, "rt_jitter_sample: jitter must be 1, 2, 4, 8 or 16");
+    const long long sw = (long long)width * samples;
+    if (width <= 0 || sw > INT32_MAX) return rt_fail(RT_EINVAL, "rt_jitter_sample: bad image size (width)");
+    if (I < 0 || I >= sw || Jr < 0 || (long long)Jr * sw + I >= (1LL << 31))
+        return rt_fail(RT_EINVAL, "rt_jitter_sample: sample (I, Jr) outside a frame of at most 2^31 samples");
+    const uint32_t w = rtj::jitter_word((uint32_t)Jr * (uint32_t)sw + (uint32_t)I, seed);
+    for (int d = 0; d < 7; ++d) levels[d] = rtj::jitter_level(w, d, jl);
     return RT_OK;
 }
 

@@ -1,5 +1,6 @@
 // rt_sampled.hip — the device entry points of the sampled renders of rt_sampled.hpp: adaptive supersampling
-// (base render, rt_classify_kernel, the refine launch) and the lens family's one launch.
+// (base render, rt_classify_kernel, the refine launch), the lens family's one launch, the jittered render's and the
+// adaptive lens render's three passes.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -234,6 +235,60 @@ extern "C" int rt_render_motion_dev(rt_ctx* c, const rt_camera* cam, int W, int 
                                     double* rgb64f, uint32_t* raycount2, void* stream) {
     return lens_render_dev(kLensMotion, "rt_render_motion_dev", c, cam, W, H, depth, samples, aperture, light_size,
                            shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+// ---- the jittered render (include/rt_api.h) -------------------------------------------------------------------------
+int jitter_arg_checks(const char* who, int jitter) {
+    if (rtj::jitter_log2_of(jitter) < 0) return rt_fail(RT_EINVAL, std::string(who) + ": jitter must be 1, 2, 4, 8 or 16");
+    return RT_OK;
+}
+
+// One launch of rt_jitter_kernel on `stream`: lens_render_dev's motion kind with the fine camera (pitch / (S J),
+// S J bottom, whose whole S J width x S J height frame must index in int32) and the seed beside it.  Nothing per view,
+// no field of the context written, no shortcut for jitter 1 or any argument of 0.
+int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int jitter,
+                      uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                      double* rgb64f, uint32_t* raycount2, void* stream) {
+    int s, rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter);
+    if (rc || (rc = jitter_arg_checks(who, jitter))) return rc;
+    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
+    if (rc) return rc;
+    if (!c->scene.d_motion) return rt_fail(RT_EINVAL, std::string(who) + ": no scene set");
+    const long long sj = (long long)samples * jitter;
+    const long long bx = sj * cam->bottom_x, by = sj * cam->bottom_y, fw = sj * W, fh = sj * H;
+    if (fw > INT32_MAX || fh > INT32_MAX || bx < INT32_MIN || by < INT32_MIN || bx + fw - 1 > INT32_MAX ||
+        by + fh - 1 > INT32_MAX)
+        return rt_fail(RT_EINVAL, std::string(who) + ": samples * jitter * (bottom_x / bottom_y, width / height) "
+                                                     "overflows int32");
+    L.jitter.pitch_f = cam->pitch / (double)sj;             // exact: a power of two
+    L.jitter.bottom_fx = (int32_t)bx;
+    L.jitter.bottom_fy = (int32_t)by;
+    L.jitter.jl = rtj::jitter_log2_of(jitter);
+    L.jitter.seed = seed;
+    L.variant = trace_variant(c->scene.tree, c->scene.transparent);
+    L.stream = (hipStream_t)stream;
+    L.scene = c->scene.d_scene;
+    L.motion = c->scene.d_motion;
+    L.aperture = aperture;
+    L.light_size = light_size;
+    L.shutter = shutter;
+    L.o32 = rgba32f;
+    L.o8 = rgba8;
+    L.o64 = rgb64f;
+    L.orc2 = raycount2;
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    const hipError_t e = with_depth(depth, [&](auto B) { return launch_jitter<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_jitter_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+extern "C" int rt_render_jitter_dev(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int jitter,
+                                    uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
+                                    uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream) {
+    return jitter_render_dev("rt_render_jitter_dev", c, cam, W, H, depth, samples, jitter, seed, aperture, light_size,
+                             shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
 }
 
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------

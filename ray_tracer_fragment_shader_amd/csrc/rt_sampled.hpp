@@ -9,6 +9,8 @@
 //   rt_lens_coarse_kernel<B, TRANSP, TREE>, rt_lens_refine_kernel<B, TRANSP, TREE>  the two tracing passes of the
 //                                      adaptive lens render (rt_render_lens_adaptive_dev): the motion kind over the
 //                                      whole frame with each pixel's sample spread, and over a compacted work list.
+//   rt_jitter_kernel<B, TRANSP, TREE>  the jittered render (rt_render_jitter_dev): the motion kind with each sample at
+//                                      a hashed sub-position of its stratum in every dimension.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -18,9 +20,10 @@
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
 // rt_adaptive.hip (rt_adaptive_b<B>.o), once per depth and kind rt_lens.hip (rt_lens_k<kind>_b<B>.o), and
-// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o).
+// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o) and rt_jitter.hip (rt_jitter_b<B>.o).
 #pragma once
 
+#include "rt_jitter.hpp"
 #include "rt_render.hpp"
 
 namespace rtk {
@@ -234,6 +237,73 @@ __global__ __launch_bounds__(64) void rt_lens_refine_kernel(const DevScene* __re
     }
 }
 
+// ---- The jittered render (rt_render_jitter_dev, include/rt_api.h): the motion kind with every sample moved, in each
+// of its seven dimensions, to one of J sub-positions of its stratum. ----
+
+// What the jittered kernel gets beside the motion kind's arguments: the fine camera's pitch and frame corner
+// (pitch / (S J), S J bottom: formed and range-checked by the host), jl = log2 J and the seed.
+struct JitterParams {
+    double pitch_f;
+    int32_t bottom_fx, bottom_fy;
+    int32_t jl;
+    uint32_t seed;
+};
+
+// rt_lens_kernel<B, TRANSP, TREE, true, true>'s wave layout, clamping, hits_ok, trace and reduction, with the lane's
+// sample (I, Jr) = (i, lr) of the sample frame drawing seven levels k_0 .. k_6 in 0 .. J - 1 from one hash word
+// (rt_jitter.hpp; the key is Jr (S width) + I with the sample frame's own width P.width and the lane's unclamped
+// coordinates: a lane outside the frame stores nothing, so its key does not matter).  Every quotient is that of the
+// regular grid J times finer, still exact (a power of two):
+//     ray end     the fine camera's screen point of fine pixel (J I + k_0, J Jr + k_1),
+//     ray start   t_x = (2 (J a + k_2) + 1 - S J) / (S J), t_y from (b, k_3),
+//     lights      g_x from (a, k_4), g_z from (b, k_5), the same formula,
+//     time        u = (2 (J n + k_6) + 1 - S S J) / (S S J), n = a + S b.
+// |t|, |g|, |u| < 1 as on the regular grid, so the motion record's swept proofs hold as they stand.  J = 1: every level
+// is 0 and each expression above is the motion kind's, bit for bit.  A kernel of its own, not a flag of rt_lens_kernel:
+// that one's parameter list, hence its instances' code, stays what it was.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_jitter_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                       RenderParams P, JitterParams Q, double aperture,
+                                                       double light_size, double shutter, int tile_rows, void* o32,
+                                                       void* o8, double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed);
+    const d3 right = ld3(P.right), upp = ld3(P.upp);
+    // screen_point of the fine camera (look, right and up' are P's: the cameras differ in pitch and corner only)
+    const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+    const d3 sp = add(add(ld3(P.look), scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                      scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+    const int a = x & S1, b = y & S1, sj = s + jl;
+    const double inv_sj = ldexp(1.0, -sj);
+    const auto t_of = [&](int c, int k) { return (double)(2 * ((c << jl) + k) + 1 - (1 << sj)) * inv_sj; };
+    const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+    const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+    const d3 e = add(add(ld3(P.eye), scl(aperture * ta, right)), scl(aperture * tb, upp));
+    const int n = a + (b << s);                             // time index a + S b
+    const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                    ldexp(1.0, -(s + sj)));
+    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+    const Motion mo{sigma, M};
+    uint32_t seg = 0, sh = 0;
+    d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                            LightShift{light_size * ga, light_size * gb}, &mo);
+    reduce_samples(s, 8, col, seg, sh);
+    if (a == 0 && b == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -255,16 +325,20 @@ struct SampledLaunch {
     double shutter;                            // MOTION: share of the displacements the exposure covers
     const DevMotion* motion;                   // MOTION: the context's motion record (rt_set_motion)
     uint8_t* spread;                           // rt_lens_coarse_kernel: one byte per output pixel
+    JitterParams jitter;                       // rt_jitter_kernel
 };
 
 // Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
-// and, the adaptive lens render's two, in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip).
+// the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), and the jittered render's in
+// rt_jitter_b<B>.o (rt_jitter.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
 hipError_t launch_lens_coarse(const SampledLaunch& L);
 template <int B>
 hipError_t launch_lens_refine(const SampledLaunch& L);
+template <int B>
+hipError_t launch_jitter(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
@@ -274,6 +348,8 @@ hipError_t launch_lens(const SampledLaunch& L);
     hipError_t launch_lens_coarse<B>(const SampledLaunch& L);         \
     template <>                                                       \
     hipError_t launch_lens_refine<B>(const SampledLaunch& L);         \
+    template <>                                                       \
+    hipError_t launch_jitter<B>(const SampledLaunch& L);              \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -342,6 +418,17 @@ hipError_t launch_lens_refine_impl(const SampledLaunch& L) {
         hipLaunchKernelGGL((rt_lens_refine_kernel<B, decltype(transp)::value, decltype(tree)::value>), dim3(L.grid),
                            dim3(64), lds, L.stream, L.scene, L.motion, L.P, L.aperture, L.light_size, L.shutter, L.out_w,
                            L.count, L.list, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_jitter_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_jitter_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.motion, L.P, L.jitter, L.aperture, L.light_size, L.shutter, tile_rows,
+                           L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

@@ -210,6 +210,28 @@ class Tracer:
         return self._render_lens_into("rt_render_motion_dev", (aperture, light_size, shutter), cam, width, height,
                                       depth, samples, bufs, stream)
 
+    def render_jitter_into(self, cam: abi.rt_camera, width: int, height: int, depth: int, samples: int, jitter: int,
+                           seed: int, aperture: float, light_size: float, shutter: float, bufs: dict,
+                           stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_jitter_dev into alloc_ss() buffers (full frames): the frame of render_motion_into() with every
+        sample moved, in each of its seven dimensions (sub-pixel, lens, light, time), to one of `jitter` sub-positions
+        of its stratum, chosen by a hash of the sample and `seed` (uint32); jitter = 1 is render_motion_into();
+        asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_jitter_dev(
+            self._ctx, ctypes.byref(cam), width, height, depth, samples, jitter, int(seed) & 0xFFFFFFFF,
+            float(aperture), float(light_size), float(shutter), _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")),
+            _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")), ctypes.c_void_p(st.cuda_stream)),
+            "rt_render_jitter_dev")
+        return bufs
+
+    def render_jitter(self, cam, width, height, depth, samples, jitter, seed, aperture, light_size, shutter,
+                      rgba32f=True, rgba8=False, rgb64f=False, raycount=False, stream=None):
+        """-> the buffers of alloc_ss() (the keys of render_ss())."""
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_jitter_into(cam, width, height, depth, samples, jitter, seed, aperture, light_size, shutter,
+                                       bufs, stream)
+
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
     def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
                             refined=True):
