@@ -119,6 +119,32 @@ int rt_diag_tile_class_plan(const uint64_t* cone, const uint8_t* sky, const uint
 int rt_diag_tile_classes(rt_ctx* ctx, int* tiles, int* sky, int* sphere_free);
 int rt_diag_tile_class_grid(rt_ctx* ctx, uint8_t* out, size_t n);
 
+/* Flat tiles: among the sphere-free tiles of such a view, those whose 64 primary rays (lanes past the frame edge
+ * clamped to the last pixel) all hit the board, seen from an eye that passes the board's origin skip.  Every such ray
+ * is lit by every light and its reflected ray hits nothing, so the cached renders of the view trace these tiles on a
+ * straight-line path (RT_FLAT_TILES=0 in the environment of rt_ctx_create leaves every record unmarked, and
+ * RT_TILE_CLASSES=0 implies it; the images are the same bytes either way).  The verdict is made by the view's
+ * calibration, for the views whose kernel instance reads it: plain renders of every depth and packed ones up to depth 1.
+ * rt_diag_flat_tiles: *tiles the tile count of this context's last calibrated view, *flat how many its calibration found
+ * flat (whatever RT_FLAT_TILES says about carrying them in the records).  Both 0 when the view holds no verdicts (no
+ * tile classes, a supersampled view, a packed view beyond depth 1, no calibrated view).  rt_diag_flat_tile_grid copies
+ * the grid out, out[ty * tiles_x + tx] = 1 flat, else 0; RT_EINVAL unless n is that tile count.  A flat tile reports as
+ * sphere-free in rt_diag_tile_class_grid.  Both wait for the device.
+ * rt_diag_disp_sky_word evaluates, on the host and with the function the device's table kernels run, the `sky` word of
+ * a dispatch record: `run` what the word holds outside the classes (0 a tracing tile, 1 .. 65535 the run length of a sky
+ * record), sphere_free and flat the tile's class (a sphere-free tile traces: run = 0).  The top bit marks sphere-free,
+ * the bit below it flat; flat is set only beside sphere-free.  RT_EINVAL for a null word, run > 65535, or a sphere-free
+ * tile with run != 0. */
+int rt_diag_flat_tiles(rt_ctx* ctx, int* tiles, int* flat);
+int rt_diag_disp_sky_word(uint32_t run, int sphere_free, int flat, uint32_t* word);
+/* rt_diag_flat_gates evaluates, on the host and with the function the device runs, the wave-uniform gates of the flat
+ * class for `scene` seen from eye[3]: *gates = 1 when the scene has its board and |eye.y| is within the board's
+ * origin-skip limit (*skip_y, if not null: that limit, -1 where the skip is not proven); *hits_ok = the per-eye flag of
+ * the hit points' bounding-sphere shortcut, as the device sets it for that eye.  No device needed.  RT_EINVAL for null
+ * eye, gates or hits_ok, or a scene the builder rejects. */
+int rt_diag_flat_gates(const rt_scene* scene, const double* eye, int* gates, int* hits_ok, double* skip_y);
+int rt_diag_flat_tile_grid(rt_ctx* ctx, uint8_t* out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,11 +226,16 @@ SIGNATURES = {
     "rt_diag_tile_class_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "rt_diag_tile_classes": (c_int, [c_void_p, _P(c_int), _P(c_int), _P(c_int)]),
     "rt_diag_tile_class_grid": (c_int, [c_void_p, c_void_p, ctypes.c_size_t]),
+    "rt_diag_flat_tiles": (c_int, [c_void_p, _P(c_int), _P(c_int)]),
+    "rt_diag_flat_tile_grid": (c_int, [c_void_p, c_void_p, ctypes.c_size_t]),
+    "rt_diag_disp_sky_word": (c_int, [ctypes.c_uint32, c_int, c_int, _P(ctypes.c_uint32)]),
+    "rt_diag_flat_gates": (c_int, [_P(rt_scene), _P(c_double), _P(c_int), _P(c_int), _P(c_double)]),
 }
 
 _DIAG = {"rt_diag_tile_order", "rt_diag_kernel_resources", "rt_diag_kernel_occupancy", "rt_diag_copy_path",
          "rt_diag_render_route", "rt_diag_sky_tiles", "rt_diag_sky_count", "rt_diag_sky_run_plan", "rt_diag_disp_count",
-         "rt_diag_tile_class_plan", "rt_diag_tile_classes", "rt_diag_tile_class_grid"}
+         "rt_diag_tile_class_plan", "rt_diag_tile_classes", "rt_diag_tile_class_grid", "rt_diag_flat_tiles",
+         "rt_diag_flat_tile_grid", "rt_diag_disp_sky_word", "rt_diag_flat_gates"}
 _lib = None
 
 

@@ -243,4 +243,24 @@ RT_HD bool tile_sphere_free(uint64_t cone, bool sky, const uint64_t* masks, int 
     return (any & bits) == 0;
 }
 
+// The `sky` word of a dispatch record (rt_render.hpp DispRec), built by the two table kernels of rt_plain.hip and, on the
+// host, by rt_diag_disp_sky_word.  `run` is what the word holds for a tile outside the classes: 0 for a tracing tile, the
+// run length (at most kDispRunMax) for a sky record.  A sphere-free tile — a tracing tile, run = 0 — carries
+// kDispSphereFree and, when it is also flat (rt_device.hpp trace_flat), kDispFlat beside it: flat is never set alone, and
+// no run length reaches either bit.
+constexpr uint32_t kDispSphereFree = 0x80000000u, kDispFlat = 0x40000000u, kDispRunMax = 65535u;
+constexpr uint32_t kDispClassBits = kDispSphereFree | kDispFlat;
+static_assert(kDispRunMax < kDispFlat, "run lengths stay below the class bits");
+// The wave-uniform gates of the flat class (rt_device.hpp trace_flat has the proof they feed; rt_plain.hip rt_flat_kernel
+// on the device, rt_diag_flat_gates on the host): the scene has its board, and the eye passes the board's origin skip
+// (origin_skip: |eye.y| <= DevScene::board_skip_y, which is -1 where the skip is not proven).  NaN fails the compare.
+RT_HD bool flat_gates_of(bool has_board, double board_skip_y, double eye_y) {
+    return has_board & (fabs(eye_y) <= board_skip_y);
+}
+
+RT_HD uint32_t disp_sky_word(uint32_t run, bool sphere_free, bool flat) {
+    if (!sphere_free) return run;
+    return kDispSphereFree | (flat ? kDispFlat : 0u);
+}
+
 }  // namespace rt

@@ -103,6 +103,7 @@ static void knobs_from_env(rt_ctx::Knobs& k) {
     if (const char* e = getenv("RT_SKY_TILES")) k.sky_tiles = atoi(e) != 0;
     if (const char* e = getenv("RT_SKY_RUN_MAX")) k.sky_run_max = std::min(std::max(atoi(e), 0), 65535);   // 0: whole streaks
     if (const char* e = getenv("RT_TILE_CLASSES")) k.tile_classes = atoi(e) != 0;
+    if (const char* e = getenv("RT_FLAT_TILES")) k.flat_tiles = atoi(e) != 0;
     if (const char* e = getenv("RT_ORDER_POLICY")) k.order_policy = std::min(std::max(atoi(e), 0), 1);
     if (const char* e = getenv("RT_ACHRO_OFF")) k.achro_off = atoi(e) != 0;
 }

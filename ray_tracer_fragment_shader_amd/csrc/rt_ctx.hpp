@@ -95,6 +95,10 @@ struct rt_ctx {
         // records and cached renders trace them without the sphere code.  RT_TILE_CLASSES=0: no record is marked (A/B;
         // the images are the same bytes).
         bool tile_classes = true;
+        // Flat tiles (rt_device.hpp trace_flat): the sphere-free tiles all of whose primary rays hit the board, which
+        // cached renders trace on the straight-line path.  RT_FLAT_TILES=0: no record is marked flat (A/B; the images
+        // are the same bytes); RT_TILE_CLASSES=0 implies it.
+        bool flat_tiles = true;
         bool achro_off = false;                // RT_ACHRO_OFF=1: the three-channel kernels for achromatic scenes (A/B)
         int sd_split = 2;                      // RT_SDMA_SPLIT: engines a frame's copy is split over (1, 2)
         int sd_writer_req = 0;                 // RT_SDMA_WRITER (A/B): 1 or 2 forces the writer, 0 tries 2 then 1
@@ -158,6 +162,12 @@ struct rt_ctx {
         // class bit of a sphere-free tile's record unless RT_TILE_CLASSES=0, and by rt_diag_tile_classes.
         uint8_t* d_tile_class = nullptr;
         size_t class_tiles_n = 0;
+        // Which of the sphere-free tiles are flat (rt_flat_kernel; `cap` bytes, 1: flat).  View state like the class
+        // byte: rebuilt by every calibration of a view whose kernel instance reads the bit (flat_tiles_n tiles; 0: the
+        // view has none), read by the two table kernels, which set kDispFlat unless RT_FLAT_TILES=0 or RT_TILE_CLASSES=0,
+        // and by rt_diag_flat_tiles.
+        uint8_t* d_tile_flat = nullptr;
+        size_t flat_tiles_n = 0;
         // Runs of sky tiles (rt_run_plan_kernel): beside d_disp the calibration of a view in tile-row order builds
         // d_disp_run, one position per run of up to Knobs::sky_run_max adjacent sky tiles, from the per-position codes
         // d_run_code and their prefix sum d_run_num (hipcub, d_run_tmp).

@@ -1544,6 +1544,65 @@ __device__ __forceinline__ d3 trace(const SceneView& V, d3 p0, d3 p1, uint64_t c
     return acc;
 }
 
+// Flat tiles (render_body's flat branch; fast opaque kernels, cached views): a sphere-free tile (trace NOSPH) whose
+// calibration also found (rt_plain.hip rt_flat_kernel)
+//  (G) has_board, and the eye passes the board's origin skip, |eye.y| <= board_skip_y (flat_gates, wave-uniform);
+//  (F) closest_hit_primary<false, NOSPH> returns the board for all 64 primary rays of the tile, clamped lanes included
+//      (its bounding-sphere cull, where prim_bound_ok is off, is part of that verdict).
+// A cached render traces the same rays with the same operations, so (F) holds in it lane for lane.  What trace<NOSPH>
+// then does, for every lane:
+//  * Level 0 hits the board: kind = 0, and the hit point is the q board_hit<true> forms for a lane that hits,
+//    q = eye + (board_num / (n . d)) d (:657, :665); its sign tests, position decision and exact triangles only decide
+//    `hit`, which (F) says is true.  u = unit(d) (lazy_u), then surface() and unit(rd), ks as below.
+//  * origin_skip(kind 0) returns 0 by (G), for the depths that evaluate it (kSkip); so in shade every
+//    occluded<.., NOSPH>(.., skip = 0) either returns "not blocked" at its bounding-sphere test or falls through the
+//    uncompiled sphere loops and the skipped board test to "not blocked": lit by every light, whatever hits_ok says.
+//    At a depth without the skips (skip = -1) the board test does run, from the board hit q of a ray from the eye — the
+//    very case origin_skip's proof is about: under (G) it misses.  Lit either way.
+//  * Level 1 (B >= 1): closest_hit<.., NOSPH>(.., skip = 0) returns -1 at its cull or after testing nothing; without the
+//    skips its board test misses by the same proof.  levels = 1: seg = min(2, B + 1), shadow = nl, and the right-nested
+//    sum is level 0's colour alone, 0 + term_0 + term_1 + .. in light order (shade's accumulation, in LDS or registers:
+//    the same additions).
+// What is left is the FP64 operations below, the general path's in its order on the same values — no divergent region,
+// no LDS, no FP32 ray image, no level loop.  (The one data-dependent index, the checker material, is 0 or 1 whatever
+// the operands: a padding position that traces a clamped tile under another tile's record reads nothing out of bounds.)
+__device__ __forceinline__ bool flat_gates(const DevScene* S, d3 eye) {
+    return flat_gates_of(S->has_board != 0, S->board_skip_y, eye.y);
+}
+
+template <int B, bool ACHRO>
+__device__ __forceinline__ d3 trace_flat(const SceneView& V, d3 p0, d3 p1, uint32_t* seg, uint32_t* shadow) {
+    const DevScene* S = V.S;
+    const d3 d = sub(p1, p0);
+    const double m = S->board_num / dot(ld3(S->tri[0].n), d);   // board_hit<true>: :648, :657
+    const d3 p = add(p0, scl(m, d));                        // :665
+    const d3 u = unit(d);                                   // closest_hit_primary, lazy_u
+    d3 n, pe;
+    int mat;
+    surface<false>(V, 0, p, u, &n, &mat, &pe);
+    const d3 rd = sub(pe, p);                               // reflectedRay = Line(p, p + r)
+    const double ks = fabs(dot(u, unit(rd)));               // |u . reflectedRay.direction()|
+    const DevMat& M = S->mat[mat];
+    d3 color = mk(0.0, 0.0, 0.0);
+    for (int i = 0; i < V.nl; ++i) {                        // shade, every light lit
+        double dl;
+        const d3 sdir = unit(sub(ld3(S->light[i].pos), p), &dl);   // :1216
+        const double kd = fabs(dot(n, sdir));
+        const double a = S->att / (S->att + dl * dl);       // attenuation (:1181)
+        if (ACHRO) {                                        // R only (shade ACHRO)
+            const double lc = a * S->light[i].col[0];       // :1223
+            color.x = color.x + ((M.amb[0] * lc + kd * (M.diff[0] * lc)) + ks * (M.spec[0] * lc));   // :1224-1226
+        } else {
+            const d3 lC = scl(a, ld3(S->light[i].col));     // :1223
+            color = add(color, add(add(had(ld3(M.amb), lC), scl(kd, had(ld3(M.diff), lC))),
+                                   scl(ks, had(ld3(M.spec), lC))));                                  // :1224-1226
+        }
+    }
+    *seg = B >= 1 ? 2u : 1u;
+    *shadow = (uint32_t)V.nl;
+    return ACHRO ? mk(color.x, color.x, color.x) : color;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Ray trees (scenes with a material that both transmits and reflects, :1238-1247): rayTraceRay recurses
 // into the transmitted child, then the reflected child, and adds each child's colour weighted by T and by

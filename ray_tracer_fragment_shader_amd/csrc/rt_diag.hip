@@ -70,6 +70,34 @@ extern "C" int rt_diag_tile_class_grid(rt_ctx* c, uint8_t* out, size_t n) {
     return tile_classes(c, out, n, true, &tiles, &sky, &sphere_free);
 }
 
+// Diagnostics (include/rt_diag.h): the flat verdicts the last calibration decided (rt_plain.hip rt_flat_kernel), copied
+// out and counted on the host.  grid (or nullptr): n bytes for the view's n tiles.
+static int flat_tiles(rt_ctx* c, uint8_t* grid, size_t n, bool sized, int* tiles, int* flat) {
+    *tiles = *flat = 0;
+    const size_t have = c->view.order_valid && c->view.cone_valid ? c->view.flat_tiles_n : 0;
+    if (sized && n != have) return rt_fail(RT_EINVAL, "rt_diag_flat_tile_grid: n is not the calibrated view's tile count");
+    if (have == 0) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    RT_HIP(hipDeviceSynchronize());
+    std::vector<uint8_t> v(have);
+    RT_HIP(hipMemcpy(v.data(), c->view.d_tile_flat, have, hipMemcpyDeviceToHost));
+    for (uint8_t x : v) *flat += x != 0;
+    *tiles = (int)have;
+    if (grid) memcpy(grid, v.data(), have);
+    return RT_OK;
+}
+
+extern "C" int rt_diag_flat_tiles(rt_ctx* c, int* tiles, int* flat) {
+    if (!c || !tiles || !flat) return rt_fail(RT_EINVAL, "rt_diag_flat_tiles: bad args");
+    return flat_tiles(c, nullptr, 0, false, tiles, flat);
+}
+
+extern "C" int rt_diag_flat_tile_grid(rt_ctx* c, uint8_t* out, size_t n) {
+    if (!c || !out) return rt_fail(RT_EINVAL, "rt_diag_flat_tile_grid: bad args");
+    int tiles, flat;
+    return flat_tiles(c, out, n, true, &tiles, &flat);
+}
+
 // Diagnostics (include/rt_diag.h): the dispatch positions of the last cached render of the calibrated view.
 extern "C" int rt_diag_disp_count(rt_ctx* c, int* positions, int* tiles, int* run_max) {
     if (!c || !positions || !tiles || !run_max) return rt_fail(RT_EINVAL, "rt_diag_disp_count: bad args");

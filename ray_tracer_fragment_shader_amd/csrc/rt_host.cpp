@@ -900,6 +900,31 @@ extern "C" int rt_diag_tile_class_plan(const uint64_t* cone, const uint8_t* sky,
     return RT_OK;
 }
 
+// The `sky` word of a dispatch record (include/rt_diag.h), through the function the device's table kernels run (rt_cone.hpp
+// disp_sky_word).
+extern "C" int rt_diag_disp_sky_word(uint32_t run, int sphere_free, int flat, uint32_t* word) {
+    if (!word || run > rt::kDispRunMax || (sphere_free && run != 0))
+        return rt_fail(RT_EINVAL, "rt_diag_disp_sky_word: bad arguments");
+    *word = rt::disp_sky_word(run, sphere_free != 0, flat != 0);
+    return RT_OK;
+}
+
+// The flat class's wave-uniform gates for `scene` seen from `eye` (include/rt_diag.h), through the function the device runs
+// (rt_cone.hpp flat_gates_of) on the scene record the device gets; and hits_ok for that eye as rt_prepare_kernel sets it
+// (rt_device.hpp hits_ok_from: the same expression).
+extern "C" int rt_diag_flat_gates(const rt_scene* scene, const double* eye, int* gates, int* hits_ok, double* skip_y) {
+    if (!eye || !gates || !hits_ok) return rt_fail(RT_EINVAL, "rt_diag_flat_gates: bad arguments");
+    std::vector<unsigned char> blob;
+    const int rc = rt_build_dev_scene(scene, &blob);
+    if (rc) return rc;
+    const rt::DevScene* d = reinterpret_cast<const rt::DevScene*>(blob.data());
+    *gates = rt::flat_gates_of(d->has_board != 0, d->board_skip_y, eye[1]) ? 1 : 0;
+    const double dx = eye[0] - d->bc[0], dy = eye[1] - d->bc[1], dz = eye[2] - d->bc[2];
+    *hits_ok = ((d->hits_inside != 0) & (dx * dx + dy * dy + dz * dz <= d->hits_lim2)) ? 1 : 0;
+    if (skip_y) *skip_y = d->board_skip_y;
+    return RT_OK;
+}
+
 extern "C" int rt_write_ppm(const char* path, const uint8_t* px, int W, int H, int channels) {
     // writePpmScreenshot (Hw4/ppm.cpp:15-25): header "P6 W H 255\n", then the bottom-up GL image's rows
     // written top-down (image[3*w*(h-1-i)]).

@@ -71,11 +71,18 @@ __global__ __launch_bounds__(256) void rt_iota_kernel(int32_t* __restrict__ v, i
 // bx of tile row row_order[gy]; with the calibration render's per-tile primary cone masks when
 // `cone` (else 0), and their sky verdicts (cone[n + tile], n the tile count).  Stored at cone_slot(L): grouped by the
 // XCD workgroup L runs on.
-// `cls` (or nullptr): the view's tile classes (rt_class_kernel); a sphere-free tile's record carries kDispSphereFree.
+// `cls` (or nullptr): the view's tile classes (rt_class_kernel); a sphere-free tile's record carries kDispSphereFree,
+// and kDispFlat beside it when `flat` (or nullptr: rt_flat_kernel's verdicts) marks the tile (class_bits).
+__device__ __forceinline__ uint32_t class_bits(const uint8_t* __restrict__ cls, const uint8_t* __restrict__ flat, size_t t,
+                                               uint32_t sky) {
+    return disp_sky_word(sky, cls && cls[t] == kClassSphereFree, flat && flat[t]);   // (sphere-free: sky was 0)
+}
+
 __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict__ row_order,
                                                       const int32_t* __restrict__ by_pos,
                                                       const uint64_t* __restrict__ cone,
-                                                      const uint8_t* __restrict__ cls, int tiles_x, int tiles_y,
+                                                      const uint8_t* __restrict__ cls,
+                                                      const uint8_t* __restrict__ flat, int tiles_x, int tiles_y,
                                                       DispRec* __restrict__ disp) {
     const size_t k = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)tiles_x * tiles_y;
     if (k >= n) return;
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     r.cone_hi = (uint32_t)(m >> 32);
     r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
     r.sky = cone ? (uint32_t)cone[n + (size_t)ty * tiles_x + tx] : 0;   // (the verdicts follow the n masks)
-    if (cls && cls[(size_t)ty * tiles_x + tx] == kClassSphereFree) r.sky = kDispSphereFree;   // (not sky: sky was 0)
+    r.sky = class_bits(cls, flat, (size_t)ty * tiles_x + tx, r.sky);
     disp[cone_slot(k, n)] = r;
 }
 
@@ -110,6 +117,41 @@ __global__ __launch_bounds__(256) void rt_class_kernel(const uint64_t* __restric
     const bool sky = cone[(size_t)n + t] != 0;
     cls[t] = sky ? kClassSky
                  : tile_sphere_free(cone[t], false, lmask + (size_t)t * slots, slots, np) ? kClassSphereFree : kClassTrace;
+}
+
+// Which sphere-free tiles of the view are flat (rt_device.hpp trace_flat has the proof this verdict feeds): one wave per
+// tile forms the tile's 64 screen points exactly as render_body does — the same clamping of lanes past the frame, the
+// same row map, the same screen_point — and evaluates the primary closest hit a sphere-free tile's render evaluates
+// (closest_hit_primary<false, NOSPH> with an empty cone mask, lazy_u) on them: flat when every lane returns the board and
+// the wave-uniform gates hold.  P is the calibration render's; the per-eye records (board_num, prim_bound_ok) are those
+// of its eye, stream-ordered before this launch.  A cached render traces the same rays with the same operations, so the
+// verdict is exact for the view.  Tiles of any other class leave 0.
+// One 64-thread workgroup per tile of the whole view, most of which leave at the class test: simpler than compacting the
+// sphere-free tiles first, and it runs once per calibration.  It is launched under RT_FLAT_TILES=0 and RT_TILE_CLASSES=0
+// as well, on purpose: the diagnostics (rt_diag_flat_tiles, tools/wave_trace.py) then name the same tiles on the other
+// path, which is what an A/B of the two paths compares.
+__global__ __launch_bounds__(64) void rt_flat_kernel(const DevScene* __restrict__ g, RenderParams P,
+                                                     const uint8_t* __restrict__ cls, int n,
+                                                     uint8_t* __restrict__ flat) {
+    const int t = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (t >= n) return;
+    bool all = false;
+    const d3 eye = ld3(P.eye);
+    if (cls[t] == kClassSphereFree && flat_gates(g, eye)) {      // (wave-uniform)
+        const int ty = t / P.tiles_x, tx = t - ty * P.tiles_x;
+        const int i = tx * 8 + (lane & 7), lr = ty * kTileH + (lane >> 3);
+        const int ic = i < P.width ? i : P.width - 1, lrc = lr < P.local_rows ? lr : P.local_rows - 1;
+        const int j = global_row_of(P, lrc);
+        const d3 sp = screen_point(P, ic, j, ld3(P.right), ld3(P.upp));
+        const SceneView V = view_of(g, g, P.np, P.ns, P.nl);
+        Ray r;
+        r.p0 = eye;
+        r.d = sub(sp, eye);
+        d3 hp;
+        const int kind = closest_hit_primary<false, true>(V, r, 0, &hp, true);
+        all = __ballot(kind == 0) == ~0ull;
+    }
+    if (lane == 0) flat[t] = all ? 1 : 0;
 }
 
 // The run-compacted dispatch table of a calibrated view in tile-row order (include/rt_diag.h; the plain table stays
@@ -139,6 +181,7 @@ struct RunHead {
 __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restrict__ row_order,
                                                           const uint64_t* __restrict__ cone,
                                                           const uint8_t* __restrict__ cls,
+                                                          const uint8_t* __restrict__ flat,
                                                           const uint32_t* __restrict__ code,
                                                           const uint32_t* __restrict__ number, int tiles_x, int tiles_y,
                                                           DispRec* __restrict__ disp) {
@@ -152,7 +195,7 @@ __global__ __launch_bounds__(256) void rt_run_disp_kernel(const int32_t* __restr
     r.cone_hi = (uint32_t)(m >> 32);
     r.tile = ((uint32_t)ty << 16) | (uint32_t)tx;
     r.sky = code[k] - 1u;
-    if (cls && cls[(size_t)ty * tiles_x + tx] == kClassSphereFree) r.sky = kDispSphereFree;   // (a tracing tile: code 1)
+    r.sky = class_bits(cls, flat, (size_t)ty * tiles_x + tx, r.sky);   // (a tracing tile: code 1, sky word 0)
     disp[cone_slot(number[k] - 1u, number[n - 1])] = r;   // (number[n - 1]: the heads' count, at most n)
 }
 
@@ -238,7 +281,7 @@ static void view_free_run_bufs(rt_ctx::View& v) {
 void rt_free_view_bufs(rt_ctx* c) {
     rt_ctx::View& v = c->view;
     void* bufs[] = {v.d_disp, v.d_tile_cost, v.d_cone_tile, v.d_sort_keys, v.d_sort_in, v.d_sort_out, v.d_sort_tmp,
-                    v.d_tile_class};
+                    v.d_tile_class, v.d_tile_flat};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     view_free_run_bufs(v);
@@ -249,8 +292,8 @@ void rt_free_view_bufs(rt_ctx* c) {
     v.d_disp = nullptr;
     v.d_tile_cost = v.d_sort_keys = nullptr;
     v.d_cone_tile = nullptr;
-    v.d_tile_class = nullptr;
-    v.class_tiles_n = 0;
+    v.d_tile_class = v.d_tile_flat = nullptr;
+    v.class_tiles_n = v.flat_tiles_n = 0;
     v.d_sort_in = v.d_sort_out = nullptr;
     v.d_sort_tmp = nullptr;
     v.sort_tmp_bytes = 0;
@@ -268,6 +311,7 @@ static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
               hipMalloc(&v.d_tile_cost, tiles * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&v.d_cone_tile, 2 * tiles * sizeof(uint64_t)) == hipSuccess &&   // masks, then sky verdicts
               hipMalloc(&v.d_tile_class, tiles) == hipSuccess &&
+              hipMalloc(&v.d_tile_flat, tiles) == hipSuccess &&
               hipMalloc(&v.d_sort_keys, tiles * sizeof(uint32_t)) == hipSuccess &&
               hipMalloc(&v.d_sort_in, tiles * sizeof(int32_t)) == hipSuccess &&
               hipMalloc(&v.d_sort_out, tiles * sizeof(int32_t)) == hipSuccess;
@@ -602,7 +646,7 @@ static void render_grow_calibration(rt_ctx* c, RenderJob& J) {
     } else {
         J.lm_calib = false;
     }
-    v.class_tiles_n = 0;                            // (the classes fall with the masks they are made from)
+    v.class_tiles_n = v.flat_tiles_n = 0;           // (the classes fall with the masks they are made from)
 }
 
 // Step 5: the primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
@@ -681,14 +725,22 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
     const uint64_t* cones = J.cone_calib ? v.d_cone_tile : nullptr;
     // The tile classes of a fast-kernel view with level masks, after the level-mask launch and ahead of the table
     // kernels; the records carry them unless RT_TILE_CLASSES=0.  Culling-kernel views and views without masks have none.
-    const uint8_t* cls = nullptr;
-    v.class_tiles_n = 0;
+    const uint8_t *cls = nullptr, *flat = nullptr;
+    v.class_tiles_n = v.flat_tiles_n = 0;
     if (J.cone_calib && J.lm_calib && !J.cull_kernel && c->scene.n_padded <= 64) {
         hipLaunchKernelGGL(rt_class_kernel, tg, dim3(256), 0, st, v.d_cone_tile, v.d_lmask, J.lm_stride,
                            c->scene.n_padded, tiles, v.d_tile_class);
         v.class_tiles_n = J.tiles;
         // (only into the records of a view whose kernel instance reads the bit: rt_render.hpp class_instance)
-        if (c->knobs.tile_classes && class_instance(J.mode == kModePacked, J.mode == kModeSS, J.depth)) cls = v.d_tile_class;
+        if (class_instance(J.mode == kModePacked, J.mode == kModeSS, J.depth)) {
+            if (c->knobs.tile_classes) cls = v.d_tile_class;
+            // ... and which of the sphere-free tiles are flat, for the same instances: the calibration render's rays,
+            // re-formed from its parameters (rt_flat_kernel).  In the records unless RT_FLAT_TILES=0 (or no class is).
+            hipLaunchKernelGGL(rt_flat_kernel, dim3((unsigned)tiles), dim3(64), 0, st, c->scene.d_scene, J.P,
+                               v.d_tile_class, tiles, v.d_tile_flat);
+            v.flat_tiles_n = J.tiles;
+            if (cls && c->knobs.flat_tiles) flat = v.d_tile_flat;
+        }
     }
     if (c->knobs.order_policy == 1) {                     // tiles longest first
         hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, v.d_sort_in, (int)tiles);
@@ -696,13 +748,13 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
         e = hipcub::DeviceRadixSort::SortPairsDescending(v.d_sort_tmp, tmp, v.d_tile_cost, v.d_sort_keys,
                                                          v.d_sort_in, v.d_sort_out, (int)tiles, 0, 32, st);
         if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, cls, tiles_x, tiles_y,
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, cls, flat, tiles_x, tiles_y,
                            v.d_disp);
     } else {                                        // tile rows longest first
         hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, v.d_tile_cost, tiles_x,
                            v.d_row_cost);
         hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, v.d_row_cost, tiles_y, v.d_tile_rows);
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, cls, tiles_x, tiles_y,
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, cls, flat, tiles_x, tiles_y,
                            v.d_disp);
         // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
         // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
@@ -715,7 +767,7 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
             hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, v.d_tile_rows,
                                v.d_cone_tile + J.tiles, tiles_x, run_max, v.d_run_code);
             if (hipcub::DeviceScan::InclusiveSum(v.d_run_tmp, tmp, heads, v.d_run_num, tiles, st) == hipSuccess) {
-                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, cls,
+                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, cls, flat,
                                    v.d_run_code, v.d_run_num, tiles_x, tiles_y, v.d_disp_run);
                 if (hipMemcpyAsync(v.h_run_n, v.d_run_num + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    st) == hipSuccess &&

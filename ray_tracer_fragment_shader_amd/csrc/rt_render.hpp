@@ -107,7 +107,10 @@ struct alignas(16) DispRec {
     uint32_t tile;
     uint32_t sky;
 };
-constexpr uint32_t kDispSphereFree = 0x80000000u;
+// Bit 30 (kDispFlat) marks a sphere-free tile that is also flat (rt_device.hpp trace_flat; decided by rt_plain.hip
+// rt_flat_kernel at calibration): set only together with the top bit, in the records of the same instances' views.
+// (Both constants, kDispSphereFree and kDispFlat, and the word's construction are in rt_cone.hpp: disp_sky_word, which the
+// host evaluates too.)
 // Which fast one-wave opaque instances read the class bit (render_body) — and so which views' records may carry it
 // (rt_plain.hip render_build_dispatch; an instance that does not read it would take the bit for a run length): the RGBA
 // instances of every depth and the packed ones up to depth 1.  Not the packed instances beyond depth 1: the second trace
@@ -463,7 +466,7 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
     // Sphere-free tiles (DispRec, kDispSphereFree): the fast one-wave opaque instances read the class bit of a cached
     // view's record; the records of every other instance's views never have it set, and their code is as it was.
     constexpr bool kClassInst = kSkyInst && !CULL && class_instance(PACKED, SS, B);
-    const uint32_t sky_len = kClassInst ? sky_cached & ~kDispSphereFree : sky_cached;
+    const uint32_t sky_len = kClassInst ? sky_cached & ~kDispClassBits : sky_cached;
     bool sky = false;
     RT_COUNT(V.S, kCntWaves, 1);
     if (P.np >= kPrimaryConeMin && P.cone_use) {
@@ -583,7 +586,12 @@ __device__ __forceinline__ void render_body(const DevScene* __restrict__ gscene,
             // read once, made a scalar, consumed by this branch — nothing of it lives through a trace): the same trace
             // compiled without the sphere loops and without the level-mask reads (trace NOSPH).  The prologue above and
             // the stores below are shared.
-            if (P.cone_use && __builtin_amdgcn_readfirstlane((int)(sky_cached >> 31)) != 0)
+            // A flat tile (kDispFlat, set only beside the class bit): all 64 primary rays hit the board and nothing else
+            // can happen to them — the straight-line path, trace_flat, which has the proof.
+            const uint32_t cls = P.cone_use ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(sky_cached >> 30)) : 0u;
+            if (cls == 3u)
+                col = trace_flat<B, ACHRO>(V, eye, sp, &seg, &sh);
+            else if (cls != 0u)
                 col = trace<B, true, false, false, WG, ACHRO, false, false, true>(V, eye, sp, 0, &seg, &sh, slot, mslot);
             else
                 col = trace<B, true, TRANSP, CULL, WG, ACHRO>(V, eye, sp, cone, &seg, &sh, slot, mslot, lm);

@@ -4,7 +4,8 @@ tools/_ab/<name>/librt_amd.so (r06: the experiment builds that travel to the GPU
 their renders interleaved round by round — so box-to-box and process-to-process clock differences (±2% at c2)
 cancel out.
 
-usage: ab_libs.py [c2,c3,c5] [rounds]        prints one JSON line per (config, lib): median / min kernel ms
+usage: ab_libs.py [c2,c3,c5] [rounds]        prints one JSON line per (config, lib): median / min / max kernel ms and
+                                             every round's figure (rounds_ms, in order)
 INFLIGHT=k: bench.py's timed pattern instead — k contexts, streams and output buffers per build, frames issued
 round-robin, per-frame interval = (last stream's end - start) / frames.
 """
@@ -147,7 +148,7 @@ def main():
         base = statistics.median(res[(c, "base")])
         med = statistics.median(v)
         print(json.dumps({"config": c, "lib": name, "median_ms": round(med, 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
-                          "vs_base": round(med / base - 1, 4)}))
+                          "vs_base": round(med / base - 1, 4), "rounds_ms": [round(x, 4) for x in v]}))
     for name, L in libs.items():
         L.rt_ctx_destroy(ctxs[name])
         for c in fly_ctx[name]:

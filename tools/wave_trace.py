@@ -8,7 +8,9 @@ positions the launch really had (rt_diag_disp_count) say how many records to rea
 traces the plain table, one wave per tile.
 Every record names its position's tile, and the context's class grid (rt_diag_tile_class_grid: decided at calibration
 whether or not RT_TILE_CLASSES lets the records carry it) splits the per-phase figures into sky positions, sphere-free
-tiles and the other tracing tiles — under RT_TILE_CLASSES=0 the same tiles on the general path.
+tiles and the other tracing tiles — under RT_TILE_CLASSES=0 the same tiles on the general path.  The sphere-free tiles
+are split again by the flat grid (rt_diag_flat_tile_grid, likewise decided whatever RT_FLAT_TILES says): flat tiles, on the
+straight-line path or (RT_FLAT_TILES=0) on the sphere-free one, and the sphere-free tiles that are not flat.
 usage: wave_trace.py [config]"""
 import ctypes
 import json
@@ -113,14 +115,18 @@ def main():
         sky = dur <= np.percentile(dur, 50)
         out["trace_us_short_half"] = round(float((t_tr - md)[sky].mean()), 3)
         out["trace_us_long_half"] = round(float((t_tr - md)[~sky].mean()), 3)
-    # the same per-phase means by the class of the position's tile (0 tracing, 1 sky, 2 sphere-free)
+    # the same per-phase means by the class of the position's tile (0 tracing, 1 sky, 2 sphere-free, 3 flat)
     tx_n, ty_n = (W + 7) // 8, (H + 7) // 8
     grid = np.zeros((ty_n, tx_n), np.uint8)
     if hasattr(lib, "rt_diag_tile_class_grid") and lib.rt_diag_tile_class_grid(t._ctx, grid.ctypes.data, grid.size) == 0:
         cls = grid[np.minimum(tile_y, ty_n - 1), np.minimum(tile_x, tx_n - 1)]
         out["tile_classes_env"] = os.environ.get("RT_TILE_CLASSES", "")
+        flat = np.zeros((ty_n, tx_n), np.uint8)
+        if hasattr(lib, "rt_diag_flat_tile_grid") and lib.rt_diag_flat_tile_grid(t._ctx, flat.ctypes.data, flat.size) == 0:
+            out["flat_tiles_env"] = os.environ.get("RT_FLAT_TILES", "")
+            cls = np.where((cls == 2) & (flat[np.minimum(tile_y, ty_n - 1), np.minimum(tile_x, tx_n - 1)] != 0), 3, cls)
         out["by_class"] = {}
-        for name_c, code in (("tracing_other", 0), ("sky", 1), ("sphere_free", 2)):
+        for name_c, code in (("tracing_other", 0), ("sky", 1), ("sphere_free", 2), ("flat", 3)):
             m = cls == code
             if not m.any():
                 continue
