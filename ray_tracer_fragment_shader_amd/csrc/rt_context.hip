@@ -61,16 +61,11 @@ extern "C" int rt_ctx_destroy(rt_ctx* c) {
     if (c->frames.cs) (void)hipStreamSynchronize(c->frames.cs);
     if (c->scene.d_scene) (void)hipFree(c->scene.d_scene);
     if (c->scene.d_motion) (void)hipFree(c->scene.d_motion);
-    if (c->view.d_tile_rows) (void)hipFree(c->view.d_tile_rows);
-    if (c->view.d_row_cost) (void)hipFree(c->view.d_row_cost);
-    rt_free_view_bufs(c);
-    if (c->view.d_lmask) (void)hipFree(c->view.d_lmask);
+    view_release(c);
     sdma_destroy(c);
     if (c->frames.ev0) (void)hipEventDestroy(c->frames.ev0);
     if (c->frames.ev1) (void)hipEventDestroy(c->frames.ev1);
     if (c->sync.view_ev) (void)hipEventDestroy(c->sync.view_ev);
-    if (c->view.run_ev) (void)hipEventDestroy(c->view.run_ev);
-    if (c->view.h_run_n) (void)hipHostFree(c->view.h_run_n);
     for (int b = 0; b < rt_ctx::kSlots; ++b) {
         if (c->frames.rendered[b]) (void)hipEventDestroy(c->frames.rendered[b]);
         if (c->frames.copied[b]) (void)hipEventDestroy(c->frames.copied[b]);
@@ -119,17 +114,13 @@ extern "C" int rt_ctx_create(int device, rt_ctx** out) {
     rt_ctx* c = new rt_ctx();
     c->device = device;
     knobs_from_env(c->knobs);
-    if (hipMalloc(&c->view.d_tile_rows, sizeof(int32_t) * kOrderMax) != hipSuccess ||
-        hipMalloc(&c->view.d_row_cost, sizeof(uint32_t) * kOrderMax) != hipSuccess) {
+    if ((rc = view_create(c))) {
         rt_ctx_destroy(c);
-        return rt_fail(RT_ENOMEM, "rt_ctx_create: hipMalloc of the tile-row order failed");
+        return rt_fail(rc, rc == RT_ENOMEM ? "rt_ctx_create: hipMalloc of the tile-row order failed"
+                                           : "rt_ctx_create: stream/event creation failed");
     }
-    c->view.n_tile_rows = kOrderMax;
-    bool ok = hipMemset(c->view.d_tile_rows, 0, sizeof(int32_t) * kOrderMax) == hipSuccess &&
-              hipEventCreate(&c->frames.ev0) == hipSuccess && hipEventCreate(&c->frames.ev1) == hipSuccess &&
+    bool ok = hipEventCreate(&c->frames.ev0) == hipSuccess && hipEventCreate(&c->frames.ev1) == hipSuccess &&
               hipEventCreateWithFlags(&c->sync.view_ev, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&c->view.run_ev, hipEventDisableTiming) == hipSuccess &&
-              hipHostMalloc(&c->view.h_run_n, sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
               hipStreamCreateWithFlags(&c->frames.rs, hipStreamDefault) == hipSuccess &&
               hipStreamCreateWithFlags(&c->frames.cs, hipStreamNonBlocking) == hipSuccess;
     for (int b = 0; b < rt_ctx::kSlots && ok; ++b)

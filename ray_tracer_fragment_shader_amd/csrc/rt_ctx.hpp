@@ -25,6 +25,7 @@
 #include <hsa/hsa.h>                           // the types of rt_ctx::Sdma only (the calls: rt_frames.hip)
 
 #include <array>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -38,7 +39,30 @@ struct RenderParams;
 
 constexpr int kOrderMax = 8192;                // tile rows rt_order_kernel sorts (one workgroup, keys in LDS)
 constexpr int kRecalibrate = 8;                // renders of a moving camera per re-timing of the tile rows
-constexpr uint8_t kClassTrace = 0, kClassSky = 1, kClassSphereFree = 2;   // rt_ctx::View::d_tile_class
+constexpr uint8_t kClassTrace = 0, kClassSky = 1, kClassSphereFree = 2;   // rt_ctx::View::tile_class
+
+// A grow-only device buffer.  reserve: room for `n` bytes, by free-then-malloc when it is too small (the caller orders
+// that against the work that reads it); false, and an empty buffer, when the device is out of memory.  No destructor:
+// the owner releases it with its device set.
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    bool reserve(size_t n) {
+        if (n <= bytes) return true;
+        release();
+        if (hipMalloc(&p, n) == hipSuccess) return bytes = n, true;
+        (void)hipGetLastError();
+        p = nullptr;
+        return false;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    T* get() const { return p; }
+};
 
 struct rt_ctx {
     int device = 0;
@@ -113,7 +137,7 @@ struct rt_ctx {
                                                // the per-eye data, so every later render re-prepares it
     } eye;
 
-    // The view cache (rt_plain.hip; read by rt_diag.hip).
+    // The view cache (rt_plain.hip alone writes it; rt_diag.hip reads it).
     // Adaptive tile-row order (rt_order_kernel): the first render of a new (scene, camera, size, rows,
     // depth, outputs) view uses the identity order; the second render of the same view is a calibration
     // render that also times its tile rows; later renders dispatch the rows by decreasing time.  A render
@@ -123,76 +147,73 @@ struct rt_ctx {
     // on it.
     using ViewKey = std::array<unsigned char, sizeof(rt_camera) + 6 * sizeof(int) + sizeof(rt_rows) + sizeof(uint64_t)>;
     struct View {
-        int32_t* d_tile_rows = nullptr;        // row order: tile rows by decreasing calibrated time
-        uint32_t* d_row_cost = nullptr;        // ... their times (rt_rowsum_kernel)
-        int n_tile_rows = 0;                   // capacity of both (kOrderMax, allocated by rt_ctx_create)
-        // The view's dispatch table (rt_disp_kernel) and what builds it, per tile (`cap` tiles each): the calibration
-        // render's wave times (d_tile_cost) and cone masks (d_cone_tile), and the tile order's radix-sort buffers.
-        rtk::DispRec* d_disp = nullptr;
-        uint32_t* d_tile_cost = nullptr;
-        uint32_t* d_sort_keys = nullptr;
-        int32_t* d_sort_in = nullptr;
-        int32_t* d_sort_out = nullptr;
-        void* d_sort_tmp = nullptr;
-        size_t sort_tmp_bytes = 0;
-        size_t cap = 0;
-        bool order_valid = false;              // d_tile_rows holds the order of view `order_key`
-        ViewKey order_key{};
-        bool seen_valid = false;               // `seen_key`: the last view rendered once in identity order
-        ViewKey seen_key{};
-        int stale = 0;                         // renders of other cameras since the order was calibrated
-        // Primary cone masks of the calibrated view (scenes with >= kPrimaryConeMin spheres): the calibration render
-        // writes each tile's mask (d_cone_tile), rt_disp_kernel puts them in the dispatch table, and later renders of
-        // exactly that view (order_key) read them instead of recomputing them.  Renders of another camera compute their
-        // own.  One-wave (8 x 8 tile) variants only.  Ordering against renders on other streams: rt_ctx::Sync.
-        uint64_t* d_cone_tile = nullptr;
-        bool cone_valid = false;               // d_disp holds the masks of view order_key
-        // r06: the culling kernels' level masks of view order_key, lmask_stride per tile (rt_device.hpp LevelMasks),
-        // written by its calibration render (grow-only, lmask_cap masks)
-        uint64_t* d_lmask = nullptr;
-        size_t lmask_cap = 0;
-        int lmask_stride = 0;
-        bool lmask_valid = false;
-        // The calibration render leaves its waves' sky verdicts behind the cone masks in d_cone_tile (sky_tiles_n of
-        // them: rt_diag_sky_count).
-        size_t sky_tiles_n = 0;
-        // The tile classes of view order_key (rt_class_kernel; `cap` bytes): 0 a tracing tile, 1 sky, 2 sphere-free.
-        // View state like the masks they are made from: rebuilt by every calibration (class_tiles_n tiles; 0: the view
-        // has none — a culling-kernel scene, no level masks), read by rt_disp_kernel / rt_run_disp_kernel, which set the
-        // class bit of a sphere-free tile's record unless RT_TILE_CLASSES=0, and by rt_diag_tile_classes.
-        uint8_t* d_tile_class = nullptr;
-        size_t class_tiles_n = 0;
-        // Which of the sphere-free tiles are flat (rt_flat_kernel; `cap` bytes, 1: flat).  View state like the class
-        // byte: rebuilt by every calibration of a view whose kernel instance reads the bit (flat_tiles_n tiles; 0: the
-        // view has none), read by the two table kernels, which set kDispFlat unless RT_FLAT_TILES=0 or RT_TILE_CLASSES=0,
-        // and by rt_diag_flat_tiles.
-        uint8_t* d_tile_flat = nullptr;
-        size_t flat_tiles_n = 0;
-        // Runs of sky tiles (rt_run_plan_kernel): beside d_disp the calibration of a view in tile-row order builds
-        // d_disp_run, one position per run of up to Knobs::sky_run_max adjacent sky tiles, from the per-position codes
-        // d_run_code and their prefix sum d_run_num (hipcub, d_run_tmp).
-        // Its position count reaches the host without a stall of the calibrating call: a copy into the pinned word
-        // h_run_n queued behind the table kernels, then run_ev; the next render of the view waits for run_ev (long
-        // passed, as a rule) and sizes its grid from the count (run_n; run_w positions per grid row).  Only cached
-        // renders of exactly that view read d_disp_run (render_plan_view); it is view state like d_disp (Sync::view_ev).
-        rtk::DispRec* d_disp_run = nullptr;
-        uint32_t* d_run_code = nullptr;
-        uint32_t* d_run_num = nullptr;
-        void* d_run_tmp = nullptr;
-        size_t run_tmp_bytes = 0;
-        uint32_t* h_run_n = nullptr;
-        hipEvent_t run_ev = nullptr;
-        bool run_pending = false;              // run_ev recorded, h_run_n not read yet
-        bool run_valid = false;                // d_disp_run holds view order_key's table of run_n positions
-        uint32_t run_n = 0;
-        int run_w = 0, run_rows = 0;
-        int run_built_max = 1;                 // the run maximum d_disp_run was built with
-        int last_positions = 0, last_tiles = 0, last_run_max = 0;   // rt_diag_disp_count
+        // What the buffers below hold of the ONE calibrated view, `cal`.  No value: there is none, and a render takes
+        // the identity order and computes its masks in the kernel.  A calibration render drops it when it starts
+        // (render_plan_view) and render_build_dispatch assigns the next one once its table kernels are queued;
+        // rt_diag_tile_order drops it too (view_forget).  Only cached renders — renders of exactly `key` — read the
+        // masks, the classes and the run table; the diagnostics describe it.
+        enum class Runs { none, pending, ready };
+        struct Calibrated {
+            ViewKey key{};
+            size_t tiles = 0;
+            // Primary cone masks (scenes with >= kPrimaryConeMin spheres, one-wave 8 x 8 tiles only): the calibration
+            // render wrote each tile's mask and, behind the `tiles` masks, its sky verdict to cone_tile, and
+            // rt_disp_kernel put both into the records of disp; cached renders read them instead of recomputing them.
+            bool cones = false;
+            // The culling kernels' level masks in lmask, this many per tile (rt_device.hpp LevelMasks; 0: none).  A
+            // cached render reads them only when its own stride is this one.
+            int lmask_stride = 0;
+            // tile_class holds the view's tile classes (rt_class_kernel: a fast-kernel view with level masks), which
+            // the table kernels put into the records unless RT_TILE_CLASSES=0; tile_flat holds which sphere-free tiles
+            // are flat (rt_flat_kernel: such a view whose kernel instance reads the bit; in the records unless
+            // RT_FLAT_TILES=0 or RT_TILE_CLASSES=0).  rt_diag_tile_classes and rt_diag_flat_tiles read the two arrays.
+            bool classes = false, flat = false;
+            // Runs of sky tiles (rt_run_plan_kernel): beside disp the calibration of a view in tile-row order builds
+            // disp_run, one position per run of up to Knobs::sky_run_max adjacent sky tiles.  Its position count reaches
+            // the host without a stall of the calibrating call: a copy into the pinned word h_run_n queued behind the
+            // table kernels, then run_ev (pending); the next cached render waits for run_ev (long passed, as a rule) and
+            // reads the count: ready, with run_n positions, run_w per grid row, or none (a failed wait, no sky tile).
+            Runs runs = Runs::none;
+            uint32_t run_n = 0;
+            int run_w = 0, run_rows = 0;
+            int run_built_max = 1;                 // the run maximum disp_run was built with
+            int stale = 0;                         // renders of other cameras since (RT_MOVING_ORDER=1)
+        };
+        std::optional<Calibrated> cal;
+        std::optional<ViewKey> seen;               // the last view rendered once in identity order: its next render calibrates
+        struct Last {                              // the last cached render, whatever happened since (rt_diag_disp_count)
+            int positions = 0, tiles = 0, run_max = 0;
+        } last;
+
+        // The buffers, grouped as they grow (view_create, view_release, rt_grow_view_bufs).  Ordering against renders on
+        // other streams: rt_ctx::Sync.
+        // kOrderMax entries each, created with the context: the row order (tile rows by decreasing calibrated time) and
+        // the rows' times (rt_rowsum_kernel).
+        DevBuf<int32_t> tile_rows;
+        DevBuf<uint32_t> row_cost;
+        // Per tile, all grown together to `tiles_cap` tiles: the view's dispatch table (rt_disp_kernel), the calibration
+        // render's wave times, its cone masks and sky verdicts (2 per tile), the class and flat bytes, and the tile
+        // order's radix-sort buffers.
+        size_t tiles_cap = 0;
+        DevBuf<rtk::DispRec> disp;
+        DevBuf<uint32_t> tile_cost, sort_keys;
+        DevBuf<uint64_t> cone_tile;
+        DevBuf<uint8_t> tile_class, tile_flat;
+        DevBuf<int32_t> sort_in, sort_out;
+        DevBuf<void> sort_tmp;
+        // ... and the run table's, all or none (without them every render reads the plain table): the table, the
+        // per-position codes, their prefix sum (hipcub, run_tmp).
+        DevBuf<rtk::DispRec> disp_run;
+        DevBuf<uint32_t> run_code, run_num;
+        DevBuf<void> run_tmp;
+        DevBuf<uint64_t> lmask;                    // the level masks, a capacity of their own
+        uint32_t* h_run_n = nullptr;               // pinned: the run table's position count
+        hipEvent_t run_ev = nullptr;               // ... is in h_run_n
     } view;
 
     // Cross-stream ordering of the per-view state (rt_plain.hip render_order_streams, render_record_view): the per-eye
-    // records inside d_scene (rt_prepare_kernel) and the calibration buffers (d_row_cost, d_tile_rows, d_tile_cost,
-    // d_cone_tile, d_disp).  Every render reads the per-eye records; a render that prepares a new eye or calibrates
+    // records inside d_scene (rt_prepare_kernel) and the view's buffers (View::row_cost, tile_rows, tile_cost,
+    // cone_tile, disp, ...).  Every render reads the per-eye records; a render that prepares a new eye or calibrates
     // also writes.  A writer records view_ev on its stream after its last write; a render on another stream first
     // waits for view_ev on the GPU (read-after-write, write-after-write).  Renders are tracked by stream: a writer
     // drains the device first when renders were queued on a stream other than its own since the last drain
@@ -262,11 +283,18 @@ inline int ss_log2_of(int samples) {
     return samples == 1 ? 0 : samples == 2 ? 1 : samples == 4 ? 2 : samples == 8 ? 3 : -1;
 }
 
-// rt_plain.hip.  The per-tile view buffers freed (rt_ctx_destroy); the device render behind rt_render_dev /
-// rt_render_dev_packed, with ray counters beside a packed image (render_packed_queue); the checks every render makes
-// on its context, camera, size, depth and row plan, and the rows this process renders; the front of the sampled _dev
-// entry points.
-void rt_free_view_bufs(rt_ctx* c);
+// rt_plain.hip.  The view cache's buffers, event and pinned word made (rt_ctx_create, with the device set; RT_OK, RT_ENOMEM
+// or RT_EHIP) and released (rt_ctx_destroy, likewise); the calibrated view and the view seen once forgotten, so that the next
+// two renders calibrate afresh (rt_diag_tile_order); the device render behind rt_render_dev / rt_render_dev_packed, with
+// ray counters beside a packed image (render_packed_queue); the checks every render makes on its context, camera, size,
+// depth and row plan, and the rows this process renders; the front of the sampled _dev entry points.
+int view_create(rt_ctx* c);
+void view_release(rt_ctx* c);
+void view_forget(rt_ctx* c);
+// The calibrated view if it has cone masks and sky verdicts — what the view diagnostics describe — or nullptr.
+inline const rt_ctx::View::Calibrated* view_with_cones(const rt_ctx* c) {
+    return c->view.cal && c->view.cal->cones ? &*c->view.cal : nullptr;
+}
 int render_dev_impl(rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows, int fmt_f, void* pf,
                     int fmt_8, void* p8, double* rgb64f, uint32_t* raycount, void* stream, int ss_log2 = -1);
 int render_local_rows(const rt_ctx* c, const rt_camera* cam, int W, int H, int depth, const rt_rows* rows,

@@ -15,10 +15,7 @@ using namespace rtk;
 extern "C" int rt_diag_tile_order(rt_ctx* c, int mode) {
     if (!c || (mode != 0 && mode != 1)) return rt_fail(RT_EINVAL, "rt_diag_tile_order: bad args");
     c->knobs.order_mode = mode;
-    // (the order and the view seen once, so that the next two renders calibrate afresh; the run table's flags stay:
-    // nothing reads them while order_valid is false, and that calibration clears them, rt_plain.hip view_invalidate)
-    c->view.order_valid = false;
-    c->view.seen_valid = false;
+    view_forget(c);                             // the next two renders calibrate afresh
     return RT_OK;
 }
 
@@ -27,11 +24,12 @@ extern "C" int rt_diag_tile_order(rt_ctx* c, int mode) {
 extern "C" int rt_diag_sky_count(rt_ctx* c, int* tiles, int* sky) {
     if (!c || !tiles || !sky) return rt_fail(RT_EINVAL, "rt_diag_sky_count: bad args");
     *tiles = *sky = 0;
-    if (!c->view.order_valid || !c->view.cone_valid || c->view.sky_tiles_n == 0) return RT_OK;
+    const rt_ctx::View::Calibrated* k = view_with_cones(c);
+    if (!k) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     RT_HIP(hipDeviceSynchronize());
-    std::vector<uint64_t> v(c->view.sky_tiles_n);
-    RT_HIP(hipMemcpy(v.data(), c->view.d_cone_tile + c->view.sky_tiles_n, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<uint64_t> v(k->tiles);          // (the verdicts follow the view's cone masks)
+    RT_HIP(hipMemcpy(v.data(), c->view.cone_tile.get() + k->tiles, v.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     int n = 0;
     for (uint64_t x : v) n += x != 0;
     *tiles = (int)v.size();
@@ -43,13 +41,14 @@ extern "C" int rt_diag_sky_count(rt_ctx* c, int* tiles, int* sky) {
 // out and counted on the host.  grid (or nullptr): n bytes for the view's n tiles.
 static int tile_classes(rt_ctx* c, uint8_t* grid, size_t n, bool sized, int* tiles, int* sky, int* sphere_free) {
     *tiles = *sky = *sphere_free = 0;
-    const size_t have = c->view.order_valid && c->view.cone_valid ? c->view.class_tiles_n : 0;
+    const rt_ctx::View::Calibrated* k = view_with_cones(c);
+    const size_t have = k && k->classes ? k->tiles : 0;
     if (sized && n != have) return rt_fail(RT_EINVAL, "rt_diag_tile_class_grid: n is not the calibrated view's tile count");
     if (have == 0) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     RT_HIP(hipDeviceSynchronize());
     std::vector<uint8_t> v(have);
-    RT_HIP(hipMemcpy(v.data(), c->view.d_tile_class, have, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(v.data(), c->view.tile_class.get(), have, hipMemcpyDeviceToHost));
     for (uint8_t x : v) {
         *sky += x == kClassSky;
         *sphere_free += x == kClassSphereFree;
@@ -74,13 +73,14 @@ extern "C" int rt_diag_tile_class_grid(rt_ctx* c, uint8_t* out, size_t n) {
 // out and counted on the host.  grid (or nullptr): n bytes for the view's n tiles.
 static int flat_tiles(rt_ctx* c, uint8_t* grid, size_t n, bool sized, int* tiles, int* flat) {
     *tiles = *flat = 0;
-    const size_t have = c->view.order_valid && c->view.cone_valid ? c->view.flat_tiles_n : 0;
+    const rt_ctx::View::Calibrated* k = view_with_cones(c);
+    const size_t have = k && k->flat ? k->tiles : 0;
     if (sized && n != have) return rt_fail(RT_EINVAL, "rt_diag_flat_tile_grid: n is not the calibrated view's tile count");
     if (have == 0) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     RT_HIP(hipDeviceSynchronize());
     std::vector<uint8_t> v(have);
-    RT_HIP(hipMemcpy(v.data(), c->view.d_tile_flat, have, hipMemcpyDeviceToHost));
+    RT_HIP(hipMemcpy(v.data(), c->view.tile_flat.get(), have, hipMemcpyDeviceToHost));
     for (uint8_t x : v) *flat += x != 0;
     *tiles = (int)have;
     if (grid) memcpy(grid, v.data(), have);
@@ -101,9 +101,9 @@ extern "C" int rt_diag_flat_tile_grid(rt_ctx* c, uint8_t* out, size_t n) {
 // Diagnostics (include/rt_diag.h): the dispatch positions of the last cached render of the calibrated view.
 extern "C" int rt_diag_disp_count(rt_ctx* c, int* positions, int* tiles, int* run_max) {
     if (!c || !positions || !tiles || !run_max) return rt_fail(RT_EINVAL, "rt_diag_disp_count: bad args");
-    *positions = c->view.last_positions;
-    *tiles = c->view.last_tiles;
-    *run_max = c->view.last_run_max;
+    *positions = c->view.last.positions;
+    *tiles = c->view.last.tiles;
+    *run_max = c->view.last.run_max;
     return RT_OK;
 }
 

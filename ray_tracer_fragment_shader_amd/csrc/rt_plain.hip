@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void rt_disp_kernel(const int32_t* __restrict_
     disp[cone_slot(k, n)] = r;
 }
 
-// The class of every tile of a fast-kernel view (rt_ctx::View::d_tile_class), from what its calibration left: the cone
+// The class of every tile of a fast-kernel view (rt_ctx::View::tile_class), from what its calibration left: the cone
 // masks and sky verdicts of the calibration render (cone, then n verdicts) and the `slots` level masks per tile of the
 // level-mask launch, whose buffer was zeroed before that launch, so a slot no wave reached reads 0.
 __global__ __launch_bounds__(256) void rt_class_kernel(const uint64_t* __restrict__ cone,
@@ -260,90 +260,81 @@ extern "C" int rt_debug_wave_trace(void* dev_buf) {
 #endif
 
 // ---- the view cache (rt_ctx::View): only the functions from here to render_record_view write it ------------------------
-// The calibrated view is no more: its order — every cached mask is read under order_valid only — and its run table.
-// Both branches of render_plan_view that start a calibration come here; render_build_dispatch makes the next view valid.
-static void view_invalidate(rt_ctx::View& v) {
-    v.order_valid = false;
-    v.run_valid = v.run_pending = false;
+// Its legal states are the values of View::cal and View::seen (rt_ctx.hpp): "no calibrated view" is cal.reset(), and
+// render_build_dispatch alone makes one.  The buffers know their own capacities (DevBuf).
+void view_forget(rt_ctx* c) {
+    c->view.cal.reset();
+    c->view.seen.reset();
 }
 
-// The run table's buffers freed (all or none are held).
-static void view_free_run_bufs(rt_ctx::View& v) {
-    void* bufs[] = {v.d_disp_run, v.d_run_code, v.d_run_num, v.d_run_tmp};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    v.d_disp_run = nullptr;
-    v.d_run_code = v.d_run_num = nullptr;
-    v.d_run_tmp = nullptr;
+template <class... B>
+static void release_all(B&... b) {
+    (b.release(), ...);
 }
 
-// The per-tile view buffers (dispatch table, tile times, cone masks, sort buffers) of a context.
-void rt_free_view_bufs(rt_ctx* c) {
+// The per-tile buffers freed, and with them the view they described.
+static void view_release_tiles(rt_ctx::View& v) {
+    v.cal.reset();
+    release_all(v.disp, v.tile_cost, v.cone_tile, v.tile_class, v.tile_flat, v.sort_keys, v.sort_in, v.sort_out, v.sort_tmp,
+                v.disp_run, v.run_code, v.run_num, v.run_tmp);
+    v.tiles_cap = 0;
+}
+
+int view_create(rt_ctx* c) {
     rt_ctx::View& v = c->view;
-    void* bufs[] = {v.d_disp, v.d_tile_cost, v.d_cone_tile, v.d_sort_keys, v.d_sort_in, v.d_sort_out, v.d_sort_tmp,
-                    v.d_tile_class, v.d_tile_flat};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    view_free_run_bufs(v);
-    v.run_tmp_bytes = 0;
-    // (the run table's flags alone, not view_invalidate: the row order in d_tile_rows is not freed here, and the one
-    // caller with a view to lose, a calibrating render, has invalidated it in step 2)
-    v.run_valid = v.run_pending = false;
-    v.d_disp = nullptr;
-    v.d_tile_cost = v.d_sort_keys = nullptr;
-    v.d_cone_tile = nullptr;
-    v.d_tile_class = v.d_tile_flat = nullptr;
-    v.class_tiles_n = v.flat_tiles_n = 0;
-    v.d_sort_in = v.d_sort_out = nullptr;
-    v.d_sort_tmp = nullptr;
-    v.sort_tmp_bytes = 0;
-    v.cap = 0;
+    if (!v.tile_rows.reserve(sizeof(int32_t) * kOrderMax) || !v.row_cost.reserve(sizeof(uint32_t) * kOrderMax))
+        return RT_ENOMEM;
+    if (hipMemset(v.tile_rows.get(), 0, sizeof(int32_t) * kOrderMax) != hipSuccess ||
+        hipEventCreateWithFlags(&v.run_ev, hipEventDisableTiming) != hipSuccess ||
+        hipHostMalloc(&v.h_run_n, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+        return RT_EHIP;
+    return RT_OK;
 }
 
-// ... grown to hold `tiles` tiles (the caller has drained the device: renders may read the old ones).  False (and no
-// buffers) when the device is out of memory: the view then keeps the identity order.
+void view_release(rt_ctx* c) {
+    rt_ctx::View& v = c->view;
+    view_release_tiles(v);
+    release_all(v.tile_rows, v.row_cost, v.lmask);
+    if (v.run_ev) (void)hipEventDestroy(v.run_ev);
+    if (v.h_run_n) (void)hipHostFree(v.h_run_n);
+}
+
+// The per-tile buffers grown to hold `tiles` tiles (the caller has drained the device: renders may read the old ones).
+// False (and no buffers) when the device is out of memory: the view then keeps the identity order.
 static bool rt_grow_view_bufs(rt_ctx* c, size_t tiles) {
     rt_ctx::View& v = c->view;
-    if (tiles <= v.cap) return true;
-    rt_free_view_bufs(c);
+    if (tiles <= v.tiles_cap) return true;
+    view_release_tiles(v);
     const size_t slots = cone_slots(tiles);
-    bool ok = hipMalloc(&v.d_disp, slots * sizeof(DispRec)) == hipSuccess &&
-              hipMalloc(&v.d_tile_cost, tiles * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&v.d_cone_tile, 2 * tiles * sizeof(uint64_t)) == hipSuccess &&   // masks, then sky verdicts
-              hipMalloc(&v.d_tile_class, tiles) == hipSuccess &&
-              hipMalloc(&v.d_tile_flat, tiles) == hipSuccess &&
-              hipMalloc(&v.d_sort_keys, tiles * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&v.d_sort_in, tiles * sizeof(int32_t)) == hipSuccess &&
-              hipMalloc(&v.d_sort_out, tiles * sizeof(int32_t)) == hipSuccess;
-    if (ok) {
-        size_t tmp = 0;
-        ok = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, v.d_tile_cost, v.d_sort_keys, v.d_sort_in,
-                                                          v.d_sort_out, (int)tiles) == hipSuccess &&
-             hipMalloc(&v.d_sort_tmp, tmp) == hipSuccess;
-        v.sort_tmp_bytes = tmp;
-    }
+    size_t tmp = 0;
+    const bool ok = v.disp.reserve(slots * sizeof(DispRec)) && v.tile_cost.reserve(tiles * sizeof(uint32_t)) &&
+                    v.cone_tile.reserve(2 * tiles * sizeof(uint64_t)) &&   // masks, then sky verdicts
+                    v.tile_class.reserve(tiles) && v.tile_flat.reserve(tiles) &&
+                    v.sort_keys.reserve(tiles * sizeof(uint32_t)) && v.sort_in.reserve(tiles * sizeof(int32_t)) &&
+                    v.sort_out.reserve(tiles * sizeof(int32_t)) &&
+                    hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, v.tile_cost.get(), v.sort_keys.get(),
+                                                                 v.sort_in.get(), v.sort_out.get(),
+                                                                 (int)tiles) == hipSuccess &&
+                    v.sort_tmp.reserve(tmp);
     if (!ok) {
         (void)hipGetLastError();
-        rt_free_view_bufs(c);
+        view_release_tiles(v);
         return false;
     }
     // the run table's buffers (all or none: without them every render reads the plain table)
     if (c->knobs.sky_run_max != 1) {
-        size_t tmp = 0;
-        const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.d_run_code, RunHead{});
-        const bool run_ok = hipMalloc(&v.d_disp_run, slots * sizeof(DispRec)) == hipSuccess &&
-                            hipMalloc(&v.d_run_code, tiles * sizeof(uint32_t)) == hipSuccess &&
-                            hipMalloc(&v.d_run_num, tiles * sizeof(uint32_t)) == hipSuccess &&
-                            hipcub::DeviceScan::InclusiveSum(nullptr, tmp, heads, v.d_run_num, (int)tiles) == hipSuccess &&
-                            hipMalloc(&v.d_run_tmp, std::max(tmp, (size_t)16)) == hipSuccess;
-        if (run_ok) {
-            v.run_tmp_bytes = tmp;
-        } else {
+        tmp = 0;
+        const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.run_code.get(), RunHead{});
+        const bool run_ok = v.disp_run.reserve(slots * sizeof(DispRec)) && v.run_code.reserve(tiles * sizeof(uint32_t)) &&
+                            v.run_num.reserve(tiles * sizeof(uint32_t)) &&
+                            hipcub::DeviceScan::InclusiveSum(nullptr, tmp, heads, v.run_num.get(), (int)tiles) == hipSuccess &&
+                            v.run_tmp.reserve(std::max(tmp, (size_t)16));
+        if (!run_ok) {
             (void)hipGetLastError();
-            view_free_run_bufs(v);
+            release_all(v.disp_run, v.run_code, v.run_num, v.run_tmp);
         }
     }
-    v.cap = tiles;
+    v.tiles_cap = tiles;
     return true;
 }
 
@@ -522,7 +513,7 @@ static int render_plan_view(rt_ctx* c, RenderJob& J) {
     if (J.lm_stride > kLevelMaskSlotsMax) J.lm_stride = 0;
     J.key = rt_ctx::ViewKey{};
     // (dispatch records pack the tile as ty << 16 | tx)
-    if (!J.capturing && c->knobs.order_mode == 0 && J.tiles_y <= v.n_tile_rows && J.tiles_x < 65536 && J.tiles_y < 65536) {
+    if (!J.capturing && c->knobs.order_mode == 0 && J.tiles_y <= kOrderMax && J.tiles_x < 65536 && J.tiles_y < 65536) {
         // Key of the frame's work: camera, size, outputs, row plan, depth and scene generation.
         unsigned char* kp = J.key.data();               // fixed size: no host allocation per render
         memcpy(kp, J.cam, sizeof(rt_camera)); kp += sizeof(rt_camera);
@@ -538,51 +529,51 @@ static int render_plan_view(rt_ctx* c, RenderJob& J) {
         kp += sizeof(rt_rows);
         memcpy(kp, &c->scene.gen, sizeof(uint64_t));
         constexpr size_t kCam = sizeof(rt_camera);
-        const bool same_shape = v.order_valid &&
-                                memcmp(J.key.data() + kCam, v.order_key.data() + kCam, J.key.size() - kCam) == 0;
-        if (v.order_valid && J.key == v.order_key) {
-            P.disp = v.d_disp;
+        const bool same_shape = v.cal && memcmp(J.key.data() + kCam, v.cal->key.data() + kCam, J.key.size() - kCam) == 0;
+        if (v.cal && J.key == v.cal->key) {
+            rt_ctx::View::Calibrated& k = *v.cal;
+            using Runs = rt_ctx::View::Runs;
+            P.disp = v.disp.get();
             // (the cached masks hold one mask per one-wave 8 x 8 tile: the 256-thread A/B instances never read them)
-            P.cone_use = v.cone_valid && !big ? 1 : 0;
+            P.cone_use = k.cones && !big ? 1 : 0;
             // the run-compacted table of this view, once its position count has arrived (a wait that has, as a rule,
             // long passed: the copy was queued behind the calibration's table kernels)
-            if (v.run_pending) {
-                v.run_pending = false;
+            if (k.runs == Runs::pending) {
+                k.runs = Runs::none;
                 if (hipEventSynchronize(v.run_ev) == hipSuccess) {
-                    v.run_n = *v.h_run_n;
-                    v.run_valid = v.run_n > 0 && v.run_n < J.tiles;   // (no sky tile: the plain table)
-                    if (v.run_valid) run_grid(v.run_n, &v.run_w, &v.run_rows);
+                    k.run_n = *v.h_run_n;
+                    if (k.run_n > 0 && k.run_n < J.tiles) {       // (no sky tile: the plain table)
+                        k.runs = Runs::ready;
+                        run_grid(k.run_n, &k.run_w, &k.run_rows);
+                    }
                 } else {
                     (void)hipGetLastError();
                 }
             }
-            J.runs = v.run_valid && P.cone_use && P.sky;
-            if (J.runs) P.disp = v.d_disp_run;
-            v.last_positions = J.runs ? (int)v.run_n : (int)J.tiles;
-            v.last_tiles = (int)J.tiles;
-            v.last_run_max = J.runs ? v.run_built_max : 1;
-            if (v.lmask_valid && J.lm_stride > 0 && v.lmask_stride == J.lm_stride) {   // this view's level masks
-                P.lmask_in = v.d_lmask;
+            J.runs = k.runs == Runs::ready && P.cone_use && P.sky;
+            if (J.runs) P.disp = v.disp_run.get();
+            v.last = {J.runs ? (int)k.run_n : (int)J.tiles, (int)J.tiles, J.runs ? k.run_built_max : 1};
+            if (J.lm_stride > 0 && k.lmask_stride == J.lm_stride) {   // this view's level masks
+                P.lmask_in = v.lmask.get();
                 P.lmask_stride = J.lm_stride;
             }
         } else if (same_shape && c->knobs.moving_order) {
-            P.disp = v.d_disp;                         // another camera: the last calibrated order, its own masks
-            if (c->knobs.recalibrate > 0 && ++v.stale >= c->knobs.recalibrate) {   // ... re-timed every recalibrate-th render
+            P.disp = v.disp.get();                     // another camera: the last calibrated order, its own masks
+            if (c->knobs.recalibrate > 0 && ++v.cal->stale >= c->knobs.recalibrate) {   // ... re-timed every recalibrate-th render
                 J.calibrate = true;
-                view_invalidate(v);
+                v.cal.reset();                          // (the render still dispatches by the old table, P.disp)
             }
-        } else if (v.seen_valid && J.key == v.seen_key) {   // (by default a moving camera's views come here: the
-                                                              // first render of a view in identity order, its second
-                                                              // the calibration — a camera that stops is calibrated)
+        } else if (v.seen && J.key == *v.seen) {        // (by default a moving camera's views come here: the
+                                                        // first render of a view in identity order, its second
+                                                        // the calibration — a camera that stops is calibrated)
             J.calibrate = true;                         // calibration render (identity order)
-            view_invalidate(v);                         // rt_disp_kernel rewrites d_disp below, and d_disp_run
+            v.cal.reset();                              // rt_disp_kernel rewrites disp below, and disp_run
             // the calibration records one mask per tile from lane 0 of its wave: one-wave workgroups only
             J.cone_calib = c->knobs.cone_cache && c->scene.n_padded >= kPrimaryConeMin && !c->scene.tree &&
                            !c->scene.transparent && !big && RT_WG_FAST == 64;
             J.lm_calib = J.cone_calib && J.lm_stride > 0;
         } else {
-            v.seen_key = J.key;                        // first render of this view: identity order
-            v.seen_valid = true;
+            v.seen = J.key;                            // first render of this view: identity order
         }
     }
     J.prepare = J.capturing || c->eye.ever_captured || !c->eye.valid || memcmp(c->eye.pos, J.cam->eye, sizeof(c->eye.pos)) != 0;
@@ -598,8 +589,8 @@ static int render_order_streams(rt_ctx* c, const RenderJob& J) {
     if (J.prepare || J.calibrate) {
         // write-after-read: renders queued on other streams may still read what this render rewrites (or frees)
         if ((c->sync.readers && (c->sync.readers_multi || c->sync.reader_st != J.st)) ||
-            (J.calibrate && J.tiles > c->view.cap) ||
-            (J.lm_calib && J.tiles * (size_t)J.lm_stride > c->view.lmask_cap))
+            (J.calibrate && J.tiles > c->view.tiles_cap) ||
+            (J.lm_calib && J.tiles * (size_t)J.lm_stride * sizeof(uint64_t) > c->view.lmask.bytes))
             RT_HIP(hipDeviceSynchronize());
         c->sync.readers = c->sync.readers_multi = false;      // same-stream renders are ordered before the rewrite
     }
@@ -613,40 +604,25 @@ static int render_order_streams(rt_ctx* c, const RenderJob& J) {
 }
 
 // Step 4 (calibration renders): the buffers the render writes every tile's wave time and, a static view's, its cone
-// and level masks to.  They grow here: step 3 drained the device.
+// and level masks to.  They grow here: step 3 drained the device.  (Step 2 dropped the calibrated view: nothing describes
+// what the buffers hold until step 7.)
 static void render_grow_calibration(rt_ctx* c, RenderJob& J) {
     rt_ctx::View& v = c->view;
     RenderParams& P = J.P;
-    // (the masks' flags fall here, not in step 2's view_invalidate: step 3 may fail in between, and nothing reads them
-    // while order_valid is false)
-    v.cone_valid = false;
-    v.lmask_valid = false;
     if (!rt_grow_view_bufs(c, J.tiles)) {           // out of memory: identity order, masks in the kernel
         J.calibrate = J.cone_calib = J.lm_calib = false;
         P.disp = nullptr;
         P.cone_use = 0;
     } else {
-        P.tile_cost = v.d_tile_cost;
-        if (J.cone_calib) P.cone_out = v.d_cone_tile;
+        P.tile_cost = v.tile_cost.get();
+        if (J.cone_calib) P.cone_out = v.cone_tile.get();
     }
-    if (J.lm_calib && J.tiles * (size_t)J.lm_stride > v.lmask_cap) {
-        if (v.d_lmask) (void)hipFree(v.d_lmask);
-        v.d_lmask = nullptr;
-        v.lmask_cap = 0;
-        if (hipMalloc(&v.d_lmask, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t)) == hipSuccess)
-            v.lmask_cap = J.tiles * (size_t)J.lm_stride;
-        else
-            (void)hipGetLastError();                // out of memory: the masks stay in the kernel
+    // (out of memory: the masks stay in the kernel)
+    if (J.lm_calib && !v.lmask.reserve(J.tiles * (size_t)J.lm_stride * sizeof(uint64_t))) J.lm_calib = false;
+    if (J.lm_calib && J.cull_kernel) {              // (fast scenes: the level-mask launch of step 6 writes them)
+        P.lmask_out = v.lmask.get();
+        P.lmask_stride = J.lm_stride;
     }
-    if (J.lm_calib && v.d_lmask) {
-        if (J.cull_kernel) {                        // (fast scenes: the level-mask launch of step 6 writes them)
-            P.lmask_out = v.d_lmask;
-            P.lmask_stride = J.lm_stride;
-        }
-    } else {
-        J.lm_calib = false;
-    }
-    v.class_tiles_n = v.flat_tiles_n = 0;           // (the classes fall with the masks they are made from)
 }
 
 // Step 5: the primary-ray sphere data for this eye (stream-ordered; only when the eye changes, or always once graphs
@@ -671,9 +647,10 @@ static int render_launch(rt_ctx* c, const RenderJob& J) {
     L.disp_w = J.tiles_x;
     L.disp_n = J.tiles_y * J.tiles_x;
     if (J.runs) {                                   // one position per tracing tile and per run of sky tiles
-        L.grid = dim3((unsigned)c->view.run_w, (unsigned)c->view.run_rows, 1);
-        L.disp_w = c->view.run_w;
-        L.disp_n = (int32_t)c->view.run_n;
+        const rt_ctx::View::Calibrated& k = *c->view.cal;
+        L.grid = dim3((unsigned)k.run_w, (unsigned)k.run_rows, 1);
+        L.disp_w = k.run_w;
+        L.disp_n = (int32_t)k.run_n;
     }
     L.lds = (size_t)J.route.lds;
     L.stream = J.st;
@@ -687,7 +664,7 @@ static int render_launch(rt_ctx* c, const RenderJob& J) {
     // stream ahead of the launch that writes them (this one, or the level-mask launch below), so that an unreached slot
     // reads "keeps no sphere" — no render consumes such a slot, and the tile classes (rt_class_kernel) read them all.
     if (J.lm_calib &&
-        hipMemsetAsync(c->view.d_lmask, 0, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t), J.st) != hipSuccess)
+        hipMemsetAsync(c->view.lmask.get(), 0, J.tiles * (size_t)J.lm_stride * sizeof(uint64_t), J.st) != hipSuccess)
         return rt_fail(RT_EHIP, "level masks: hipMemsetAsync failed");
     hipError_t e = with_depth(J.depth, [&](auto B) { return launch_render<decltype(B)::value>(L); });
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_render_kernel launch: ") + hipGetErrorString(e));
@@ -698,7 +675,7 @@ static int render_launch(rt_ctx* c, const RenderJob& J) {
         RenderLaunch M = L;
         M.key = mask.key;
         M.lds = (size_t)mask.lds;
-        M.P.lmask_out = c->view.d_lmask;
+        M.P.lmask_out = c->view.lmask.get();
         M.P.lmask_in = nullptr;
         M.P.lmask_stride = J.lm_stride;
         M.P.disp = nullptr;
@@ -722,72 +699,70 @@ static int render_build_dispatch(rt_ctx* c, const RenderJob& J) {
     const hipStream_t st = J.st;
     hipError_t e;
     const dim3 tg((unsigned)((J.tiles + 255) / 256));
-    const uint64_t* cones = J.cone_calib ? v.d_cone_tile : nullptr;
+    rt_ctx::View::Calibrated k;                           // the view these kernels describe: the context's at the end
+    k.key = J.key;
+    k.tiles = J.tiles;
+    k.cones = J.cone_calib;
+    k.lmask_stride = J.lm_calib ? J.lm_stride : 0;
+    const uint64_t* cones = J.cone_calib ? v.cone_tile.get() : nullptr;
     // The tile classes of a fast-kernel view with level masks, after the level-mask launch and ahead of the table
     // kernels; the records carry them unless RT_TILE_CLASSES=0.  Culling-kernel views and views without masks have none.
     const uint8_t *cls = nullptr, *flat = nullptr;
-    v.class_tiles_n = v.flat_tiles_n = 0;
     if (J.cone_calib && J.lm_calib && !J.cull_kernel && c->scene.n_padded <= 64) {
-        hipLaunchKernelGGL(rt_class_kernel, tg, dim3(256), 0, st, v.d_cone_tile, v.d_lmask, J.lm_stride,
-                           c->scene.n_padded, tiles, v.d_tile_class);
-        v.class_tiles_n = J.tiles;
+        hipLaunchKernelGGL(rt_class_kernel, tg, dim3(256), 0, st, v.cone_tile.get(), v.lmask.get(), J.lm_stride,
+                           c->scene.n_padded, tiles, v.tile_class.get());
+        k.classes = true;
         // (only into the records of a view whose kernel instance reads the bit: rt_render.hpp class_instance)
         if (class_instance(J.mode == kModePacked, J.mode == kModeSS, J.depth)) {
-            if (c->knobs.tile_classes) cls = v.d_tile_class;
+            if (c->knobs.tile_classes) cls = v.tile_class.get();
             // ... and which of the sphere-free tiles are flat, for the same instances: the calibration render's rays,
             // re-formed from its parameters (rt_flat_kernel).  In the records unless RT_FLAT_TILES=0 (or no class is).
             hipLaunchKernelGGL(rt_flat_kernel, dim3((unsigned)tiles), dim3(64), 0, st, c->scene.d_scene, J.P,
-                               v.d_tile_class, tiles, v.d_tile_flat);
-            v.flat_tiles_n = J.tiles;
-            if (cls && c->knobs.flat_tiles) flat = v.d_tile_flat;
+                               v.tile_class.get(), tiles, v.tile_flat.get());
+            k.flat = true;
+            if (cls && c->knobs.flat_tiles) flat = v.tile_flat.get();
         }
     }
     if (c->knobs.order_policy == 1) {                     // tiles longest first
-        hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, v.d_sort_in, (int)tiles);
-        size_t tmp = v.sort_tmp_bytes;
-        e = hipcub::DeviceRadixSort::SortPairsDescending(v.d_sort_tmp, tmp, v.d_tile_cost, v.d_sort_keys,
-                                                         v.d_sort_in, v.d_sort_out, (int)tiles, 0, 32, st);
+        hipLaunchKernelGGL(rt_iota_kernel, tg, dim3(256), 0, st, v.sort_in.get(), (int)tiles);
+        size_t tmp = v.sort_tmp.bytes;
+        e = hipcub::DeviceRadixSort::SortPairsDescending(v.sort_tmp.get(), tmp, v.tile_cost.get(), v.sort_keys.get(),
+                                                         v.sort_in.get(), v.sort_out.get(), (int)tiles, 0, 32, st);
         if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("tile order sort: ") + hipGetErrorString(e));
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.d_sort_out, cones, cls, flat, tiles_x, tiles_y,
-                           v.d_disp);
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, nullptr, v.sort_out.get(), cones, cls, flat, tiles_x,
+                           tiles_y, v.disp.get());
     } else {                                        // tile rows longest first
-        hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, v.d_tile_cost, tiles_x,
-                           v.d_row_cost);
-        hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, v.d_row_cost, tiles_y, v.d_tile_rows);
-        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, nullptr, cones, cls, flat, tiles_x, tiles_y,
-                           v.d_disp);
+        hipLaunchKernelGGL(rt_rowsum_kernel, dim3((unsigned)tiles_y), dim3(256), 0, st, v.tile_cost.get(), tiles_x,
+                           v.row_cost.get());
+        hipLaunchKernelGGL(rt_order_kernel, dim3(1), dim3(1024), 0, st, v.row_cost.get(), tiles_y, v.tile_rows.get());
+        hipLaunchKernelGGL(rt_disp_kernel, tg, dim3(256), 0, st, v.tile_rows.get(), nullptr, cones, cls, flat, tiles_x,
+                           tiles_y, v.disp.get());
         // ... and beside it the run-compacted table, for the cached renders of a view with sky verdicts whose
         // instance stores runs (render_body: one-wave opaque tiles, which cone_calib implies; not supersampled).  The
         // plan runs along dispatch columns and the kernel stores image columns tx .. tx + r - 1: the same thing because
         // dispatch column bx traces image column bx in every row.
         const int run_max = c->knobs.sky_run_max == 0 ? 65535 : c->knobs.sky_run_max;
-        if (J.cone_calib && c->knobs.sky_tiles && run_max > 1 && v.d_disp_run && J.mode != kModeSS) {
-            const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.d_run_code, RunHead{});
-            size_t tmp = v.run_tmp_bytes;
-            hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st, v.d_tile_rows,
-                               v.d_cone_tile + J.tiles, tiles_x, run_max, v.d_run_code);
-            if (hipcub::DeviceScan::InclusiveSum(v.d_run_tmp, tmp, heads, v.d_run_num, tiles, st) == hipSuccess) {
-                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.d_tile_rows, v.d_cone_tile, cls, flat,
-                                   v.d_run_code, v.d_run_num, tiles_x, tiles_y, v.d_disp_run);
-                if (hipMemcpyAsync(v.h_run_n, v.d_run_num + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
+        if (J.cone_calib && c->knobs.sky_tiles && run_max > 1 && v.disp_run.get() && J.mode != kModeSS) {
+            const hipcub::TransformInputIterator<uint32_t, RunHead, const uint32_t*> heads(v.run_code.get(), RunHead{});
+            size_t tmp = v.run_tmp.bytes;
+            hipLaunchKernelGGL(rt_run_plan_kernel, dim3((unsigned)tiles_y), dim3(256), (size_t)tiles_x, st,
+                               v.tile_rows.get(), v.cone_tile.get() + J.tiles, tiles_x, run_max, v.run_code.get());
+            if (hipcub::DeviceScan::InclusiveSum(v.run_tmp.get(), tmp, heads, v.run_num.get(), tiles, st) == hipSuccess) {
+                hipLaunchKernelGGL(rt_run_disp_kernel, tg, dim3(256), 0, st, v.tile_rows.get(), v.cone_tile.get(), cls,
+                                   flat, v.run_code.get(), v.run_num.get(), tiles_x, tiles_y, v.disp_run.get());
+                if (hipMemcpyAsync(v.h_run_n, v.run_num.get() + (J.tiles - 1), sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    st) == hipSuccess &&
                     hipEventRecord(v.run_ev, st) == hipSuccess) {
-                    v.run_pending = true;
-                    v.run_built_max = run_max;
+                    k.runs = rt_ctx::View::Runs::pending;
+                    k.run_built_max = run_max;
                 }
             }
-            if (!v.run_pending) (void)hipGetLastError();   // (the view keeps the plain table)
+            if (k.runs != rt_ctx::View::Runs::pending) (void)hipGetLastError();   // (the view keeps the plain table)
         }
     }
     e = hipGetLastError();
     if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("dispatch table: ") + hipGetErrorString(e));
-    v.order_key = J.key;                           // only once the order kernel is queued
-    v.order_valid = true;
-    v.cone_valid = J.cone_calib;
-    v.sky_tiles_n = J.cone_calib ? J.tiles : 0;
-    v.lmask_valid = J.lm_calib;
-    v.lmask_stride = J.lm_calib ? J.lm_stride : 0;
-    v.stale = 0;
+    v.cal = k;                                     // only once the order kernel is queued
     return RT_OK;
 }
 

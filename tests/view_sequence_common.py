@@ -313,8 +313,9 @@ def _shape(key):
 
 class Model:
     """The documented rule of the view cache, restated: for each step the branch render_plan_view takes (first,
-    calibration, cached, other camera, captured), whether the eye's records are prepared, and whether the calibration
-    records cone masks and level masks.  `forget`: key fields this model leaves out of the key — the true model forgets
+    calibration, cached, other camera, captured), whether the eye's records are prepared, whether the calibration
+    records cone masks and level masks, and the calibrated view the diagnostics describe after the step (view()).
+    `forget`: key fields this model leaves out of the key — the true model forgets
     none; one that forgets a field calls a render cached where the library must not."""
 
     def __init__(self, forget=(), moving_order=False, recalibrate=8, cone_cache=True, level_masks=True):
@@ -325,13 +326,27 @@ class Model:
         self.order_key = self.seen_key = None        # None: not valid
         self.order_plan = None                       # the calibrated view (a forgetful model's stale view)
         self.cone_valid = False
+        self.classes = self.flat = False             # ... has tile classes (rt_class_kernel) / flat verdicts (rt_flat_kernel)
         self.stale = 0
         self.eye = None                              # None: not valid
         self.ever_captured = False
 
+    def view(self):
+        """The calibrated view as rt_diag_sky_count, rt_diag_tile_classes and rt_diag_flat_tiles describe it: the last
+        completed calibration, until the next calibration starts or a tile_order step -> dict(plan, cone, classes,
+        flat), or None."""
+        if self.order_key is None:
+            return None
+        return {"plan": self.order_plan, "cone": self.cone_valid, "classes": self.classes, "flat": self.flat}
+
     def step(self, step):
-        """-> dict(branch, prepare, calibrate, cone, lmask, plan); branch None for a step without a render_dev_impl
-        call."""
+        """-> dict(branch, prepare, calibrate, cone, lmask, plan, view); branch None for a step without a
+        render_dev_impl call; view: view() after the step."""
+        out = self._step(step)
+        out["view"] = self.view()
+        return out
+
+    def _step(self, step):
         out = {"branch": None, "prepare": False, "calibrate": False, "cone": False, "lmask": False, "plan": None}
         op = step["op"]
         if op == "set_scene":
@@ -367,7 +382,12 @@ class Model:
                 lm_stride = 0
             cone = self.cone_cache and n_padded >= 8 and opaque
             out.update(branch="calibration", calibrate=True, cone=cone, lmask=cone and lm_stride > 0)
-            self._calibrated(key, p, cone)
+            # render_build_dispatch: the classes of a fast-kernel view (< 16 padded spheres: no culling kernel) with
+            # level masks; the flat verdicts where the kernel instance reads the bit (rt_render.hpp class_instance:
+            # not supersampled, and not packed from depth 2)
+            classes = out["lmask"] and n_padded < 16
+            packed = bool(p["outs"][1]) and p["format"][1] != "rgba8"
+            self._calibrated(key, p, cone, classes, classes and p["samples"] == 0 and not (packed and p["depth"] >= 2))
         else:                                        # identity order; by default a moving camera's views come here too
             out["branch"] = "other" if same_shape else "first"
             self.seen_key = key
@@ -376,8 +396,9 @@ class Model:
         self.eye = eye
         return out
 
-    def _calibrated(self, key, p, cone):
+    def _calibrated(self, key, p, cone, classes=False, flat=False):
         self.order_key, self.order_plan, self.cone_valid, self.stale = key, p, cone, 0
+        self.classes, self.flat = classes, flat
 
 
 def sky_verdict(p):
