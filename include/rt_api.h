@@ -425,7 +425,7 @@ int rt_render_soft(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, int
  *     call writes no pixel.
  * 10. Not offered: moving meshes, board, lights or camera; curved or accelerated paths; jittered times; a pairing of
  *     time with (a, b) other than rule 2.  A streak is therefore a sum of at most S S copies, the same in every pixel
- *     (rt_render_jitter_dev jitters the times).
+ *     (rt_render_jitter_dev jitters the times; rt_render_shutter_dev moves the camera).
  *     rt_render_multi, the packed and asynchronous host paths and the drop-in draw() stay frozen in time.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, one sphere moving by |d| = 40, F = 1, A = R = 0, RGBA32F + RGBA8,
  * tools/bench_motion.py): S = 2 139 us and S = 4 565 us per frame, 1.05 x and 1.06 x rt_render_soft_dev at the same S
@@ -555,7 +555,74 @@ int rt_render_jitter(rt_ctx* ctx, const rt_scene* scene, const double* displacem
                      int height, int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
                      double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
-/* ---- packed pixel formats (ABI 5) --------------------------------------------------------------- */
+/* ---- camera motion blur: a moving eye and look-at point (ABI 10: new symbols only) ------------------------------ */
+/* rt_render_jitter_dev with the camera itself moving during the exposure: a pan, a dolly, a crane or an orbit streaks
+ * the whole frame the way a moving sphere streaks its own image.  Every sample has the camera of its own shutter time,
+ * eye, look-at point and basis.  Deterministic, and defined entirely by rt_set_scene and rt_trace_rays_dev on scenes and
+ * rays this text spells out.  For a full width x height frame, S, J, `seed`, A, R, F and the displacements as for
+ * rt_render_jitter_dev, and `motion` the half-extents of the camera's move during the exposure, in world units:
+ *  1. Everything of rt_render_jitter_dev holds unchanged: the hash, the levels k_0 .. k_6, the fine camera's pitch_f and
+ *     bottom_f, the lens quotients t, the light quotients g, the time sigma = F * u with k_6, the sphere centres, the
+ *     reduction tree and the outputs.  J = 1 gives the regular grid of rt_render_motion_dev.
+ *  2. Camera of a sample.  A sample at time sigma has the camera
+ *         eye_s[c] = eye[c] + (sigma * motion.eye[c]),   look_s[c] = look_at[c] + (sigma * motion.look_at[c])
+ *     per component: one multiplication, then one addition; up, pitch and bottom are `cam`'s.  Its basis is the camera
+ *     comment's formula on those values in the reference's operation order (MySdlApplication.cpp:1270-1277,
+ *     Point::normalize :174-175): LD = look_s - eye_s, right_s = normalize(LD x up), up'_s = normalize(right_s x LD);
+ *     normalize(v): l = sqrt(v.x v.x + v.y v.y + v.z v.z), summed left to right, then three IEEE divisions by l;
+ *     a x b = (a.y b.z - b.y a.z, a.z b.x - a.x b.z, a.x b.y - a.y b.x).  rt_camera_at returns exactly this camera: eye
+ *     and look_at moved, everything else copied (`out` may be `cam`; motion NULL: no move); RT_EINVAL for a null
+ *     pointer, a non-finite sigma or a non-finite displacement.
+ *  3. Ray.  It ends at (look_s + (pitch_f * (double)(fi + bottom_fx)) * right_s) + (pitch_f * (double)(fj + bottom_fy)) *
+ *     up'_s, (fi, fj) = (J I + k_0, J Jr + k_1), and starts at (eye_s + (A * t_x) * right_s) + (A * t_y) * up'_s: rules 3
+ *     and 4 of rt_render_jitter_dev with the sample's own camera.
+ *  4. Value.  The colour and the counters of a sample are what rt_trace_rays_dev gives that ray on the scene of
+ *     rt_render_jitter_dev rules 5 and 6.
+ *  5. Pins that follow, with NO shortcut in the implementation (one kernel runs for every argument): motion NULL or all
+ *     zero writes exactly what rt_render_jitter_dev writes, images and counters — with J = 1 rt_render_motion_dev's
+ *     output, and down the chain rt_render_soft_dev's, rt_render_dof_dev's, rt_render_ss_dev's and rt_render_dev's; so
+ *     does F = 0 with any motion.  The pins assume that no eye or look_at component is -0.0.  With J = 1, A = R = 0
+ *     and frozen spheres, sample (a, b) of pixel (i, j) is pixel (S i + a, S j + b) of the S width x S height frame
+ *     rt_render_dev renders with rt_camera_supersample(rt_camera_at(cam, motion, sigma_n), S), n = a + S b.
+ *  6. rt_render_shutter_dev: full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host
+ *     synchronisation, so the call may be captured in a hipGraph.  No per-view state; the scene and motion records are
+ *     read, never written, and the cone masks, the level masks and the tile order stay intact.  The camera motion is an
+ *     argument of the call, not state of the context.
+ *  7. RT_EINVAL (rt_last_error names the argument) for every check of rt_render_jitter_dev, a non-finite displacement in
+ *     `motion`, and a camera at sigma in {-F, 0, +F} whose right or up' is not finite (a view direction parallel to up
+ *     at an end or the middle of the exposure).  A rejected call writes no pixel.  A basis that degenerates strictly
+ *     between those times is the caller's responsibility: the sample's value is still rule 4's.
+ *  8. Not offered: a moving up, curved or accelerated paths, moving lights, board and meshes, camera motion in
+ *     rt_render_lens_adaptive_dev, a shutter per effect.  rt_render_multi, the packed and asynchronous host paths and the
+ *     drop-in draw() keep a frozen camera.
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, one sphere moving by |d| = 40, F = 1, A = 0, RGBA32F + RGBA8,
+ * tools/bench_shutter.py, profiles/shutter/bench_shutter.json; against rt_render_jitter_dev with the same arguments in
+ * the same run): a zero motion costs 1.20 x at every size (S = 2: 179.0 us at J = 1 and 181.3 us at J = 16 against 148.2 us
+ * and 150.5 us; S = 4: 728.5 us and 731.2 us against 604.2 us and 607.2 us), a crane of |eye move| = 40 1.32 x - 1.35 x
+ * (S = 2: 195.4 us and 203.5 us; S = 4: 811.9 us and 818.1 us).  The 20 % are the issue slots of the 141 FP64 instructions
+ * of the per-lane basis (two IEEE square roots, six IEEE divisions) on a kernel that is FP64-issue bound and executes
+ * about 700 per sample at this depth; the crane's further 9 - 12 % come with fewer rays, not more (likely the wave-level
+ * sphere culling, which widens with the spread of a wave's ray origins; not measured).  profiles/shutter/README.md has
+ * the counts.  Other scenes, depths, apertures and motions: not measured. */
+typedef struct rt_camera_motion {   /* half-extents of the camera's move during the exposure, world units */
+    double eye[3];
+    double look_at[3];
+} rt_camera_motion;
+/* Host only: the camera of rule 2 at time sigma. */
+int rt_camera_at(const rt_camera* cam, const rt_camera_motion* motion, double sigma, rt_camera* out);
+/* Device pointers, each output nullable, width * height pixels. */
+int rt_render_shutter_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width, int height,
+                          int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                          double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                          void* stream);
+/* Synchronous host-buffer convenience, as rt_render_jitter: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the frame.  *stats as rt_render_jitter. */
+int rt_render_shutter(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                      const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
+                      uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
+                      uint8_t* rgba8, double* rgb64f, rt_stats* stats);
+
+/* ---- packed pixel formats (ABI 5)--------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.
  * GRAY formats hold the R channel only and are accepted only for an ACHROMATIC scene (rt_scene_achromatic):
  * there R = G = B bit for bit, since every colour term of rayTraceRay (:1223-1226, :1241-1246) is a

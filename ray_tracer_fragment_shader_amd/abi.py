@@ -88,6 +88,11 @@ class rt_rows(Structure):
     _fields_ = [("band_height", c_int32), ("n_ranks", c_int32), ("rank", c_int32), ("frames", c_int32)]
 
 
+class rt_camera_motion(Structure):
+    """Half-extents of the camera's move during the exposure (rt_render_shutter_dev), world units."""
+    _fields_ = [("eye", D3), ("look_at", D3)]
+
+
 class rt_stats(Structure):
     _fields_ = [("primary_rays", c_uint64), ("reflect_rays", c_uint64), ("shadow_rays", c_uint64),
                 ("kernel_ms", c_double)]
@@ -208,6 +213,13 @@ SIGNATURES = {
     "rt_render_jitter": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), c_int, c_int, c_int, c_int, c_int,
                                  ctypes.c_uint32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                  _P(rt_stats)]),
+    "rt_camera_at": (c_int, [_P(rt_camera), _P(rt_camera_motion), c_double, _P(rt_camera)]),
+    "rt_render_shutter_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int, c_int, c_int, c_int,
+                                      ctypes.c_uint32, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
+    "rt_render_shutter": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion), c_int, c_int,
+                                  c_int, c_int, c_int, ctypes.c_uint32, c_double, c_double, c_double, c_void_p, c_void_p,
+                                  c_void_p, _P(rt_stats)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

@@ -47,6 +47,11 @@
 //                                                  the frame of the lens, soft-shadow and motion modes with every sample
 //                                                  at one of 16 hashed sub-positions of its stratum in each dimension
 //                                                  (rt_render_jitter; J in 1, 2, 4, 8, 16; the seed defaults to 1)
+//   rt_render --config c2 --samples 4 --shutter 1 --eye-move 0,40,0 [--look-move DX,DY,DZ] [--jitter 16 [--seed 7]]
+//             [--move 0:40,0,0 ...] [--aperture 8 [--focus 0.8]] [--light-size 40] --out c2_shutter.ppm
+//                                                  camera motion blur: the eye moves by +-(0, 40, 0) and the look-at
+//                                                  point by +-(DX, DY, DZ) (world units) during the exposure; every sample
+//                                                  sees from the camera of its own time (rt_render_shutter; J defaults to 1)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -89,6 +94,8 @@ struct Options {
     bool refine = false;                     // ... and --samples x --samples where they disagree by more than T
     int refine_t = 0;
     int jitter = 0;                          // --jitter J: rt_render_jitter with --seed (needs --samples)
+    bool camera_motion = false;              // --eye-move / --look-move DX,DY,DZ: rt_render_shutter (needs --shutter)
+    rt_camera_motion camera_move = {};
     std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -116,6 +123,18 @@ void move_arg(const std::string& v, Options* o) {
     }
     o->move_k.push_back(k);
     o->move_d.insert(o->move_d.end(), d, d + 3);
+}
+
+// --eye-move / --look-move DX,DY,DZ: three finite numbers, or a usage error.
+void camera_move_arg(const std::string& flag, const std::string& v, double out[3]) {
+    int used = 0;
+    double d[3];
+    if (std::sscanf(v.c_str(), "%lf,%lf,%lf%n", &d[0], &d[1], &d[2], &used) != 3 || used != (int)v.size() ||
+        !std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2])) {
+        std::fprintf(stderr, "rt_render: %s needs DX,DY,DZ (three numbers), got '%s'\n", flag.c_str(), v.c_str());
+        std::exit(2);
+    }
+    std::copy(d, d + 3, out);
 }
 
 [[noreturn]] void die(const std::string& what, int code) {
@@ -249,15 +268,24 @@ int main(int argc, char** argv) {
         else if (a == "--light-size") { o.soft = true; o.light_size = number_arg(a, next()); }
         else if (a == "--shutter") { o.motion = true; o.shutter = number_arg(a, next()); }
         else if (a == "--move") move_arg(next(), &o);
+        else if (a == "--eye-move") { o.camera_motion = true; camera_move_arg(a, next(), o.camera_move.eye); }
+        else if (a == "--look-move") { o.camera_motion = true; camera_move_arg(a, next(), o.camera_move.look_at); }
         else if (a == "--coarse") o.coarse = std::atoi(next().c_str());
         else if (a == "--refine") { o.refine = true; o.refine_t = std::atoi(next().c_str()); }
         else if (a == "--jitter") { o.jitter = std::atoi(next().c_str()); if (o.jitter == 0) o.jitter = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K]]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K]] "
+                                    "[--eye-move DX,DY,DZ] [--look-move DX,DY,DZ]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
+    }
+    if (o.camera_motion && (!o.motion || o.samples == 0 || o.adaptive || o.refine || o.coarse != 0 || o.faithful >= 0 ||
+                            o.gpus > 0)) {
+        std::fprintf(stderr, "rt_render: --eye-move and --look-move need --shutter and --samples, exclude --adaptive, "
+                             "--coarse and --refine and apply to plain frames (not --faithful or --gpus)\n");
+        return 2;
     }
     if (o.adaptive && (o.samples == 0 || o.faithful >= 0 || o.gpus > 0)) {
         std::fprintf(stderr, "rt_render: --adaptive needs --samples and applies to plain frames (not --faithful or "
@@ -457,6 +485,10 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
+        else if (o.camera_motion)
+            check(rt_render_shutter(ctx, &scene, displacement.data(), &cam, &o.camera_move, W, H, depth, o.samples,
+                                    o.jitter != 0 ? o.jitter : 1, (uint32_t)o.seed, o.aperture, o.light_size, o.shutter,
+                                    nullptr, rgba8.data(), nullptr, &st), "rt_render_shutter");
         else if (o.jitter != 0)
             check(rt_render_jitter(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth, o.samples,
                                    o.jitter, (uint32_t)o.seed, o.aperture, o.light_size, o.shutter, nullptr, rgba8.data(),
@@ -493,6 +525,13 @@ int main(int argc, char** argv) {
                     "%llu of %llu pixels refined from %d x %d to %d x %d samples\n", o.refine_t, o.shutter, o.light_size,
                     o.aperture, (unsigned long long)n_refined, (unsigned long long)W * H, o.coarse, o.coarse, o.samples,
                     o.samples);
+    else if (o.camera_motion)
+        std::printf("rt_render: camera motion, eye +-(%g, %g, %g), look-at +-(%g, %g, %g), shutter %g, J = %d, seed %u, %d "
+                    "moving spheres, light half-width %g, lens half-width %g: %d x %d samples per pixel, %llu primary "
+                    "rays\n", o.camera_move.eye[0], o.camera_move.eye[1], o.camera_move.eye[2], o.camera_move.look_at[0],
+                    o.camera_move.look_at[1], o.camera_move.look_at[2], o.shutter, o.jitter != 0 ? o.jitter : 1, o.seed,
+                    (int)o.move_k.size(), o.light_size, o.aperture, o.samples, o.samples,
+                    (unsigned long long)st.primary_rays);
     else if (o.jitter != 0)
         std::printf("rt_render: jittered, J = %d sub-positions per stratum and axis, seed %u, shutter %g, %d moving "
                     "spheres, light half-width %g, lens half-width %g: %d x %d samples per pixel, %llu primary rays\n",

@@ -314,6 +314,10 @@ int jitter_arg_checks(const char* who, int jitter);
 int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int jitter,
                       uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
                       double* rgb64f, uint32_t* raycount2, void* stream);
+// The device render of the shutter render, as `who` (rt_frames.hip's host entry point too).
+int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                       int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                       double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream);
 
 // rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after
 // the context's streams have drained).

@@ -77,6 +77,13 @@ __device__ __forceinline__ double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y
 __device__ __forceinline__ double len(d3 a) { return sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }  // :174
 __device__ __forceinline__ d3 divs(d3 a, double l) { return mk(a.x / l, a.y / l, a.z / l); }      // :175
 __device__ __forceinline__ d3 ld3(const double* p) { return mk(p[0], p[1], p[2]); }
+// The camera basis's two operations as rt_host.cpp's cross and normalize (rt_camera_basis) have them: the reference's
+// cross product (:1271-1277) and Point::normalize (:174-175) with the compiler's IEEE sqrt and its three IEEE
+// divisions — not unit(), whose operand ranges nothing proves for a camera formed per lane.
+__device__ __forceinline__ d3 cross(d3 a, d3 b) {
+    return mk(a.y * b.z - b.y * a.z, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+__device__ __forceinline__ d3 cam_normalize(d3 a) { return divs(a, len(a)); }
 
 // ------------------------------------------------------------------------------------------------
 // Exact fast paths for |v| and v / |v|.

@@ -371,6 +371,28 @@ extern "C" int rt_render_jitter(rt_ctx* c, const rt_scene* scene, const double* 
         [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }
 
+// rt_render for a frame with a moving camera: rt_render_jitter's steps with shutter_render_dev (as rt_render_shutter_dev).
+extern "C" int rt_render_shutter(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                                 const rt_camera_motion* motion, int W, int H, int depth, int samples, int jitter,
+                                 uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
+                                 uint8_t* rgba8, double* rgb64f, rt_stats* stats) {
+    const char* who = "rt_render_shutter";
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc || (rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const size_t npx = (size_t)W * H;
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, nullptr, 0,
+        [&](void* const* d) {
+            return shutter_render_dev("rt_render_shutter_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                                      aperture, light_size, shutter, (float*)d[0], (uint8_t*)d[1], (double*)d[2],
+                                      (uint32_t*)d[3], c->frames.rs);
+        },
+        [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
+}
+
 // rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
 // rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
 // back.

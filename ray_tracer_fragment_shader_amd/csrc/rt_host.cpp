@@ -225,6 +225,25 @@ extern "C" int rt_camera_focus(const rt_camera* cam, double ratio, rt_camera* ou
     return RT_OK;
 }
 
+// The camera of the shutter render (rt_api.h) at time sigma: eye and look_at moved by sigma times the motion's
+// half-extents, one multiplication and one addition per component; everything else copied.  motion = NULL: no move.
+extern "C" int rt_camera_at(const rt_camera* cam, const rt_camera_motion* motion, double sigma, rt_camera* out) {
+    if (!cam || !out) return rt_fail(RT_EINVAL, "rt_camera_at: null pointer");
+    if (!std::isfinite(sigma)) return rt_fail(RT_EINVAL, "rt_camera_at: sigma must be finite");
+    rt_camera c = *cam;                                                         // (out may alias cam)
+    if (motion) {
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(motion->eye[q]) || !std::isfinite(motion->look_at[q]))
+                return rt_fail(RT_EINVAL, "rt_camera_at: non-finite displacement (motion)");
+        for (int q = 0; q < 3; ++q) {
+            c.eye[q] = cam->eye[q] + (sigma * motion->eye[q]);
+            c.look_at[q] = cam->look_at[q] + (sigma * motion->look_at[q]);
+        }
+    }
+    *out = c;
+    return RT_OK;
+}
+
 // The seven levels of sample (I, Jr) of the jittered render's S width-wide sample frame, by the kernel's own functions
 // (rt_jitter.hpp).
 extern "C" int rt_jitter_sample(int width, int samples, int jitter, uint32_t seed, int I, int Jr, int32_t levels[7]) {

@@ -1,6 +1,6 @@
 // rt_sampled.hip — the device entry points of the sampled renders of rt_sampled.hpp: adaptive supersampling
-// (base render, rt_classify_kernel, the refine launch), the lens family's one launch, the jittered render's and the
-// adaptive lens render's three passes.
+// (base render, rt_classify_kernel, the refine launch), the lens family's one launch, the jittered render's, the
+// shutter render's and the adaptive lens render's three passes.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -243,15 +243,14 @@ int jitter_arg_checks(const char* who, int jitter) {
     return RT_OK;
 }
 
-// One launch of rt_jitter_kernel on `stream`: lens_render_dev's motion kind with the fine camera (pitch / (S J),
-// S J bottom, whose whole S J width x S J height frame must index in int32) and the seed beside it.  Nothing per view,
-// no field of the context written, no shortcut for jitter 1 or any argument of 0.
-int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int jitter,
-                      uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
-                      double* rgb64f, uint32_t* raycount2, void* stream) {
+// The jittered render's checks and its launch record: lens_render_dev's motion kind with the fine camera (pitch / (S J),
+// S J bottom, whose whole S J width x S J height frame must index in int32) and the seed beside it.
+static int jitter_launch(const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples,
+                         int jitter, uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
+                         uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream, SampledLaunch* out) {
     int s, rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter);
     if (rc || (rc = jitter_arg_checks(who, jitter))) return rc;
-    SampledLaunch L{};                                      // P: the sample grid's, the kernel's ray set-up
+    SampledLaunch& L = *out;                                // P: the sample grid's, the kernel's ray set-up
     rc = sample_grid_front(c, cam, W, H, depth, samples, &s, &L.P);
     if (rc) return rc;
     if (!c->scene.d_motion) return rt_fail(RT_EINVAL, std::string(who) + ": no scene set");
@@ -277,6 +276,18 @@ int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, i
     L.o8 = rgba8;
     L.o64 = rgb64f;
     L.orc2 = raycount2;
+    return RT_OK;
+}
+
+// One launch of rt_jitter_kernel on `stream`.  Nothing per view, no field of the context written, no shortcut for
+// jitter 1 or any argument of 0.
+int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, int H, int depth, int samples, int jitter,
+                      uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f, uint8_t* rgba8,
+                      double* rgb64f, uint32_t* raycount2, void* stream) {
+    SampledLaunch L{};
+    const int rc = jitter_launch(who, c, cam, W, H, depth, samples, jitter, seed, aperture, light_size, shutter, rgba32f,
+                                 rgba8, rgb64f, raycount2, stream, &L);
+    if (rc) return rc;
     if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     const hipError_t e = with_depth(depth, [&](auto B) { return launch_jitter<decltype(B)::value>(L); });
@@ -289,6 +300,55 @@ extern "C" int rt_render_jitter_dev(rt_ctx* c, const rt_camera* cam, int W, int 
                                     uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream) {
     return jitter_render_dev("rt_render_jitter_dev", c, cam, W, H, depth, samples, jitter, seed, aperture, light_size,
                              shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+// ---- the shutter render: a moving camera (include/rt_api.h) ----------------------------------------------------------
+// One launch of rt_shutter_kernel on `stream`: the jittered render's checks and launch record, then the camera motion's
+// own checks: finite half-extents, and a finite basis at the two ends and the middle of the exposure (a view direction
+// parallel to up there is rejected; in between it is the caller's).  The six half-extents and the camera's up travel in
+// the kernel arguments; motion = nullptr is the zero motion.  Nothing per view, no field of the context written, no
+// shortcut for a zero motion, shutter 0, jitter 1 or any argument of 0.
+int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                       int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                       double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                       void* stream) {
+    SampledLaunch L{};
+    const int rc = jitter_launch(who, c, cam, W, H, depth, samples, jitter, seed, aperture, light_size, shutter, rgba32f,
+                                 rgba8, rgb64f, raycount2, stream, &L);
+    if (rc) return rc;
+    const rt_camera_motion none{};
+    const rt_camera_motion& m = motion ? *motion : none;
+    for (int q = 0; q < 3; ++q)
+        if (!std::isfinite(m.eye[q]) || !std::isfinite(m.look_at[q]))
+            return rt_fail(RT_EINVAL, std::string(who) + ": non-finite displacement (motion)");
+    for (const double sigma : {-shutter, 0.0, shutter}) {
+        rt_camera at;
+        double right[3], upp[3];
+        if (rt_camera_at(cam, &m, sigma, &at)) return RT_EINVAL;
+        rt_camera_basis(&at, right, upp);
+        for (int q = 0; q < 3; ++q)
+            if (!std::isfinite(right[q]) || !std::isfinite(upp[q]))
+                return rt_fail(RT_EINVAL, std::string(who) + ": the camera's view direction is parallel to up within "
+                                                             "the exposure (cam, motion)");
+    }
+    for (int q = 0; q < 3; ++q) {
+        L.camera.up[q] = cam->up[q];
+        L.camera.eye_move[q] = m.eye[q];
+        L.camera.look_move[q] = m.look_at[q];
+    }
+    if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
+    RT_HIP(hipSetDevice(c->device));
+    const hipError_t e = with_depth(depth, [&](auto B) { return launch_shutter<decltype(B)::value>(L); });
+    if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_shutter_kernel: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+extern "C" int rt_render_shutter_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                     int depth, int samples, int jitter, uint32_t seed, double aperture,
+                                     double light_size, double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                     uint32_t* raycount2, void* stream) {
+    return shutter_render_dev("rt_render_shutter_dev", c, cam, motion, W, H, depth, samples, jitter, seed, aperture,
+                              light_size, shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
 }
 
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------

@@ -11,6 +11,8 @@
 //                                      whole frame with each pixel's sample spread, and over a compacted work list.
 //   rt_jitter_kernel<B, TRANSP, TREE>  the jittered render (rt_render_jitter_dev): the motion kind with each sample at
 //                                      a hashed sub-position of its stratum in every dimension.
+//   rt_shutter_kernel<B, TRANSP, TREE> the shutter render (rt_render_shutter_dev): the jittered kind with the camera
+//                                      of each sample's own time, its basis formed per lane.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -20,7 +22,8 @@
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
 // rt_adaptive.hip (rt_adaptive_b<B>.o), once per depth and kind rt_lens.hip (rt_lens_k<kind>_b<B>.o), and
-// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o) and rt_jitter.hip (rt_jitter_b<B>.o).
+// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o), rt_jitter.hip (rt_jitter_b<B>.o) and rt_shutter.hip
+// (rt_shutter_b<B>.o).
 #pragma once
 
 #include "rt_jitter.hpp"
@@ -304,6 +307,78 @@ __global__ __launch_bounds__(64) void rt_jitter_kernel(const DevScene* __restric
     }
 }
 
+// ---- The shutter render (rt_render_shutter_dev, include/rt_api.h): the jittered render with the camera itself moving
+// during the exposure, so that every sample has the camera of its own time. ----
+
+// What the shutter kernel gets beside the jittered kernel's arguments: the camera's up and the half-extents of the
+// eye's and the look-at point's move (rt_camera_motion: six doubles; all zero without a motion).
+struct ShutterParams {
+    double up[3];
+    double eye_move[3];
+    double look_move[3];
+};
+
+// rt_jitter_kernel statement for statement — wave layout, clamping, the key from the true sample-frame width, the
+// levels, the swept hits_ok, trace, reduction and store — but for the camera: P's eye and look are those of sigma = 0,
+// P's right and up' are not read, and the lane forms
+//     eye_s = eye + (sigma * eye_move),   look_s = look + (sigma * look_move)       (one operation per parenthesis),
+//     LD = look_s - eye_s,   right_s = normalize(LD x up),   up'_s = normalize(right_s x LD)
+// with rt_host.cpp's operation order (rt_camera_basis; cross and cam_normalize of rt_device.hpp: IEEE sqrt and
+// division), so sigma moves up ahead of the ray's end.  Under jitter a frame has up to S S J distinct times, so the
+// basis cannot be a table of the host's.  A zero move gives eye_s = eye and look_s = look (no component is -0.0) and
+// the basis rt_camera_basis gave P, bit for bit: the jittered render's frame.  eye_s, look_s and the basis are dead
+// once e and sp are formed — nothing of them is live across the trace.  hits_ok is the motion record's swept proof
+// from the lane's own start e, which now differs between the lanes of a wave by the eye's move too.  A kernel of its
+// own, not a flag of rt_jitter_kernel: that one's parameter list, hence its instances' code, stays what it was.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_shutter_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                        RenderParams P, JitterParams Q, ShutterParams C,
+                                                        double aperture, double light_size, double shutter,
+                                                        int tile_rows, void* o32, void* o8, double* o64,
+                                                        uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int x = lane & 7, y = lane >> 3;
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    const int i = tx * 8 + x, lr = ty * 8 + y;
+    const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+    const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed);
+    const int a = x & S1, b = y & S1, sj = s + jl;
+    const int n = a + (b << s);                             // time index a + S b
+    const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                    ldexp(1.0, -(s + sj)));
+    // the camera of the lane's time
+    const d3 eye = add(ld3(P.eye), scl(sigma, ld3(C.eye_move)));
+    const d3 look = add(ld3(P.look), scl(sigma, ld3(C.look_move)));
+    const d3 ld = sub(look, eye);
+    const d3 right = cam_normalize(cross(ld, ld3(C.up)));
+    const d3 upp = cam_normalize(cross(right, ld));
+    // screen_point of the fine camera at that time
+    const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+    const d3 sp = add(add(look, scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                      scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+    const double inv_sj = ldexp(1.0, -sj);
+    const auto t_of = [&](int c, int k) { return (double)(2 * ((c << jl) + k) + 1 - (1 << sj)) * inv_sj; };
+    const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+    const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+    const d3 e = add(add(eye, scl(aperture * ta, right)), scl(aperture * tb, upp));
+    const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+    V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+    const Motion mo{sigma, M};
+    uint32_t seg = 0, sh = 0;
+    d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                            LightShift{light_size * ga, light_size * gb}, &mo);
+    reduce_samples(s, 8, col, seg, sh);
+    if (a == 0 && b == 0 && i < P.width && lr < P.height && !pad) {
+        const size_t k = (size_t)(lr >> s) * (size_t)(P.width >> s) + (size_t)(i >> s);
+        store_sampled(P, k, col, seg, sh, o32, o8, o64, orc2);
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -325,12 +400,13 @@ struct SampledLaunch {
     double shutter;                            // MOTION: share of the displacements the exposure covers
     const DevMotion* motion;                   // MOTION: the context's motion record (rt_set_motion)
     uint8_t* spread;                           // rt_lens_coarse_kernel: one byte per output pixel
-    JitterParams jitter;                       // rt_jitter_kernel
+    JitterParams jitter;                       // rt_jitter_kernel, rt_shutter_kernel
+    ShutterParams camera;                      // rt_shutter_kernel
 };
 
 // Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
-// the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), and the jittered render's in
-// rt_jitter_b<B>.o (rt_jitter.hip).
+// the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), the jittered render's in
+// rt_jitter_b<B>.o (rt_jitter.hip) and the shutter render's in rt_shutter_b<B>.o (rt_shutter.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
@@ -339,6 +415,8 @@ template <int B>
 hipError_t launch_lens_refine(const SampledLaunch& L);
 template <int B>
 hipError_t launch_jitter(const SampledLaunch& L);
+template <int B>
+hipError_t launch_shutter(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
@@ -350,6 +428,8 @@ hipError_t launch_lens(const SampledLaunch& L);
     hipError_t launch_lens_refine<B>(const SampledLaunch& L);         \
     template <>                                                       \
     hipError_t launch_jitter<B>(const SampledLaunch& L);              \
+    template <>                                                       \
+    hipError_t launch_shutter<B>(const SampledLaunch& L);             \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -429,6 +509,17 @@ hipError_t launch_jitter_impl(const SampledLaunch& L) {
         hipLaunchKernelGGL((rt_jitter_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
                            L.stream, L.scene, L.motion, L.P, L.jitter, L.aperture, L.light_size, L.shutter, tile_rows,
                            L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_shutter_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_shutter_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
+                           L.stream, L.scene, L.motion, L.P, L.jitter, L.camera, L.aperture, L.light_size, L.shutter,
+                           tile_rows, L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

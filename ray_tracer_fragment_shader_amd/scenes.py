@@ -286,6 +286,22 @@ PINNED_RAYS = {"c1": 380_817, "c2": 3_684_271, "c3": 18_956_255, "c5": 90_722_78
                "demo": 358_434}
 
 
+def camera_motion(eye=(0.0, 0.0, 0.0), look_at=(0.0, 0.0, 0.0)) -> abi.rt_camera_motion:
+    """The half-extents of a camera's move during the exposure (Tracer.render_shutter): at shutter time sigma in
+    (-1, 1) the eye is at cam.eye + sigma * eye and looks at cam.look_at + sigma * look_at."""
+    m = abi.rt_camera_motion()
+    m.eye, m.look_at = abi.vec3(eye), abi.vec3(look_at)
+    return m
+
+
+def camera_at(cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], sigma: float) -> abi.rt_camera:
+    """rt_camera_at: the camera of Tracer.render_shutter's samples at shutter time `sigma`."""
+    out = abi.rt_camera()
+    abi.check(abi.lib().rt_camera_at(ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None,
+                                     float(sigma), ctypes.byref(out)), "rt_camera_at")
+    return out
+
+
 def rows(band_height: int = 1, n_ranks: int = 1, rank: int = 0, frames: int = 1) -> abi.rt_rows:
     r = abi.rt_rows()
     r.band_height, r.n_ranks, r.rank, r.frames = band_height, n_ranks, rank, frames

@@ -232,6 +232,28 @@ class Tracer:
         return self.render_jitter_into(cam, width, height, depth, samples, jitter, seed, aperture, light_size, shutter,
                                        bufs, stream)
 
+    def render_shutter_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int, height: int,
+                            depth: int, samples: int, jitter: int, seed: int, aperture: float, light_size: float,
+                            shutter: float, bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_shutter_dev into alloc_ss() buffers (full frames): the frame of render_jitter_into() with the
+        camera moving during the exposure: a sample at shutter time sigma sees from cam.eye + sigma * motion.eye
+        towards cam.look_at + sigma * motion.look_at (scenes.camera_motion; None: a frozen camera, which is
+        render_jitter_into()); asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        abi.check(abi.lib().rt_render_shutter_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height, depth,
+            samples, jitter, int(seed) & 0xFFFFFFFF, float(aperture), float(light_size), float(shutter),
+            _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
+            ctypes.c_void_p(st.cuda_stream)), "rt_render_shutter_dev")
+        return bufs
+
+    def render_shutter(self, cam, motion, width, height, depth, samples, jitter, seed, aperture, light_size, shutter,
+                       rgba32f=True, rgba8=False, rgb64f=False, raycount=False, stream=None):
+        """-> the buffers of alloc_ss() (the keys of render_ss())."""
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        return self.render_shutter_into(cam, motion, width, height, depth, samples, jitter, seed, aperture, light_size,
+                                        shutter, bufs, stream)
+
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
     def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
                             refined=True):
