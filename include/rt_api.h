@@ -622,6 +622,63 @@ int rt_render_shutter(rt_ctx* ctx, const rt_scene* scene, const double* displace
                       uint32_t seed, double aperture, double light_size, double shutter, float* rgba32f,
                       uint8_t* rgba8, double* rgb64f, rt_stats* stats);
 
+/* ---- progressive accumulation: many jittered passes summed in the kernel (ABI 10: new symbols only) -------------- */
+/* rt_render_shutter_dev takes at most 8 x 8 samples per pixel at one of 16 sub-positions per dimension: one noisy
+ * estimate.  rt_render_accum_dev adds the frames of K consecutive seeds to a caller-owned sum, in a fixed order, and
+ * writes the mean of all passes so far: 256 or 1024 samples per pixel in one call, or a preview that sharpens call after
+ * call.  Every value is a fixed-order sum of frames rt_render_shutter_dev defines.  For n0 = `first_pass`, K = `passes`
+ * >= 1, and every other argument as for rt_render_shutter_dev:
+ *  1. Pass.  Pass p, n0 <= p < n0 + K, has the value v_p: what rt_render_shutter_dev writes to rgb64f with the same
+ *     arguments and the seed (seed + p) mod 2^32 (after the reduction tree and the product with 1 / (S S)); its counters
+ *     are that frame's raycount2.
+ *  2. Sum.  Per channel, in FP64, one IEEE addition per pass, left to right:
+ *       n0 = 0: `accum` is NOT READ (it may be uninitialised); acc = v_0, then acc = acc + v_p for p = 1 .. K - 1;
+ *       n0 > 0: acc = accum, then acc = acc + v_p for p = n0 .. n0 + K - 1;
+ *     accum <- acc.  The order is part of the contract: summing the call's passes first and adding that sum to `accum`
+ *     is another value (on the oracle it differs in 30 of 209 pixels for n0 = 2, K = 3 of the tests' case).
+ *  3. Mean and outputs.  m = acc / (double)(n0 + K), one IEEE division per channel — not a product with a reciprocal,
+ *     which differs (26 and 37 of 209 pixels at K = 3 and K = 7 of the tests' case).  rgb64f is m; rgba32f and rgba8 derive from m by
+ *     rt_render_ss_dev rule 4; raycount2 is the sum of the K passes' counters of THIS call only, uint32 and wrapping.  A
+ *     channel with a NaN pass stays NaN in `accum` from then on (which NaN: unspecified); its rgba8 byte is 0.
+ *  4. Pins that follow, with NO shortcut in the implementation (one kernel runs for every argument): n0 = 0, K = 1 writes
+ *     exactly the images and counters of rt_render_shutter_dev with `seed`, and `accum` equals its rgb64f — so every pin
+ *     of the chain holds through it (rt_render_jitter_dev, _motion_dev, _soft_dev, _dof_dev, _ss_dev, and the plain frame
+ *     at S = J = 1).  A call (0, a) followed by a call (a, b) on the same `accum` leaves the same bytes in `accum` and
+ *     in every image as one call (0, a + b), and the two calls' counters sum to the one call's.  Equal arguments and an
+ *     equal `accum` give equal bytes, call after call and under graph replay.
+ *  5. rt_render_accum_dev: full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host
+ *     synchronisation, so the call may be captured in a hipGraph.  No per-view state; the scene and motion records are
+ *     read, never written.  The host may split a call into several launches of at most L passes each, so that one
+ *     launch on a shared GPU stays short; L is 4 (below) unless RT_ACCUM_MAX_PASSES (read by rt_ctx_create, 1 .. 65536)
+ *     says otherwise.  Rule 2 makes the split invisible: the images are the same bytes under every value.
+ *  6. RT_EINVAL (rt_last_error names the argument), with no byte of `accum` or of any image written, for every check of
+ *     rt_render_shutter_dev, a null `accum`, `passes` < 1 or above 65536, and `first_pass + passes` above 2^31.
+ *  7. Not offered: a per-pixel variance or stopping rule; accumulation for rt_render_lens_adaptive_dev; row bands; the
+ *     packed and multi-GPU paths; weights other than 1.  Jitter is quantised, so the mean converges to the regular grid
+ *     S J times finer per dimension, not to the continuous integral.
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, one sphere moving by |d| = 40, F = 1, A = 0, crane of
+ * |eye move| = 40, J = 16, RGBA32F + RGBA8, tools/bench_accum.py, profiles/accum/bench_accum.json; one
+ * rt_render_shutter_dev frame in the same run: 54 us at S = 1, 204 us at S = 2, 817 us at S = 4): one call of K passes
+ * takes 229 us (K = 4) and 906 us (K = 16) at S = 1, 888 us and 3508 us at S = 2 — 1.05 x - 1.09 x the single frame per
+ * pass; against K rt_render_shutter_dev calls into rgb64f with a separate FP64 accumulation per pass and one division
+ * and conversion at the end it is 0.49 x and 0.65 x at S = 1, 0.84 x and 0.95 x at S = 2, and against K calls of one pass
+ * each 0.81 x - 0.86 x; all three give the same bytes.  S = 4, K = 4, one launch: 3.58 ms, which is why L = 4.  The
+ * per-pass excess is the loop's own: the kernel arguments outlive the register file across the trace (64 scalar
+ * registers kept in vector lanes in the depth-1 opaque instance) and the running sums wait in LDS; profiles/accum/
+ * README.md has the counts.  Other scenes, depths and motions: not measured. */
+/* Device pointers; `accum`: width * height * 3 doubles, required; each output nullable, width * height pixels. */
+int rt_render_accum_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width, int height,
+                        int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes,
+                        double aperture, double light_size, double shutter, double* accum, float* rgba32f,
+                        uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_shutter: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the passes.  `accum` is a host buffer of width * height * 3 doubles, read
+ * when first_pass > 0 and written on success.  *stats as rt_render_shutter, over all passes of the call. */
+int rt_render_accum(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                    const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
+                    uint32_t seed, uint32_t first_pass, int passes, double aperture, double light_size, double shutter,
+                    double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
+
 /* ---- packed pixel formats (ABI 5)--------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.
  * GRAY formats hold the R channel only and are accepted only for an ACHROMATIC scene (rt_scene_achromatic):

@@ -52,6 +52,10 @@
 //                                                  camera motion blur: the eye moves by +-(0, 40, 0) and the look-at
 //                                                  point by +-(DX, DY, DZ) (world units) during the exposure; every sample
 //                                                  sees from the camera of its own time (rt_render_shutter; J defaults to 1)
+//   rt_render --config c2 --samples 2 --jitter 16 [--seed 7] --passes 64 [--shutter 1 [--eye-move 0,40,0] ...]
+//             [--aperture 8] [--light-size 40] --out c2_accum.ppm
+//                                                  64 jittered passes with the seeds 7 .. 70 summed in the kernel; the
+//                                                  image is their mean (rt_render_accum; K in 1 .. 65536)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -96,6 +100,7 @@ struct Options {
     int jitter = 0;                          // --jitter J: rt_render_jitter with --seed (needs --samples)
     bool camera_motion = false;              // --eye-move / --look-move DX,DY,DZ: rt_render_shutter (needs --shutter)
     rt_camera_motion camera_move = {};
+    int passes = 0;                          // --passes K: rt_render_accum, K passes from --seed on (needs --jitter)
     std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -273,10 +278,11 @@ int main(int argc, char** argv) {
         else if (a == "--coarse") o.coarse = std::atoi(next().c_str());
         else if (a == "--refine") { o.refine = true; o.refine_t = std::atoi(next().c_str()); }
         else if (a == "--jitter") { o.jitter = std::atoi(next().c_str()); if (o.jitter == 0) o.jitter = -1; }
+        else if (a == "--passes") { o.passes = std::atoi(next().c_str()); if (o.passes == 0) o.passes = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K]] "
                                     "[--eye-move DX,DY,DZ] [--look-move DX,DY,DZ]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
@@ -334,6 +340,14 @@ int main(int argc, char** argv) {
     }
     if (o.jitter != 0 && o.jitter != 1 && o.jitter != 2 && o.jitter != 4 && o.jitter != 8 && o.jitter != 16) {
         std::fprintf(stderr, "rt_render: --jitter must be 1, 2, 4, 8 or 16\n");
+        return 2;
+    }
+    if (o.passes != 0 && o.jitter == 0) {
+        std::fprintf(stderr, "rt_render: --passes needs --jitter\n");
+        return 2;
+    }
+    if (o.passes != 0 && (o.passes < 1 || o.passes > 65536)) {
+        std::fprintf(stderr, "rt_render: --passes must lie in 1 .. 65536\n");
         return 2;
     }
     if ((o.coarse != 0) != o.refine) {
@@ -459,6 +473,7 @@ int main(int argc, char** argv) {
     rt_ctx* ctx = nullptr;
     check(rt_ctx_create(o.device, &ctx), "rt_ctx_create");
     std::vector<uint8_t> rgba8((size_t)W * H * 4);
+    std::vector<double> accum(o.passes != 0 ? (size_t)W * H * 3 : 0);
     if (o.faithful >= 0) {
         uint64_t calls = 0;
         std::vector<uint8_t> ns((size_t)W * H);
@@ -485,6 +500,11 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
+        else if (o.passes != 0)
+            check(rt_render_accum(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                  o.camera_motion ? &o.camera_move : nullptr, W, H, depth, o.samples, o.jitter,
+                                  (uint32_t)o.seed, 0u, o.passes, o.aperture, o.light_size, o.shutter, accum.data(),
+                                  nullptr, rgba8.data(), nullptr, &st), "rt_render_accum");
         else if (o.camera_motion)
             check(rt_render_shutter(ctx, &scene, displacement.data(), &cam, &o.camera_move, W, H, depth, o.samples,
                                     o.jitter != 0 ? o.jitter : 1, (uint32_t)o.seed, o.aperture, o.light_size, o.shutter,
@@ -520,6 +540,10 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
+    if (o.passes != 0)
+        std::printf("rt_render: accumulated, %d passes with the seeds %u .. %u: the mean of %d x %d x %d samples per "
+                    "pixel, %llu primary rays\n", o.passes, o.seed, (unsigned)(o.seed + (unsigned)o.passes - 1u), o.passes,
+                    o.samples, o.samples, (unsigned long long)st.primary_rays);
     if (o.refine)
         std::printf("rt_render: adaptive lens render, threshold %d, shutter %g, light half-width %g, lens half-width %g: "
                     "%llu of %llu pixels refined from %d x %d to %d x %d samples\n", o.refine_t, o.shutter, o.light_size,

@@ -101,6 +101,7 @@ static void knobs_from_env(rt_ctx::Knobs& k) {
     if (const char* e = getenv("RT_FLAT_TILES")) k.flat_tiles = atoi(e) != 0;
     if (const char* e = getenv("RT_ORDER_POLICY")) k.order_policy = std::min(std::max(atoi(e), 0), 1);
     if (const char* e = getenv("RT_ACHRO_OFF")) k.achro_off = atoi(e) != 0;
+    if (const char* e = getenv("RT_ACCUM_MAX_PASSES")) k.accum_max_passes = std::min(std::max(atoi(e), 1), 65536);
 }
 
 extern "C" int rt_ctx_create(int device, rt_ctx** out) {

@@ -39,6 +39,7 @@ struct RenderParams;
 
 constexpr int kOrderMax = 8192;                // tile rows rt_order_kernel sorts (one workgroup, keys in LDS)
 constexpr int kRecalibrate = 8;                // renders of a moving camera per re-timing of the tile rows
+constexpr int kAccumMaxPasses = 4;             // passes per rt_accum_kernel launch (rt_ctx::Knobs::accum_max_passes)
 constexpr uint8_t kClassTrace = 0, kClassSky = 1, kClassSphereFree = 2;   // rt_ctx::View::tile_class
 
 // A grow-only device buffer.  reserve: room for `n` bytes, by free-then-malloc when it is too small (the caller orders
@@ -127,6 +128,14 @@ struct rt_ctx {
         int sd_split = 2;                      // RT_SDMA_SPLIT: engines a frame's copy is split over (1, 2)
         int sd_writer_req = 0;                 // RT_SDMA_WRITER (A/B): 1 or 2 forces the writer, 0 tries 2 then 1
         int sd_wait_ms = 5000;                 // RT_SDMA_WAIT_MS: how often sdma_wait re-checks a slow render
+        // RT_ACCUM_MAX_PASSES: the most passes one rt_accum_kernel launch runs (rt_sampled.hip accum_render_dev splits a
+        // call; the images are the same bytes under every value).  A launch holds the CUs until its last pass is done, so
+        // on a GPU shared with other work it should stay in the low milliseconds: a pass of the measured workload (c2
+        // 1920 x 1080, depth 1, crane, one moving sphere, J = 16) takes 0.89 ms at S = 4 inside the loop, a launch of
+        // kAccumMaxPasses = 4 of them 3.58 ms (profiles/accum/bench_accum.json; 0.89 ms at S = 2, 0.23 ms at S = 1; S = 8,
+        // four times the rays, not measured).  A larger value saves little more: per launch the split costs one read
+        // and one write of the sums (48 bytes per pixel).  Other scenes, depths and motions: not measured.
+        int accum_max_passes = kAccumMaxPasses;
     } knobs;
 
     // The eye the per-eye records inside d_scene were prepared for (rt_plain.hip; rt_set_scene clears `valid`).
@@ -245,9 +254,9 @@ struct rt_ctx {
         uint64_t ticket = 0;                   // rt_render_packed_async frames queued so far
         int last_copy_mode = -1;               // the mode the last packed frame took (rt_diag_copy_path)
         // rt_render's device buffers (grow-only, reused across calls): rgba32f, rgba8, rgb64f, raycount, sums,
-        // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace
-        static constexpr int kBufRefined = 5 + kSlots, kBufAdaptive = 6 + kSlots;
-        static constexpr int kBufs = 7 + kSlots;
+        // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace, and rt_render_accum's sums
+        static constexpr int kBufRefined = 5 + kSlots, kBufAdaptive = 6 + kSlots, kBufAccum = 7 + kSlots;
+        static constexpr int kBufs = 8 + kSlots;
         void* d_out[kBufs] = {};
         size_t out_cap[kBufs] = {};
     } frames;
@@ -318,6 +327,12 @@ int jitter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, int W, i
 int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                        int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
                        double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream);
+// The device render of the accumulating render, as `who` (rt_frames.hip's host entry point too); the most passes of a call.
+constexpr int kAccumCallPasses = 65536;
+int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                     int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
+                     double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                     uint32_t* raycount2, void* stream);
 
 // rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after
 // the context's streams have drained).

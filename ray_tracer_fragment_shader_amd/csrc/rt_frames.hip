@@ -393,6 +393,41 @@ extern "C" int rt_render_shutter(rt_ctx* c, const rt_scene* scene, const double*
         [&](uint64_t* prim) { *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples; return RT_OK; });
 }
 
+// rt_render for accumulated passes: rt_render_shutter's steps with accum_render_dev (as rt_render_accum_dev) on a
+// device copy of `accum`, which is uploaded first when the call continues a sum (first_pass > 0) and copied back after
+// the render.  The counters behind *stats are the call's, so its primary rays are those of all its passes.
+extern "C" int rt_render_accum(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                               const rt_camera_motion* motion, int W, int H, int depth, int samples, int jitter,
+                               uint32_t seed, uint32_t first_pass, int passes, double aperture, double light_size,
+                               double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                               rt_stats* stats) {
+    const char* who = "rt_render_accum";
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc || (rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (passes < 1 || passes > kAccumCallPasses)
+        return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
+    if ((uint64_t)first_pass + (uint64_t)passes > (1ull << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": first_pass + passes must not exceed 2^31");
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const size_t npx = (size_t)W * H;
+    ExtraBuf x[1] = {{rt_ctx::Frames::kBufAccum, npx * 24, accum, nullptr}};
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, x, 1,
+        [&](void* const* d) {
+            if (first_pass > 0) RT_HIP(hipMemcpyAsync(x[0].dev, accum, npx * 24, hipMemcpyHostToDevice, c->frames.rs));
+            return accum_render_dev("rt_render_accum_dev", c, cam, motion, W, H, depth, samples, jitter, seed, first_pass,
+                                    passes, aperture, light_size, shutter, (double*)x[0].dev, (float*)d[0],
+                                    (uint8_t*)d[1], (double*)d[2], (uint32_t*)d[3], c->frames.rs);
+        },
+        [&](uint64_t* prim) {
+            *prim = (uint64_t)npx * (uint64_t)samples * (uint64_t)samples * (uint64_t)passes;
+            return RT_OK;
+        });
+}
+
 // rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
 // rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
 // back.

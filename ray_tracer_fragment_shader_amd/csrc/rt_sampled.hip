@@ -1,6 +1,6 @@
 // rt_sampled.hip — the device entry points of the sampled renders of rt_sampled.hpp: adaptive supersampling
 // (base render, rt_classify_kernel, the refine launch), the lens family's one launch, the jittered render's, the
-// shutter render's and the adaptive lens render's three passes.
+// shutter render's, the accumulating render's launches and the adaptive lens render's three passes.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -308,11 +308,12 @@ extern "C" int rt_render_jitter_dev(rt_ctx* c, const rt_camera* cam, int W, int 
 // parallel to up there is rejected; in between it is the caller's).  The six half-extents and the camera's up travel in
 // the kernel arguments; motion = nullptr is the zero motion.  Nothing per view, no field of the context written, no
 // shortcut for a zero motion, shutter 0, jitter 1 or any argument of 0.
-int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
-                       int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
-                       double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
-                       void* stream) {
-    SampledLaunch L{};
+// The shutter render's checks and its launch record: jitter_launch, then the camera motion's own checks and fields.
+static int shutter_launch(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                          int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                          double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                          void* stream, SampledLaunch* out) {
+    SampledLaunch& L = *out;
     const int rc = jitter_launch(who, c, cam, W, H, depth, samples, jitter, seed, aperture, light_size, shutter, rgba32f,
                                  rgba8, rgb64f, raycount2, stream, &L);
     if (rc) return rc;
@@ -336,6 +337,17 @@ int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const r
         L.camera.eye_move[q] = m.eye[q];
         L.camera.look_move[q] = m.look_at[q];
     }
+    return RT_OK;
+}
+
+int shutter_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                       int depth, int samples, int jitter, uint32_t seed, double aperture, double light_size,
+                       double shutter, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                       void* stream) {
+    SampledLaunch L{};
+    const int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
+                                  rgba32f, rgba8, rgb64f, raycount2, stream, &L);
+    if (rc) return rc;
     if (!rgba32f && !rgba8 && !rgb64f && !raycount2) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     const hipError_t e = with_depth(depth, [&](auto B) { return launch_shutter<decltype(B)::value>(L); });
@@ -349,6 +361,53 @@ extern "C" int rt_render_shutter_dev(rt_ctx* c, const rt_camera* cam, const rt_c
                                      uint32_t* raycount2, void* stream) {
     return shutter_render_dev("rt_render_shutter_dev", c, cam, motion, W, H, depth, samples, jitter, seed, aperture,
                               light_size, shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
+}
+
+// ---- progressive accumulation (include/rt_api.h) -----------------------------------------------------------------------
+// Passes first_pass .. first_pass + passes - 1 of the shutter render (seed + p each) added to `accum` in the contract's
+// order by rt_accum_kernel: the shutter render's checks and launch record, the call's own checks, then launches of at most
+// L = Knobs::accum_max_passes passes each on `stream`.  A launch reads `accum` unless it begins at pass 0 and writes it, so
+// the sum a later launch continues is the one the launch before it stored: one addition per pass from the loaded value
+// either way, and the split is invisible in the bytes.  Every launch adds its passes' counters to raycount2 (the call's
+// first launch starts them at zero); only the last one gets the image pointers, so the mean is formed once, from the
+// whole sum.  Nothing per view, no field of the context written, no allocation, no shortcut for any argument; with no
+// output at all the sum is still advanced.
+int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                     int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
+                     double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                     uint32_t* raycount2, void* stream) {
+    SampledLaunch L{};
+    const int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
+                                  rgba32f, rgba8, rgb64f, raycount2, stream, &L);
+    if (rc) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (passes < 1 || passes > kAccumCallPasses)
+        return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
+    if ((uint64_t)first_pass + (uint64_t)passes > (1ull << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": first_pass + passes must not exceed 2^31");
+    RT_HIP(hipSetDevice(c->device));
+    L.accum = accum;
+    L.call_first = first_pass;
+    const uint32_t end = first_pass + (uint32_t)passes, step = (uint32_t)c->knobs.accum_max_passes;
+    for (uint32_t p = first_pass; p < end; p += step) {
+        L.first_pass = p;
+        L.passes = std::min(step, end - p);
+        const bool last = p + L.passes == end;
+        L.o32 = last ? rgba32f : nullptr;
+        L.o8 = last ? rgba8 : nullptr;
+        L.o64 = last ? rgb64f : nullptr;
+        const hipError_t e = with_depth(depth, [&](auto B) { return launch_accum<decltype(B)::value>(L); });
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_accum_kernel: ") + hipGetErrorString(e));
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_render_accum_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                   int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes,
+                                   double aperture, double light_size, double shutter, double* accum, float* rgba32f,
+                                   uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream) {
+    return accum_render_dev("rt_render_accum_dev", c, cam, motion, W, H, depth, samples, jitter, seed, first_pass, passes,
+                            aperture, light_size, shutter, accum, rgba32f, rgba8, rgb64f, raycount2, stream);
 }
 
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------

@@ -13,6 +13,8 @@
 //                                      a hashed sub-position of its stratum in every dimension.
 //   rt_shutter_kernel<B, TRANSP, TREE> the shutter render (rt_render_shutter_dev): the jittered kind with the camera
 //                                      of each sample's own time, its basis formed per lane.
+//   rt_accum_kernel<B, TRANSP, TREE>   progressive accumulation (rt_render_accum_dev): the shutter kind's frames of
+//                                      consecutive seeds, summed per pixel in a fixed order by the wave that owns it.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -22,8 +24,8 @@
 //
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
 // rt_adaptive.hip (rt_adaptive_b<B>.o), once per depth and kind rt_lens.hip (rt_lens_k<kind>_b<B>.o), and
-// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o), rt_jitter.hip (rt_jitter_b<B>.o) and rt_shutter.hip
-// (rt_shutter_b<B>.o).
+// rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o), rt_jitter.hip (rt_jitter_b<B>.o), rt_shutter.hip
+// (rt_shutter_b<B>.o) and rt_accum.hip (rt_accum_b<B>.o).
 #pragma once
 
 #include "rt_jitter.hpp"
@@ -379,6 +381,137 @@ __global__ __launch_bounds__(64) void rt_shutter_kernel(const DevScene* __restri
     }
 }
 
+// ---- Progressive accumulation (rt_render_accum_dev, include/rt_api.h): the frames of consecutive seeds of the shutter
+// render summed per pixel in the kernel, in the contract's fixed order. ----
+
+// What the accumulating kernel gets beside the shutter kernel's arguments: the passes of this launch, first ..
+// first + count - 1 (first + count <= 2^31), and the first pass of the call the launch belongs to (the host splits a
+// call into launches of at most rt_ctx::Knobs::accum_max_passes passes).
+struct AccumParams {
+    uint32_t first;
+    uint32_t count;
+    uint32_t call_first;
+};
+
+// rt_shutter_kernel's wave layout, clamping and key; then a loop over the launch's passes whose body is that kernel's
+// statements from the hash word on, with the seed Q.seed + p (uint32, wrapping) of pass p: word, levels, time, the
+// lane's camera and basis, ray, light shift, swept hits_ok, trace and reduce_samples.  After the reduction every lane of
+// a pixel's block holds the pass's value v_p and counters; the block's first lane, (a, b) = (0, 0), adds them to the
+// pixel's running sum:
+//     acc = accum[k] if first > 0, and acc = acc + v_p pass by pass: one IEEE addition per channel, left to right from
+//           the LOADED value — never a local partial sum added to it afterwards, which rounds differently;
+//     acc = v_0 for pass 0: accum is not read when first = 0 (it may be uninitialised).
+// Both branches are on kernel arguments: wave-uniform.  accum is read at most once, before the loop, and written once,
+// after it; so are the counters: orc2 holds the sum over the passes of the CALL, so a launch that is not the call's
+// first (first > call_first) starts from the words the launch before it left.  The images derive from the mean
+// m = acc / (double)(first + count), one IEEE division per channel (not a product with a reciprocal: other bits), by
+// store_sampled; the host passes the image pointers to a call's last launch only, and the division runs under them.
+// The running sum and the two counters are parked in LDS across the trace, not held in registers: with them (and the
+// lane's coordinates) live across the trace the opaque instance needed 107 VGPRs and the transparent one 142, a wave per
+// SIMD fewer than the shutter kernel's 84 and 119; parked they need 93 and 126 at depth 1 and keep its 5 and 4 waves.
+// A kernel of its own, not a flag of rt_shutter_kernel: that one's parameter list, hence its instances' code, stays what
+// it was.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_accum_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                      RenderParams P, JitterParams Q, ShutterParams C, AccumParams N,
+                                                      double aperture, double light_size, double shutter,
+                                                      int tile_rows, double* accum, void* o32, void* o8, double* o64,
+                                                      uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl, sj = s + jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    // The lane's coordinates are formed from its number again wherever they are read — before the loop, in every pass
+    // and after the loop — behind an empty asm that hides the number's origin from the optimiser: otherwise the dozen
+    // values derived from it stay in registers across the trace beside the running sum, which cost the opaque and the
+    // transparent instances a wave per SIMD each (107 and 142 VGPRs against the shutter kernel's 84 and 119).
+    struct Lane { int i, lr, a, b, q; bool owner; size_t k; };
+    const auto lane_of = [&]() {
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        const int x = l & 7, y = l >> 3;
+        Lane r;
+        r.i = tx * 8 + x;
+        r.lr = ty * 8 + y;
+        r.a = x & S1;
+        r.b = y & S1;
+        r.q = ((y >> s) << (3 - s)) + (x >> s);          // the pixel's number in the tile
+        r.owner = r.a == 0 && r.b == 0 && r.i < P.width && r.lr < P.height && !pad;
+        r.k = (size_t)(r.lr >> s) * (size_t)(P.width >> s) + (size_t)(r.i >> s);      // read under `owner` only
+        return r;
+    };
+    // The running sums wait in LDS behind trace()'s slots, one slot per output pixel of the tile (accum_park_bytes):
+    // three doubles and the two counters, touched by the pixel's first lane alone.
+    const int npix = 64 >> (2 * s);
+    double* park_rgb = reinterpret_cast<double*>(smem + (TREE ? 0 : slot_bytes(B, TRANSP, 64)));
+    uint32_t* park_rc = reinterpret_cast<uint32_t*>(park_rgb + 3 * npix);
+    {
+        const Lane ln = lane_of();
+        if (ln.owner) {
+            d3 acc = mk(0.0, 0.0, 0.0);
+            uint32_t seg_sum = 0, sh_sum = 0;
+            if (N.first > 0) acc = mk(accum[3 * ln.k], accum[3 * ln.k + 1], accum[3 * ln.k + 2]);
+            if (N.first > N.call_first && orc2) { seg_sum = orc2[2 * ln.k]; sh_sum = orc2[2 * ln.k + 1]; }
+            park_rgb[ln.q] = acc.x; park_rgb[npix + ln.q] = acc.y; park_rgb[2 * npix + ln.q] = acc.z;
+            park_rc[ln.q] = seg_sum; park_rc[npix + ln.q] = sh_sum;
+        }
+    }
+    for (uint32_t t = 0; t < N.count; ++t) {
+        const uint32_t p = N.first + t;
+        const Lane ln = lane_of();
+        const int i = ln.i, lr = ln.lr, a = ln.a, b = ln.b;
+        const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+        const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed + p);
+        const int n = a + (b << s);                         // time index a + S b
+        const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                        ldexp(1.0, -(s + sj)));
+        // the camera of the lane's time
+        const d3 eye = add(ld3(P.eye), scl(sigma, ld3(C.eye_move)));
+        const d3 look = add(ld3(P.look), scl(sigma, ld3(C.look_move)));
+        const d3 ld = sub(look, eye);
+        const d3 right = cam_normalize(cross(ld, ld3(C.up)));
+        const d3 upp = cam_normalize(cross(right, ld));
+        // screen_point of the fine camera at that time
+        const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+        const d3 sp = add(add(look, scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                          scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+        const double inv_sj = ldexp(1.0, -sj);
+        const auto t_of = [&](int c, int kd) { return (double)(2 * ((c << jl) + kd) + 1 - (1 << sj)) * inv_sj; };
+        const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+        const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+        const d3 e = add(add(eye, scl(aperture * ta, right)), scl(aperture * tb, upp));
+        const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+        V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+        const Motion mo{sigma, M};
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                                LightShift{light_size * ga, light_size * gb}, &mo);
+        reduce_samples(s, 8, col, seg, sh);
+        const Lane after = lane_of();
+        if (after.owner) {
+            const int q = after.q;
+            const d3 acc = p == 0 ? col : add(mk(park_rgb[q], park_rgb[npix + q], park_rgb[2 * npix + q]), col);
+            park_rgb[q] = acc.x; park_rgb[npix + q] = acc.y; park_rgb[2 * npix + q] = acc.z;
+            park_rc[q] += seg;
+            park_rc[npix + q] += sh;
+        }
+    }
+    const Lane ln = lane_of();
+    if (ln.owner) {
+        const size_t k = ln.k;
+        const int q = ln.q;
+        const d3 acc = mk(park_rgb[q], park_rgb[npix + q], park_rgb[2 * npix + q]);
+        const uint32_t seg_sum = park_rc[q], sh_sum = park_rc[npix + q];
+        accum[3 * k] = acc.x; accum[3 * k + 1] = acc.y; accum[3 * k + 2] = acc.z;
+        if (o32 || o8 || o64 || orc2) {
+            const double cnt = (double)(N.first + N.count);
+            store_sampled(P, k, mk(acc.x / cnt, acc.y / cnt, acc.z / cnt), seg_sum, sh_sum, o32, o8, o64, orc2);
+        }
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -401,12 +534,16 @@ struct SampledLaunch {
     const DevMotion* motion;                   // MOTION: the context's motion record (rt_set_motion)
     uint8_t* spread;                           // rt_lens_coarse_kernel: one byte per output pixel
     JitterParams jitter;                       // rt_jitter_kernel, rt_shutter_kernel
-    ShutterParams camera;                      // rt_shutter_kernel
+    ShutterParams camera;                      // rt_shutter_kernel, rt_accum_kernel
+    // rt_accum_kernel: the launch's passes are first_pass .. first_pass + passes - 1 of the call that began at call_first
+    uint32_t first_pass, passes, call_first;
+    double* accum;                             // the running sums, 3 doubles per output pixel
 };
 
 // Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
 // the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), the jittered render's in
-// rt_jitter_b<B>.o (rt_jitter.hip) and the shutter render's in rt_shutter_b<B>.o (rt_shutter.hip).
+// rt_jitter_b<B>.o (rt_jitter.hip), the shutter render's in rt_shutter_b<B>.o (rt_shutter.hip) and the accumulating
+// render's in rt_accum_b<B>.o (rt_accum.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
@@ -417,6 +554,8 @@ template <int B>
 hipError_t launch_jitter(const SampledLaunch& L);
 template <int B>
 hipError_t launch_shutter(const SampledLaunch& L);
+template <int B>
+hipError_t launch_accum(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
@@ -430,6 +569,8 @@ hipError_t launch_lens(const SampledLaunch& L);
     hipError_t launch_jitter<B>(const SampledLaunch& L);              \
     template <>                                                       \
     hipError_t launch_shutter<B>(const SampledLaunch& L);             \
+    template <>                                                       \
+    hipError_t launch_accum<B>(const SampledLaunch& L);               \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -520,6 +661,21 @@ hipError_t launch_shutter_impl(const SampledLaunch& L) {
         hipLaunchKernelGGL((rt_shutter_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64), lds,
                            L.stream, L.scene, L.motion, L.P, L.jitter, L.camera, L.aperture, L.light_size, L.shutter,
                            tile_rows, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+// LDS of rt_accum_kernel's parked sums behind trace()'s slots: 3 doubles and 2 counters per output pixel of a tile.
+inline size_t accum_park_bytes(int ss_log2) { return (size_t)(64 >> (2 * ss_log2)) * (3 * 8 + 2 * 4); }
+
+template <int B>
+hipError_t launch_accum_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    const AccumParams n{L.first_pass, L.passes, L.call_first};
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_accum_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64),
+                           lds + accum_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera, n, L.aperture, L.light_size, L.shutter,
+                           tile_rows, L.accum, L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

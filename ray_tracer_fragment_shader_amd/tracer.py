@@ -254,6 +254,44 @@ class Tracer:
         return self.render_shutter_into(cam, motion, width, height, depth, samples, jitter, seed, aperture, light_size,
                                         shutter, bufs, stream)
 
+    # ---------------------------------------------------------------------------- progressive accumulation
+    def alloc_accum(self, width: int, height: int):
+        """The running sums of render_accum_into(): (H, W, 3) float64, uninitialised (a call with first_pass = 0 does
+        not read them)."""
+        return torch.empty((height, width, 3), dtype=torch.float64, device=torch.device("cuda", self.device))
+
+    def render_accum_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int, height: int,
+                          depth: int, samples: int, jitter: int, seed: int, first_pass: int, passes: int,
+                          aperture: float, light_size: float, shutter: float, accum: torch.Tensor, bufs: dict,
+                          stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_accum_dev: the frames render_shutter_into() gives the seeds seed + first_pass .. seed + first_pass
+        + passes - 1 added to `accum` (alloc_accum()) one by one, in that order, and the mean of all first_pass + passes
+        frames written into alloc_ss() buffers (`raycount`: the sums of this call's passes); first_pass = 0 starts a
+        new sum.  Asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if accum is None or accum.dtype != torch.float64 or accum.numel() != width * height * 3:
+            raise ValueError("accum must be a float64 tensor of width * height * 3 elements (alloc_accum)")
+        abi.check(abi.lib().rt_render_accum_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height, depth,
+            samples, jitter, int(seed) & 0xFFFFFFFF, int(first_pass), int(passes), float(aperture), float(light_size),
+            float(shutter), _ptr(accum), _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")),
+            _ptr(bufs.get("raycount")), ctypes.c_void_p(st.cuda_stream)), "rt_render_accum_dev")
+        return bufs
+
+    def render_accum(self, cam, motion, width, height, depth, samples, jitter, seed, first_pass, passes, aperture,
+                     light_size, shutter, accum=None, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
+                     stream=None):
+        """-> (the buffers of alloc_ss(), the accumulator): `accum` continued, or a new one when it is None (then
+        first_pass must be 0)."""
+        if accum is None:
+            if first_pass != 0:
+                raise ValueError("first_pass > 0 continues a sum: pass its accum")
+            accum = self.alloc_accum(width, height)
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        self.render_accum_into(cam, motion, width, height, depth, samples, jitter, seed, first_pass, passes, aperture,
+                               light_size, shutter, accum, bufs, stream)
+        return bufs, accum
+
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
     def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
                             refined=True):
