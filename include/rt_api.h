@@ -653,9 +653,10 @@ int rt_render_shutter(rt_ctx* ctx, const rt_scene* scene, const double* displace
  *     says otherwise.  Rule 2 makes the split invisible: the images are the same bytes under every value.
  *  6. RT_EINVAL (rt_last_error names the argument), with no byte of `accum` or of any image written, for every check of
  *     rt_render_shutter_dev, a null `accum`, `passes` < 1 or above 65536, and `first_pass + passes` above 2^31.
- *  7. Not offered: a per-pixel variance or stopping rule; accumulation for rt_render_lens_adaptive_dev; row bands; the
+ *  7. Not offered: accumulation for rt_render_lens_adaptive_dev; row bands; the
  *     packed and multi-GPU paths; weights other than 1.  Jitter is quantised, so the mean converges to the regular grid
- *     S J times finer per dimension, not to the continuous integral.
+ *     S J times finer per dimension, not to the continuous integral.  A per-pixel variance and stopping rule is a call
+ *     of its own: rt_render_converge_dev (below), which sums in this call's order.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, one sphere moving by |d| = 40, F = 1, A = 0, crane of
  * |eye move| = 40, J = 16, RGBA32F + RGBA8, tools/bench_accum.py, profiles/accum/bench_accum.json; one
  * rt_render_shutter_dev frame in the same run: 54 us at S = 1, 204 us at S = 2, 817 us at S = 4): one call of K passes
@@ -678,6 +679,86 @@ int rt_render_accum(rt_ctx* ctx, const rt_scene* scene, const double* displaceme
                     const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
                     uint32_t seed, uint32_t first_pass, int passes, double aperture, double light_size, double shutter,
                     double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats);
+
+/* ---- converging accumulation: a pixel stops once its standard error is low (ABI 10: new symbols only) ------------ */
+/* rt_render_accum_dev gives every pixel the same K passes, though most pixels of a frame never change from pass to pass
+ * and the rest stays noisy for dozens.  rt_render_converge_dev accumulates in rt_render_accum_dev's fixed order, keeps a
+ * per-pixel sum of squares and pass count beside the sum, and stops giving a pixel passes once the estimated standard
+ * error of its mean is at most a tolerance in every channel: a budget of 64 or 256 passes that only the noisy pixels use.
+ * Every argument is as for rt_render_accum_dev, except that `first_pass` is gone and that `passes` = K >= 1 is a budget
+ * per pixel and call, `min_passes` = M and `tolerance` = E.
+ *  State.  Three caller-owned device buffers hold the state (acc, sq, n) of a pixel: `accum`, 3 doubles per pixel;
+ *     `accum2`, 3 doubles per pixel, the sums of squares; `count`, one uint32 per pixel.  All three are required.  A new
+ *     sum starts from a zeroed `count`; where n = 0, `accum` and `accum2` are NOT READ (they may be uninitialised).
+ *     Every pixel is independent of every other.
+ *  1. Pass.  v_p is what rt_render_shutter_dev writes to rgb64f for this pixel with the seed (seed + p) mod 2^32; its
+ *     counters are that frame's raycount2 words for the pixel.  The pass a pixel receives next is the pass with the
+ *     number of its own n: a pixel's passes are always 0, 1, 2, ..., without a gap, whatever happens to other pixels.
+ *  2. Step, up to K times per call: if stopped(acc, sq, n), end.  Otherwise v = v_n and, per channel, in FP64, one IEEE
+ *     operation per operator, no contraction:
+ *       n = 0: acc = v, sq = v * v;
+ *       n > 0: acc = acc + v, sq = sq + (v * v) — one multiplication, then one addition; a fused multiply-add gives
+ *              other bits (on the oracle 90 of 627 channel values differ after 6 passes of the tests' main case);
+ *     then n = n + 1.
+ *  3. Stop rule.  stopped(acc, sq, n) is true iff n = 2^31, or n >= M and no channel has d > lim, where
+ *       d = sq - (acc * acc) / (double)n            (a multiplication, a division, a subtraction),
+ *       lim = (E * E) * ((double)n * (double)(n - 1))   (three multiplications):
+ *     the estimated standard error of the mean is at most E.  A NaN d does not hold a pixel back (the comparison is
+ *     false).  The rule is evaluated before every pass, at the start of a call too, so a pixel that was stopped under a
+ *     loose E resumes, with its next pass, when a later call gives a smaller E or a larger M.
+ *  4. Outputs, written for every pixel whether or not it received a pass in this call: the state is written back;
+ *     m = acc / (double)n, one IEEE division (n >= 1 after any call); rgb64f, rgba32f and rgba8 derive from m by
+ *     rt_render_ss_dev rule 4; raycount2 holds the sums of the counters of the passes the pixel received in THIS call
+ *     (0, 0 for a pixel that received none); `active`, a nullable device uint32, holds the number of pixels for which
+ *     stopped() is false on the final state.
+ *  5. Pins that follow, with NO shortcut in the implementation (one kernel runs for every argument).  With M > K and a
+ *     zeroed `count`: `accum`, every image and raycount2 hold exactly the bytes of rt_render_accum_dev(first_pass 0,
+ *     passes K), `count` = K everywhere and `active` = width * height — so K = 1 is rt_render_shutter_dev and every pin
+ *     of the chain holds through it.  For any arguments a pixel with count n has in `accum` exactly what
+ *     rt_render_accum_dev(0, n) leaves there.  A call of a passes followed by a call of b passes, with equal M and E,
+ *     leaves the same bytes in all three state buffers and in every image as one call of a + b, and the two calls'
+ *     counters sum to the one call's; the host's split into launches of at most L passes (rt_render_accum_dev rule 5,
+ *     RT_ACCUM_MAX_PASSES) is invisible for the same reason.  Equal arguments and equal state give equal bytes, call
+ *     after call and under graph replay.
+ *  6. Full frames only (no rt_rows).  Asynchronous on `stream`, no allocation and no host synchronisation; capturable
+ *     in a hipGraph: one stream, a straight line of nodes, the reset of `active` a memset node of the call.  No per-view
+ *     state; the scene and motion records are read, never written.
+ *  7. RT_EINVAL (rt_last_error names the argument), with no byte written, for every check of rt_render_shutter_dev, a
+ *     null `accum`, `accum2` or `count`, `passes` outside 1 .. 65536, `min_passes` outside 2 .. 2^31, and a `tolerance`
+ *     that is negative, NaN or infinite.
+ *  8. Not offered: a relative or perceptual tolerance; a tolerance per channel; compaction of the live tiles into a
+ *     work list; a stopping rule in rt_render_lens_adaptive_dev; row bands; the packed and multi-GPU paths.
+ * One wave keeps its 8 x 8 tile of the sample grid for the whole launch, as in rt_render_accum_dev, and leaves its pass
+ * loop as soon as all of its pixels have stopped; a wave whose pixels had all stopped before the launch traces nothing.
+ * The lanes of a stopped pixel in a live wave trace and discard.
+ * Measured: MI355X, c2 1920 x 1080 output, depth 1, the scene of rt_render_accum_dev's figures, J = 16, K = 64, M = 4,
+ * RGBA32F + RGBA8, tools/bench_converge.py, profiles/converge/bench_converge.json; rt_render_accum_dev(0, 64) in the
+ * same run: 3.63 ms at S = 1, 14.05 ms at S = 2. With M = 65, so that nothing stops, the call takes 4.20 ms and 15.81
+ * ms, 1.16 x and 1.13 x: the price of the second sum and of the rule (at S = 2 8 % per launch: 7.5 % more vector
+ * instructions, 52 instead of 24 bytes of state per pixel; and 0.7 ms in the last launch, where every wave adds to
+ * `active`). From a zeroed count it takes 3.34 ms (E = 1 / 255) and 3.23 ms (4 / 255) at S = 1, 10.57 ms and 8.42 ms
+ * at S = 2: 0.92 x, 0.89 x, 0.75 x and 0.60 x rt_render_accum_dev, while tracing 0.51, 0.48, 0.46 and 0.35 of the
+ * wave-passes (0.42, 0.36, 0.39, 0.25 of the pixel-passes); the gap is stopped lanes in live waves, the waves of all
+ * 16 launches that only load their state and leave, and the live waves being the costly ones of the frame. The RMS
+ * difference to a 256-pass mean doubles against the full budget (0.0134 against 0.0072 at S = 2, E = 1 / 255): with M
+ * = 4 a pixel whose first four passes agree stops at once. profiles/converge/README.md has the records. Other scenes,
+ * depths and motions: not measured. */
+/* Device pointers; `accum`, `accum2`: width * height * 3 doubles, `count`: width * height uint32, all required; each
+ * output and `active` nullable. */
+int rt_render_converge_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width, int height,
+                           int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
+                           double tolerance, double aperture, double light_size, double shutter, double* accum,
+                           double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                           uint32_t* raycount2, uint32_t* active, void* stream);
+/* Synchronous host-buffer convenience, as rt_render_accum: rt_set_scene(scene), rt_set_motion(displacement,
+ * scene->n_spheres) (NULL: no motion), then the passes.  `accum`, `accum2` and `count` are host arrays, read and written
+ * on success.  *n_active (nullable): what `active` holds.  *stats as rt_render_accum, over the passes this call traced:
+ * its primary rays are S S times the growth of the sum of `count`. */
+int rt_render_converge(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                       const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
+                       uint32_t seed, int passes, uint32_t min_passes, double tolerance, double aperture,
+                       double light_size, double shutter, double* accum, double* accum2, uint32_t* count,
+                       float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats, uint64_t* n_active);
 
 /* ---- packed pixel formats (ABI 5)--------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

@@ -226,6 +226,14 @@ SIGNATURES = {
     "rt_render_accum": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion), c_int, c_int,
                                 c_int, c_int, c_int, ctypes.c_uint32, ctypes.c_uint32, c_int, c_double, c_double,
                                 c_double, c_void_p, c_void_p, c_void_p, c_void_p, _P(rt_stats)]),
+    "rt_render_converge_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int, c_int, c_int, c_int,
+                                       ctypes.c_uint32, c_int, ctypes.c_uint32, c_double, c_double, c_double, c_double,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "rt_render_converge": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion), c_int,
+                                   c_int, c_int, c_int, c_int, ctypes.c_uint32, c_int, ctypes.c_uint32, c_double,
+                                   c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, _P(rt_stats), _P(c_uint64)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

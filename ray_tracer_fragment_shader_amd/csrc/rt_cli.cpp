@@ -56,6 +56,10 @@
 //             [--aperture 8] [--light-size 40] --out c2_accum.ppm
 //                                                  64 jittered passes with the seeds 7 .. 70 summed in the kernel; the
 //                                                  image is their mean (rt_render_accum; K in 1 .. 65536)
+//   ... --passes 64 --tolerance 0.004 [--min-passes 4]
+//                                                  64 is a budget: a pixel stops receiving passes once it has 4 and the
+//                                                  standard error of its mean is at most 0.004 in every channel
+//                                                  (rt_render_converge; M in 2 .. 2^31, default 4)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -101,6 +105,9 @@ struct Options {
     bool camera_motion = false;              // --eye-move / --look-move DX,DY,DZ: rt_render_shutter (needs --shutter)
     rt_camera_motion camera_move = {};
     int passes = 0;                          // --passes K: rt_render_accum, K passes from --seed on (needs --jitter)
+    bool converge = false;                   // --tolerance E: rt_render_converge with the budget --passes (needs it)
+    double tolerance = 0.0;
+    long long min_passes = 0;                // --min-passes M (needs --tolerance; default 4)
     std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -279,10 +286,12 @@ int main(int argc, char** argv) {
         else if (a == "--refine") { o.refine = true; o.refine_t = std::atoi(next().c_str()); }
         else if (a == "--jitter") { o.jitter = std::atoi(next().c_str()); if (o.jitter == 0) o.jitter = -1; }
         else if (a == "--passes") { o.passes = std::atoi(next().c_str()); if (o.passes == 0) o.passes = -1; }
+        else if (a == "--tolerance") { o.converge = true; o.tolerance = number_arg(a, next()); }
+        else if (a == "--min-passes") { o.min_passes = std::atoll(next().c_str()); if (o.min_passes == 0) o.min_passes = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K [--tolerance E [--min-passes M]]]] "
                                     "[--eye-move DX,DY,DZ] [--look-move DX,DY,DZ]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
@@ -348,6 +357,22 @@ int main(int argc, char** argv) {
     }
     if (o.passes != 0 && (o.passes < 1 || o.passes > 65536)) {
         std::fprintf(stderr, "rt_render: --passes must lie in 1 .. 65536\n");
+        return 2;
+    }
+    if (o.converge && o.passes == 0) {
+        std::fprintf(stderr, "rt_render: --tolerance needs --passes\n");
+        return 2;
+    }
+    if (o.converge && !(o.tolerance >= 0.0)) {
+        std::fprintf(stderr, "rt_render: --tolerance must be >= 0\n");
+        return 2;
+    }
+    if (o.min_passes != 0 && !o.converge) {
+        std::fprintf(stderr, "rt_render: --min-passes needs --tolerance\n");
+        return 2;
+    }
+    if (o.min_passes != 0 && (o.min_passes < 2 || o.min_passes > (1ll << 31))) {
+        std::fprintf(stderr, "rt_render: --min-passes must lie in 2 .. 2147483648\n");
         return 2;
     }
     if ((o.coarse != 0) != o.refine) {
@@ -474,6 +499,10 @@ int main(int argc, char** argv) {
     check(rt_ctx_create(o.device, &ctx), "rt_ctx_create");
     std::vector<uint8_t> rgba8((size_t)W * H * 4);
     std::vector<double> accum(o.passes != 0 ? (size_t)W * H * 3 : 0);
+    std::vector<double> accum2(o.converge ? (size_t)W * H * 3 : 0);
+    std::vector<uint32_t> count(o.converge ? (size_t)W * H : 0);
+    const uint32_t min_passes = o.min_passes != 0 ? (uint32_t)o.min_passes : 4u;
+    uint64_t n_active = 0;
     if (o.faithful >= 0) {
         uint64_t calls = 0;
         std::vector<uint8_t> ns((size_t)W * H);
@@ -500,7 +529,14 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
-        else if (o.passes != 0)
+        else if (o.converge) {
+            std::fill(count.begin(), count.end(), 0u);      // every repeat is a new sum
+            check(rt_render_converge(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                     o.camera_motion ? &o.camera_move : nullptr, W, H, depth, o.samples, o.jitter,
+                                     (uint32_t)o.seed, o.passes, min_passes, o.tolerance, o.aperture, o.light_size,
+                                     o.shutter, accum.data(), accum2.data(), count.data(), nullptr, rgba8.data(), nullptr,
+                                     &st, &n_active), "rt_render_converge");
+        } else if (o.passes != 0)
             check(rt_render_accum(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
                                   o.camera_motion ? &o.camera_move : nullptr, W, H, depth, o.samples, o.jitter,
                                   (uint32_t)o.seed, 0u, o.passes, o.aperture, o.light_size, o.shutter, accum.data(),
@@ -540,7 +576,14 @@ int main(int argc, char** argv) {
                 W, H, depth, o.out.c_str(), (unsigned long long)rays, (unsigned long long)st.primary_rays,
                 (unsigned long long)st.reflect_rays, (unsigned long long)st.shadow_rays, st.kernel_ms,
                 rays / (st.kernel_ms * 1e3));
-    if (o.passes != 0)
+    if (o.converge) {
+        unsigned long long traced = 0;
+        for (uint32_t n : count) traced += n;
+        std::printf("rt_render: converged, a budget of %d passes from seed %u, tolerance %g, at least %u passes: %llu of "
+                    "%llu pixels still active, %llu of %llu pixel-passes traced, %llu primary rays\n", o.passes, o.seed,
+                    o.tolerance, min_passes, (unsigned long long)n_active, (unsigned long long)W * H, traced,
+                    (unsigned long long)W * H * (unsigned long long)o.passes, (unsigned long long)st.primary_rays);
+    } else if (o.passes != 0)
         std::printf("rt_render: accumulated, %d passes with the seeds %u .. %u: the mean of %d x %d x %d samples per "
                     "pixel, %llu primary rays\n", o.passes, o.seed, (unsigned)(o.seed + (unsigned)o.passes - 1u), o.passes,
                     o.samples, o.samples, (unsigned long long)st.primary_rays);

@@ -254,9 +254,11 @@ struct rt_ctx {
         uint64_t ticket = 0;                   // rt_render_packed_async frames queued so far
         int last_copy_mode = -1;               // the mode the last packed frame took (rt_diag_copy_path)
         // rt_render's device buffers (grow-only, reused across calls): rgba32f, rgba8, rgb64f, raycount, sums,
-        // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace, and rt_render_accum's sums
+        // packed slot 0, packed slot 1; then rt_render_adaptive's refined mask and workspace, rt_render_accum's sums, and
+        // rt_render_converge's sums of squares, pass counts and active word (its sums are rt_render_accum's buffer)
         static constexpr int kBufRefined = 5 + kSlots, kBufAdaptive = 6 + kSlots, kBufAccum = 7 + kSlots;
-        static constexpr int kBufs = 8 + kSlots;
+        static constexpr int kBufAccum2 = 8 + kSlots, kBufCount = 9 + kSlots, kBufActive = 10 + kSlots;
+        static constexpr int kBufs = 11 + kSlots;
         void* d_out[kBufs] = {};
         size_t out_cap[kBufs] = {};
     } frames;
@@ -333,6 +335,13 @@ int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_
                      int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
                      double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
                      uint32_t* raycount2, void* stream);
+// The checks on the converging render's own arguments and its device render, as `who` (rt_frames.hip's host entry point too).
+int converge_arg_checks(const char* who, int passes, uint32_t min_passes, double tolerance);
+int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                        int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
+                        double tolerance, double aperture, double light_size, double shutter, double* accum,
+                        double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                        uint32_t* raycount2, uint32_t* active, void* stream);
 
 // rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after
 // the context's streams have drained).

@@ -428,6 +428,54 @@ extern "C" int rt_render_accum(rt_ctx* c, const rt_scene* scene, const double* d
         });
 }
 
+// rt_render for converging passes: rt_render_accum's steps with converge_render_dev (as rt_render_converge_dev) on
+// device copies of the three state arrays, all uploaded first (a pixel's `count` says whether its sums are read) and
+// copied back after the render.  The pass counts before the call are kept on the host, so that the primary rays behind
+// *stats are those of the pixel-passes this call traced for the pixels that received them.
+extern "C" int rt_render_converge(rt_ctx* c, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                                  const rt_camera_motion* motion, int W, int H, int depth, int samples, int jitter,
+                                  uint32_t seed, int passes, uint32_t min_passes, double tolerance, double aperture,
+                                  double light_size, double shutter, double* accum, double* accum2, uint32_t* count,
+                                  float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats, uint64_t* n_active) {
+    const char* who = "rt_render_converge";
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc || (rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
+    if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
+    if ((rc = converge_arg_checks(who, passes, min_passes, tolerance))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const size_t npx = (size_t)W * H;
+    uint64_t before = 0;                                    // the pixel-passes the state holds
+    for (size_t k = 0; k < npx; ++k) before += count[k];
+    ExtraBuf x[4] = {{rt_ctx::Frames::kBufAccum, npx * 24, accum, nullptr},
+                     {rt_ctx::Frames::kBufAccum2, npx * 24, accum2, nullptr},
+                     {rt_ctx::Frames::kBufCount, npx * 4, count, nullptr},
+                     {rt_ctx::Frames::kBufActive, 4, nullptr, nullptr}};
+    return host_render(
+        c, npx, 2, rgba32f, rgba8, rgb64f, stats, x, 4,
+        [&](void* const* d) {
+            RT_HIP(hipMemcpyAsync(x[0].dev, accum, npx * 24, hipMemcpyHostToDevice, c->frames.rs));
+            RT_HIP(hipMemcpyAsync(x[1].dev, accum2, npx * 24, hipMemcpyHostToDevice, c->frames.rs));
+            RT_HIP(hipMemcpyAsync(x[2].dev, count, npx * 4, hipMemcpyHostToDevice, c->frames.rs));
+            return converge_render_dev("rt_render_converge_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                                       passes, min_passes, tolerance, aperture, light_size, shutter, (double*)x[0].dev,
+                                       (double*)x[1].dev, (uint32_t*)x[2].dev, (float*)d[0], (uint8_t*)d[1],
+                                       (double*)d[2], (uint32_t*)d[3], (uint32_t*)x[3].dev, c->frames.rs);
+        },
+        [&](uint64_t* prim) {
+            uint32_t n = 0;
+            RT_HIP(hipMemcpy(&n, x[3].dev, sizeof(n), hipMemcpyDeviceToHost));
+            if (n_active) *n_active = n;
+            uint64_t after = 0;                             // (the copies back are done: host_render synchronised)
+            for (size_t k = 0; k < npx; ++k) after += count[k];
+            *prim = (after - before) * (uint64_t)samples * (uint64_t)samples;
+            return RT_OK;
+        });
+}
+
 // rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
 // rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
 // back.

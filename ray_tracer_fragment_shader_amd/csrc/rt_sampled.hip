@@ -410,6 +410,71 @@ extern "C" int rt_render_accum_dev(rt_ctx* c, const rt_camera* cam, const rt_cam
                             aperture, light_size, shutter, accum, rgba32f, rgba8, rgb64f, raycount2, stream);
 }
 
+// ---- converging accumulation (include/rt_api.h) ------------------------------------------------------------------------
+// Up to `passes` passes per pixel, each pixel on the pass number of its own `count`, by rt_converge_kernel: the shutter
+// render's checks and launch record, the call's own checks, the reset of `active` (a memset on `stream`: a node of the
+// call under capture), then launches of at most L = Knobs::accum_max_passes passes each.  A launch loads the state and
+// stores it, so a later launch continues every pixel where the launch before it left it, stopped pixels included (the
+// rule is evaluated before every pass from the state alone): the split is invisible in the bytes.  Every launch adds its
+// passes' counters to raycount2 (the call's first launch starts them at zero); only the last one gets the image
+// pointers and `active`.  Nothing per view, no field of the context written, no allocation, no shortcut for any
+// argument; with no output at all the state is still advanced.
+int converge_arg_checks(const char* who, int passes, uint32_t min_passes, double tolerance) {
+    if (passes < 1 || passes > kAccumCallPasses)
+        return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
+    if (min_passes < 2 || min_passes > (1u << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": min_passes must lie in 2 .. 2^31");
+    if (!(tolerance >= 0.0) || !std::isfinite(tolerance))
+        return rt_fail(RT_EINVAL, std::string(who) + ": tolerance must be finite and not negative");
+    return RT_OK;
+}
+
+int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                        int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
+                        double tolerance, double aperture, double light_size, double shutter, double* accum,
+                        double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                        uint32_t* raycount2, uint32_t* active, void* stream) {
+    SampledLaunch L{};
+    int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
+                            rgba32f, rgba8, rgb64f, raycount2, stream, &L);
+    if (rc) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
+    if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
+    if ((rc = converge_arg_checks(who, passes, min_passes, tolerance))) return rc;
+    RT_HIP(hipSetDevice(c->device));
+    if (active) RT_HIP(hipMemsetAsync(active, 0, sizeof(uint32_t), L.stream));
+    L.accum = accum;
+    L.accum2 = accum2;
+    L.npasses = count;
+    L.min_passes = min_passes;
+    L.tolerance = tolerance;
+    const uint32_t end = (uint32_t)passes, step = (uint32_t)c->knobs.accum_max_passes;
+    for (uint32_t p = 0; p < end; p += step) {
+        L.passes = std::min(step, end - p);
+        L.later = p > 0;
+        L.last = p + L.passes == end;
+        L.o32 = L.last ? rgba32f : nullptr;
+        L.o8 = L.last ? rgba8 : nullptr;
+        L.o64 = L.last ? rgb64f : nullptr;
+        L.active = L.last ? active : nullptr;
+        const hipError_t e = with_depth(depth, [&](auto B) { return launch_converge<decltype(B)::value>(L); });
+        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_converge_kernel: ") + hipGetErrorString(e));
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_render_converge_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                      int depth, int samples, int jitter, uint32_t seed, int passes,
+                                      uint32_t min_passes, double tolerance, double aperture, double light_size,
+                                      double shutter, double* accum, double* accum2, uint32_t* count, float* rgba32f,
+                                      uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, uint32_t* active,
+                                      void* stream) {
+    return converge_render_dev("rt_render_converge_dev", c, cam, motion, W, H, depth, samples, jitter, seed, passes,
+                               min_passes, tolerance, aperture, light_size, shutter, accum, accum2, count, rgba32f, rgba8,
+                               rgb64f, raycount2, active, stream);
+}
+
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------
 // Three passes on `stream`, all of the motion kind: rt_lens_coarse_kernel on the samples_lo grid straight into the
 // caller's outputs (the RGBA8 image into the workspace when the caller has none) with each pixel's spread byte,

@@ -15,6 +15,8 @@
 //                                      of each sample's own time, its basis formed per lane.
 //   rt_accum_kernel<B, TRANSP, TREE>   progressive accumulation (rt_render_accum_dev): the shutter kind's frames of
 //                                      consecutive seeds, summed per pixel in a fixed order by the wave that owns it.
+//   rt_converge_kernel<B, TRANSP, TREE> converging accumulation (rt_render_converge_dev): that sum with a sum of
+//                                      squares and a pass count per pixel; a pixel stops once its standard error is low.
 // All take RenderParams P of the SAMPLE grid (camera rt_camera_supersample, width = S x the output's, ss_log2 set) and
 // share the sample-grid contract with render_body's supersampled instances through the helpers of rt_render.hpp:
 // screen_point forms a sample's ray end, reduce_samples is the contract's fixed pairwise tree, store_sampled writes
@@ -25,7 +27,7 @@
 // The instances are compiled once per bounce depth, in parallel with the render kernels' translation units:
 // rt_adaptive.hip (rt_adaptive_b<B>.o), once per depth and kind rt_lens.hip (rt_lens_k<kind>_b<B>.o), and
 // rt_lens_adaptive.hip (rt_lens_adaptive_b<B>.o), rt_jitter.hip (rt_jitter_b<B>.o), rt_shutter.hip
-// (rt_shutter_b<B>.o) and rt_accum.hip (rt_accum_b<B>.o).
+// (rt_shutter_b<B>.o), rt_accum.hip (rt_accum_b<B>.o) and rt_converge.hip (rt_converge_b<B>.o).
 #pragma once
 
 #include "rt_jitter.hpp"
@@ -512,6 +514,188 @@ __global__ __launch_bounds__(64) void rt_accum_kernel(const DevScene* __restrict
     }
 }
 
+// ---- Converging accumulation (rt_render_converge_dev, include/rt_api.h): rt_accum_kernel's sum with a sum of squares
+// and a pass count per pixel, and a pixel that stops receiving passes once its standard error is low. ----
+
+// What the converging kernel gets beside the shutter kernel's arguments: the most passes a pixel receives in this
+// launch, the rule's M and E, whether the launch is not the first of its call (then the counters continue from the
+// words the launch before it left) and whether it is the last (then it writes the images and counts `active`).
+struct ConvergeParams {
+    double tolerance;
+    uint32_t count;
+    uint32_t min_passes;
+    uint32_t later;
+    uint32_t last;
+};
+
+// Rule 3 of the contract: one IEEE operation per operator, in this order (-ffp-contract=off: nothing fuses).  n = 0 is
+// never stopped (M >= 2); a NaN d compares false and does not hold the pixel back.
+__device__ __forceinline__ bool converge_stopped(d3 acc, d3 sq, uint32_t n, uint32_t min_passes, double tol) {
+    if (n == 0x80000000u) return true;
+    if (n < min_passes) return false;
+    const double dn = (double)n;
+    const double lim = (tol * tol) * (dn * (double)(n - 1u));
+    const double dx = sq.x - (acc.x * acc.x) / dn, dy = sq.y - (acc.y * acc.y) / dn, dz = sq.z - (acc.z * acc.z) / dn;
+    return !(dx > lim) && !(dy > lim) && !(dz > lim);
+}
+
+// rt_accum_kernel's wave layout, clamping, key, lane_of and pass body, with every pixel on a pass number of its own: the
+// state (acc, sq, n) of a pixel waits in LDS behind trace()'s slots (converge_park_bytes: 60 bytes per output pixel of
+// the tile), written by the pixel's first lane alone and, n, read by all S S lanes of the pixel, whose seed is
+// Q.seed + n (uint32, wrapping): a per-lane value.  Before every pass the first lane of each pixel evaluates rule 3 on the
+// parked state and one __ballot over these lanes gives `live`, the wave's pixels that receive this pass, in a scalar
+// pair: live = 0 ends the loop (wave-uniform), so a wave whose pixels had all stopped before the launch traces nothing.
+// In a live wave the lanes of a stopped pixel trace the pixel's would-be next pass (a valid ray: seed Q.seed + n) and
+// discard it, as pad lanes do; that is sound because a lane's value does not depend on the other lanes' rays —
+// trace() reduces over the wave for its loop conditions only, which the refine kernels (rt_refine_kernel,
+// rt_lens_refine_kernel) already rely on — and reduce_samples never crosses a pixel's S x S block.  After the reduction
+// the first lane of a pixel in `live` does rule 2: acc = v, sq = v * v for n = 0, else acc = acc + v, sq = sq + (v * v),
+// one multiplication then one addition (not fused), from the PARKED values; n = n + 1; the pass's counters are added.
+// Stores: `accum`, `accum2` and `count` once after the loop, by a wave that ran a pass (the others hold what is
+// there); the counters in every launch; the images from m = acc / (double)n in the call's last launch, which also adds
+// the wave's pixels that are not stopped to *active: a ballot popcount and one vector atomic per wave.
+// LDS: 60 instead of rt_accum_kernel's 32 bytes per pixel is 3840 B per wave at S = 1 (960, 240, 60 B at S = 2, 4, 8);
+// profiles/converge/README.md has what that costs in workgroups per CU and why sq is not kept in `accum2`.
+// A kernel of its own, not a flag of rt_accum_kernel: that one's parameter list, hence its instances' code, stays what
+// it was.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_converge_kernel(const DevScene* __restrict__ S, const DevMotion* __restrict__ M,
+                                                         RenderParams P, JitterParams Q, ShutterParams C,
+                                                         ConvergeParams N, double aperture, double light_size,
+                                                         double shutter, int tile_rows, double* accum, double* accum2,
+                                                         uint32_t* count, uint32_t* active, void* o32, void* o8,
+                                                         double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl, sj = s + jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const int tx = blockIdx.x, ty_raw = (int)(blockIdx.z * kDofGridY + blockIdx.y);
+    const bool pad = ty_raw >= tile_rows;
+    const int ty = pad ? tile_rows - 1 : ty_raw;
+    // (rt_accum_kernel: the lane's coordinates are formed again wherever they are read)
+    struct Lane { int i, lr, a, b, q; bool first, owner; size_t k; };
+    const auto lane_of = [&]() {
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        const int x = l & 7, y = l >> 3;
+        Lane r;
+        r.i = tx * 8 + x;
+        r.lr = ty * 8 + y;
+        r.a = x & S1;
+        r.b = y & S1;
+        r.q = ((y >> s) << (3 - s)) + (x >> s);          // the pixel's number in the tile
+        r.first = r.a == 0 && r.b == 0;
+        r.owner = r.first && r.i < P.width && r.lr < P.height && !pad;
+        r.k = (size_t)(r.lr >> s) * (size_t)(P.width >> s) + (size_t)(r.i >> s);      // read under `owner` only
+        return r;
+    };
+    const int npix = 64 >> (2 * s);
+    double* park_rgb = reinterpret_cast<double*>(smem + (TREE ? 0 : slot_bytes(B, TRANSP, 64)));
+    double* park_sq = park_rgb + 3 * npix;
+    uint32_t* park_rc = reinterpret_cast<uint32_t*>(park_sq + 3 * npix);
+    uint32_t* park_n = park_rc + 2 * npix;
+    const auto parked = [&](const double* p, int q) { return mk(p[q], p[npix + q], p[2 * npix + q]); };
+    const auto park = [&](double* p, int q, d3 v) { p[q] = v.x; p[npix + q] = v.y; p[2 * npix + q] = v.z; };
+    {
+        // every pixel slot of the tile is filled: a slot outside the frame holds n = 0 and is never live
+        const Lane ln = lane_of();
+        if (ln.first) {
+            d3 acc = mk(0.0, 0.0, 0.0), sq = mk(0.0, 0.0, 0.0);
+            uint32_t n = 0, seg_sum = 0, sh_sum = 0;
+            if (ln.owner) {
+                n = count[ln.k];
+                if (n > 0) {                                // n = 0: accum and accum2 are not read
+                    acc = mk(accum[3 * ln.k], accum[3 * ln.k + 1], accum[3 * ln.k + 2]);
+                    sq = mk(accum2[3 * ln.k], accum2[3 * ln.k + 1], accum2[3 * ln.k + 2]);
+                }
+                if (N.later && orc2) { seg_sum = orc2[2 * ln.k]; sh_sum = orc2[2 * ln.k + 1]; }
+            }
+            park(park_rgb, ln.q, acc);
+            park(park_sq, ln.q, sq);
+            park_rc[ln.q] = seg_sum; park_rc[npix + ln.q] = sh_sum;
+            park_n[ln.q] = n;
+        }
+    }
+    bool ran = false;
+    for (uint32_t t = 0; t < N.count; ++t) {
+        // what the wave's first lanes parked, before the loop or in the pass before, is read by every lane below
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const Lane ln = lane_of();
+        const uint32_t n_px = park_n[ln.q];
+        const bool go = ln.owner && !converge_stopped(parked(park_rgb, ln.q), parked(park_sq, ln.q), n_px, N.min_passes,
+                                                      N.tolerance);
+        const uint64_t live = __ballot(go);
+        if (live == 0) break;
+        ran = true;
+        const int i = ln.i, lr = ln.lr, a = ln.a, b = ln.b;
+        const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+        const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed + n_px);
+        const int n = a + (b << s);                         // time index a + S b
+        const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                        ldexp(1.0, -(s + sj)));
+        // the camera of the lane's time
+        const d3 eye = add(ld3(P.eye), scl(sigma, ld3(C.eye_move)));
+        const d3 look = add(ld3(P.look), scl(sigma, ld3(C.look_move)));
+        const d3 ld = sub(look, eye);
+        const d3 right = cam_normalize(cross(ld, ld3(C.up)));
+        const d3 upp = cam_normalize(cross(right, ld));
+        // screen_point of the fine camera at that time
+        const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+        const d3 sp = add(add(look, scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                          scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+        const double inv_sj = ldexp(1.0, -sj);
+        const auto t_of = [&](int c, int kd) { return (double)(2 * ((c << jl) + kd) + 1 - (1 << sj)) * inv_sj; };
+        const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+        const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+        const d3 e = add(add(eye, scl(aperture * ta, right)), scl(aperture * tb, upp));
+        const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+        V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+        const Motion mo{sigma, M};
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                                LightShift{light_size * ga, light_size * gb}, &mo);
+        reduce_samples(s, 8, col, seg, sh);
+        const Lane after = lane_of();
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        if (after.owner && ((live >> l) & 1ull)) {          // nothing of a stopped pixel's ray reaches the state
+            const int q = after.q;
+            const uint32_t np = park_n[q];
+            const d3 v2 = mk(col.x * col.x, col.y * col.y, col.z * col.z);
+            const d3 acc = np == 0 ? col : add(parked(park_rgb, q), col);
+            const d3 sq = np == 0 ? v2 : add(parked(park_sq, q), v2);
+            park(park_rgb, q, acc);
+            park(park_sq, q, sq);
+            park_rc[q] += seg;
+            park_rc[npix + q] += sh;
+            park_n[q] = np + 1u;
+        }
+    }
+    const Lane ln = lane_of();
+    bool open = false;                                      // the pixel is not stopped on its final state
+    if (ln.owner) {
+        const size_t k = ln.k;
+        const int q = ln.q;
+        const d3 acc = parked(park_rgb, q), sq = parked(park_sq, q);
+        const uint32_t n = park_n[q], seg_sum = park_rc[q], sh_sum = park_rc[npix + q];
+        if (ran) {
+            accum[3 * k] = acc.x; accum[3 * k + 1] = acc.y; accum[3 * k + 2] = acc.z;
+            accum2[3 * k] = sq.x; accum2[3 * k + 1] = sq.y; accum2[3 * k + 2] = sq.z;
+            count[k] = n;
+        }
+        if (N.last) {
+            const double cnt = (double)n;
+            store_sampled(P, k, mk(acc.x / cnt, acc.y / cnt, acc.z / cnt), seg_sum, sh_sum, o32, o8, o64, orc2);
+            open = !converge_stopped(acc, sq, n, N.min_passes, N.tolerance);
+        } else if (orc2) {
+            orc2[2 * k] = seg_sum; orc2[2 * k + 1] = sh_sum;
+        }
+    }
+    if (N.last && active) {
+        const uint64_t still = __ballot(open);
+        if (still != 0 && threadIdx.x == 0) atomicAdd(active, (uint32_t)__popcll(still));
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -538,12 +722,19 @@ struct SampledLaunch {
     // rt_accum_kernel: the launch's passes are first_pass .. first_pass + passes - 1 of the call that began at call_first
     uint32_t first_pass, passes, call_first;
     double* accum;                             // the running sums, 3 doubles per output pixel
+    // rt_converge_kernel: at most `passes` passes per pixel; `later`: not the call's first launch, `last`: its last
+    double* accum2;                            // the sums of squares, 3 doubles per output pixel
+    uint32_t* npasses;                         // the pass counts, one word per output pixel
+    uint32_t* active;                          // nullable: the pixels not stopped after the call
+    uint32_t min_passes;
+    double tolerance;
+    bool later, last;
 };
 
 // Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
 // the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), the jittered render's in
 // rt_jitter_b<B>.o (rt_jitter.hip), the shutter render's in rt_shutter_b<B>.o (rt_shutter.hip) and the accumulating
-// render's in rt_accum_b<B>.o (rt_accum.hip).
+// render's in rt_accum_b<B>.o (rt_accum.hip); the converging render's in rt_converge_b<B>.o (rt_converge.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
@@ -556,6 +747,8 @@ template <int B>
 hipError_t launch_shutter(const SampledLaunch& L);
 template <int B>
 hipError_t launch_accum(const SampledLaunch& L);
+template <int B>
+hipError_t launch_converge(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
@@ -571,6 +764,8 @@ hipError_t launch_lens(const SampledLaunch& L);
     hipError_t launch_shutter<B>(const SampledLaunch& L);             \
     template <>                                                       \
     hipError_t launch_accum<B>(const SampledLaunch& L);               \
+    template <>                                                       \
+    hipError_t launch_converge<B>(const SampledLaunch& L);            \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -676,6 +871,23 @@ hipError_t launch_accum_impl(const SampledLaunch& L) {
         hipLaunchKernelGGL((rt_accum_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64),
                            lds + accum_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera, n, L.aperture, L.light_size, L.shutter,
                            tile_rows, L.accum, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+// LDS of rt_converge_kernel's parked state behind trace()'s slots: 6 doubles, 2 counters and the pass count per output
+// pixel of a tile.
+inline size_t converge_park_bytes(int ss_log2) { return (size_t)(64 >> (2 * ss_log2)) * (6 * 8 + 3 * 4); }
+
+template <int B>
+hipError_t launch_converge_impl(const SampledLaunch& L) {
+    int tile_rows;
+    const dim3 g = lens_grid(L.P, &tile_rows);
+    const ConvergeParams n{L.tolerance, L.passes, L.min_passes, L.later ? 1u : 0u, L.last ? 1u : 0u};
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_converge_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64),
+                           lds + converge_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera,
+                           n, L.aperture, L.light_size, L.shutter, tile_rows, L.accum, L.accum2, L.npasses, L.active,
+                           L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

@@ -292,6 +292,55 @@ class Tracer:
                                light_size, shutter, accum, bufs, stream)
         return bufs, accum
 
+    # ---------------------------------------------------------------------------- converging accumulation
+    def alloc_converge(self, width: int, height: int):
+        """The state of render_converge_into(): (accum, accum2, count) — two (H, W, 3) float64 tensors, uninitialised
+        (a pixel with count 0 does not read them), and a zeroed (H, W) int32 tensor holding uint32 pass counts."""
+        dev = torch.device("cuda", self.device)
+        return (torch.empty((height, width, 3), dtype=torch.float64, device=dev),
+                torch.empty((height, width, 3), dtype=torch.float64, device=dev),
+                torch.zeros((height, width), dtype=torch.int32, device=dev))
+
+    def render_converge_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int, height: int,
+                             depth: int, samples: int, jitter: int, seed: int, passes: int, min_passes: int,
+                             tolerance: float, aperture: float, light_size: float, shutter: float, state, bufs: dict,
+                             active: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_converge_dev: up to `passes` more passes per pixel of the sum render_accum_into() forms, each pixel
+        continuing from its own count in `state` (alloc_converge()) and stopping once it has `min_passes` passes and
+        the estimated standard error of its mean is at most `tolerance` in every channel; the mean of every pixel's
+        passes written into alloc_ss() buffers (`raycount`: the sums of this call's passes) and the number of pixels
+        not yet stopped into `active` (a one-element int32 tensor, or None).  Asynchronous on `stream` (default:
+        torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        accum, accum2, count = state
+        for t, name in ((accum, "accum"), (accum2, "accum2")):
+            if t is None or t.dtype != torch.float64 or t.numel() != width * height * 3:
+                raise ValueError(f"{name} must be a float64 tensor of width * height * 3 elements (alloc_converge)")
+        if count is None or count.dtype != torch.int32 or count.numel() != width * height:
+            raise ValueError("count must be an int32 tensor of width * height elements (alloc_converge)")
+        if active is not None and (active.dtype != torch.int32 or active.numel() != 1):
+            raise ValueError("active must be a one-element int32 tensor")
+        abi.check(abi.lib().rt_render_converge_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height, depth,
+            samples, jitter, int(seed) & 0xFFFFFFFF, int(passes), int(min_passes) & 0xFFFFFFFF, float(tolerance),
+            float(aperture), float(light_size), float(shutter), _ptr(accum), _ptr(accum2), _ptr(count),
+            _ptr(bufs.get("rgba32f")), _ptr(bufs.get("rgba8")), _ptr(bufs.get("rgb64f")), _ptr(bufs.get("raycount")),
+            _ptr(active), ctypes.c_void_p(st.cuda_stream)), "rt_render_converge_dev")
+        return bufs
+
+    def render_converge(self, cam, motion, width, height, depth, samples, jitter, seed, passes, min_passes, tolerance,
+                        aperture, light_size, shutter, state=None, rgba32f=True, rgba8=False, rgb64f=False,
+                        raycount=False, stream=None):
+        """-> (the buffers of alloc_ss(), the state, the active count as a one-element device tensor): `state`
+        continued, or a new one when it is None."""
+        if state is None:
+            state = self.alloc_converge(width, height)
+        bufs = self.alloc_ss(width, height, None, rgba32f, rgba8, rgb64f, raycount)
+        active = torch.zeros((1,), dtype=torch.int32, device=torch.device("cuda", self.device))
+        self.render_converge_into(cam, motion, width, height, depth, samples, jitter, seed, passes, min_passes,
+                                  tolerance, aperture, light_size, shutter, state, bufs, active, stream)
+        return bufs, state, active
+
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
     def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
                             refined=True):
