@@ -653,8 +653,8 @@ int rt_render_shutter(rt_ctx* ctx, const rt_scene* scene, const double* displace
  *     says otherwise.  Rule 2 makes the split invisible: the images are the same bytes under every value.
  *  6. RT_EINVAL (rt_last_error names the argument), with no byte of `accum` or of any image written, for every check of
  *     rt_render_shutter_dev, a null `accum`, `passes` < 1 or above 65536, and `first_pass + passes` above 2^31.
- *  7. Not offered: accumulation for rt_render_lens_adaptive_dev; row bands; the
- *     packed and multi-GPU paths; weights other than 1.  Jitter is quantised, so the mean converges to the regular grid
+ *  7. Not offered: accumulation for rt_render_lens_adaptive_dev; rt_rows (a rectangle of the frame, and with it a
+ *     split over GPUs or tiles, is rt_render_accum_window_dev below); the packed and group paths; weights other than 1.  Jitter is quantised, so the mean converges to the regular grid
  *     S J times finer per dimension, not to the continuous integral.  A per-pixel variance and stopping rule is a call
  *     of its own: rt_render_converge_dev (below), which sums in this call's order.
  * Measured (MI355X, c2 1920 x 1080 output, depth 1, R = 40, one sphere moving by |d| = 40, F = 1, A = 0, crane of
@@ -727,7 +727,8 @@ int rt_render_accum(rt_ctx* ctx, const rt_scene* scene, const double* displaceme
  *     null `accum`, `accum2` or `count`, `passes` outside 1 .. 65536, `min_passes` outside 2 .. 2^31, and a `tolerance`
  *     that is negative, NaN or infinite.
  *  8. Not offered: a relative or perceptual tolerance; a tolerance per channel; compaction of the live tiles into a
- *     work list; a stopping rule in rt_render_lens_adaptive_dev; row bands; the packed and multi-GPU paths.
+ *     work list; a stopping rule in rt_render_lens_adaptive_dev; rt_rows (a rectangle of the frame is
+ *     rt_render_converge_window_dev below); the packed and group paths.
  * One wave keeps its 8 x 8 tile of the sample grid for the whole launch, as in rt_render_accum_dev, and leaves its pass
  * loop as soon as all of its pixels have stopped; a wave whose pixels had all stopped before the launch traces nothing.
  * The lanes of a stopped pixel in a live wave trace and discard.
@@ -759,6 +760,83 @@ int rt_render_converge(rt_ctx* ctx, const rt_scene* scene, const double* displac
                        uint32_t seed, int passes, uint32_t min_passes, double tolerance, double aperture,
                        double light_size, double shutter, double* accum, double* accum2, uint32_t* count,
                        float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats, uint64_t* n_active);
+
+/* ---- windows of the accumulating and converging renders (ABI 10: new symbols only) ------------------------------- */
+/* rt_render_accum_dev and rt_render_converge_dev render whole frames, and a camera shifted to a region does not give
+ * the region's bytes under jitter: the sample key is Jr (S width) + I in the coordinates of the frame being rendered.
+ * The window calls render one rectangle of the width x height frame with the frame's own bytes — what a rank of a
+ * multi-GPU split or a tile of a frame whose FP64 state does not fit at once owns, or the region a viewer refines.
+ * Every argument is as for the un-windowed call; `win` says which pixels, and how the buffers are laid out. */
+typedef struct rt_window {      /* a rectangle of the width x height output frame, in output pixels, j = 0 at the bottom */
+    int32_t x0, y0;             /* frame pixel of window pixel (0, 0) */
+    int32_t width, height;      /* >= 1; x0 + width <= frame width, y0 + height <= frame height */
+    int32_t stride;             /* >= width: window pixel (i, j) is element j * stride + i of every per-pixel buffer */
+} rt_window;
+/* Every buffer pointer points at window pixel (0, 0).  An element is the buffer's own per-pixel unit: 3 doubles for
+ * `accum`, `accum2` and rgb64f, one uint32 for `count`, 4 floats for rgba32f, 4 bytes for rgba8, 2 uint32 for raycount2;
+ * one stride serves all buffers.  stride = win.width is a dense window; stride = the frame's width with the pointers
+ * offset to the window's origin is a window in place inside full-frame buffers.
+ *  1. Value.  For every window pixel (i, j) the state (`accum`; for converge also `accum2` and `count`), the mean, the
+ *     three images and the counters are exactly what the un-windowed call with the same arguments writes for frame
+ *     pixel (x0 + i, y0 + j).  In particular the sample key is the full frame's: rt_jitter_sample(S width, ...,
+ *     I = S (x0 + i) + a, Jr = S (y0 + j) + b) with the FRAME's width, not the window's.
+ *  2. Nothing else is touched.  Elements outside the window are neither read nor written: the gap between the rows when
+ *     stride > win.width, and everything outside an in-place window.
+ *  3. `active` (converge) holds the number of the WINDOW's pixels that are not stopped on the final state.
+ *  4. Whole-frame pin.  With win = {0, 0, width, height, width} every byte equals the un-windowed call's.  There is no
+ *     shortcut in either direction: the un-windowed entry points run the kernels they always ran, the window calls run
+ *     theirs for every window.  A state written by either call can be continued by the other.
+ *  5. Tiling pin.  Windows that partition the frame, rendered in any order into full-frame buffers (stride = width,
+ *     pointers offset to each window's origin), leave the bytes of one un-windowed call in every buffer, and their
+ *     `active` values sum to its `active`.  The split-call rules hold per window: (0, a) then (a, b) equals (0, a + b);
+ *     the host's launch split (RT_ACCUM_MAX_PASSES) stays invisible; a loosely stopped window resumes under a smaller E.
+ *     One pass from pass 0 on a window is that rectangle of rt_render_shutter_dev's frame, so the window calls give
+ *     windows of every sampled render of the chain.
+ *  6. No alignment rule: any x0, y0, width and height.  Waves tile the window from its own origin, so a wave holds other
+ *     pixels than the full frame's waves do; a lane's value does not depend on the other lanes' rays
+ *     (rt_render_converge_dev), so the bytes are the same.
+ *  7. RT_EINVAL (rt_last_error names `window`), with no byte written, for a null `win`, a negative x0 or y0, a width or
+ *     height below 1, a window that leaves the frame, stride < win.width, and every check of the un-windowed call.
+ *  8. Asynchronous on `stream`, no allocation and no host synchronisation; capturable in a hipGraph, the reset of
+ *     `active` a memset node of the call.  No per-view state.
+ *  9. Not offered: windows of rt_render_lens_adaptive_dev; rt_rows; the packed and group paths; a list of windows in
+ *     one launch.
+ * The kernels are rt_accum_kernel and rt_converge_kernel with the lane's sample formed from the window's sample origin;
+ * the host folds the window into five words and moves the pointers, and every instance keeps its parent's waves per
+ * SIMD (profiles/window/resource_usage.txt).
+ * Measured (MI355X, c2 1920 x 1080 output, depth 1, the scene of rt_render_accum_dev's figures, J = 16, accum (0, 16) and
+ * converge K = 64, M = 4, E = 1 / 255, RGBA32F + RGBA8, tools/bench_window.py, profiles/window/bench_window.json, every
+ * leg's bytes checked equal first; the un-windowed calls in the same run: 0.91 and 3.34 ms at S = 1, 3.53 and 10.56 ms at
+ * S = 2): the whole-frame window takes 1.014 x and 1.005 x (S = 1), 1.011 x and 1.008 x (S = 2) the un-windowed call, above
+ * the spreads at S = 2 only.  The frame as 2 / 4 / 8 strips of whole rows, one call each: 1.17 x / 1.47 x / 1.70 x (accum)
+ * and 1.20 x / 1.60 x / 1.74 x (converge) at S = 1, 1.05 x / 1.14 x / 1.25 x and 1.07 x / 1.20 x / 1.34 x at S = 2; as 4 x 4
+ * tiles 2.57 x, 3.02 x, 1.40 x, 1.71 x: 22 - 47 us of ramp and drain per extra launch.  A 960 x 540 window at (3, 5) is not
+ * slower than one at (8, 8) (0.94 x - 0.99 x).  profiles/window/README.md has the records.  Other scenes, depths and
+ * motions: not measured. */
+int rt_render_accum_window_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width, int height,
+                               const rt_window* win, int depth, int samples, int jitter, uint32_t seed,
+                               uint32_t first_pass, int passes, double aperture, double light_size, double shutter,
+                               double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                               void* stream);
+int rt_render_converge_window_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width,
+                                  int height, const rt_window* win, int depth, int samples, int jitter, uint32_t seed,
+                                  int passes, uint32_t min_passes, double tolerance, double aperture, double light_size,
+                                  double shutter, double* accum, double* accum2, uint32_t* count, float* rgba32f,
+                                  uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, uint32_t* active, void* stream);
+/* Synchronous host-buffer conveniences, as rt_render_accum and rt_render_converge: the host arrays are addressed with
+ * the window's stride as the device buffers are, and only the window's rows move (the state up, everything back).
+ * *n_active and *stats are the window's. */
+int rt_render_accum_window(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                           const rt_camera_motion* motion, int width, int height, const rt_window* win, int depth,
+                           int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
+                           double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8,
+                           double* rgb64f, rt_stats* stats);
+int rt_render_converge_window(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                              const rt_camera_motion* motion, int width, int height, const rt_window* win, int depth,
+                              int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes, double tolerance,
+                              double aperture, double light_size, double shutter, double* accum, double* accum2,
+                              uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats,
+                              uint64_t* n_active);
 
 /* ---- packed pixel formats (ABI 5)--------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

@@ -93,6 +93,11 @@ class rt_camera_motion(Structure):
     _fields_ = [("eye", D3), ("look_at", D3)]
 
 
+class rt_window(Structure):
+    """A rectangle of the output frame and the row stride of its buffers (rt_render_accum_window_dev), output pixels."""
+    _fields_ = [("x0", c_int32), ("y0", c_int32), ("width", c_int32), ("height", c_int32), ("stride", c_int32)]
+
+
 class rt_stats(Structure):
     _fields_ = [("primary_rays", c_uint64), ("reflect_rays", c_uint64), ("shadow_rays", c_uint64),
                 ("kernel_ms", c_double)]
@@ -234,6 +239,23 @@ SIGNATURES = {
                                    c_int, c_int, c_int, c_int, ctypes.c_uint32, c_int, ctypes.c_uint32, c_double,
                                    c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, _P(rt_stats), _P(c_uint64)]),
+    "rt_render_accum_window_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int, _P(rt_window),
+                                           c_int, c_int, c_int, ctypes.c_uint32, ctypes.c_uint32, c_int, c_double,
+                                           c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
+    "rt_render_converge_window_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int,
+                                              _P(rt_window), c_int, c_int, c_int, ctypes.c_uint32, c_int,
+                                              ctypes.c_uint32, c_double, c_double, c_double, c_double, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "rt_render_accum_window": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion), c_int,
+                                       c_int, _P(rt_window), c_int, c_int, c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                       c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       _P(rt_stats)]),
+    "rt_render_converge_window": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion),
+                                          c_int, c_int, _P(rt_window), c_int, c_int, c_int, ctypes.c_uint32, c_int,
+                                          ctypes.c_uint32, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, _P(rt_stats), _P(c_uint64)]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

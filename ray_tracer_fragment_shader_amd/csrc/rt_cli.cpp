@@ -60,6 +60,10 @@
 //                                                  64 is a budget: a pixel stops receiving passes once it has 4 and the
 //                                                  standard error of its mean is at most 0.004 in every channel
 //                                                  (rt_render_converge; M in 2 .. 2^31, default 4)
+//   ... --passes 64 [--tolerance 0.004] --window X,Y,W,H
+//                                                  only the W x H rectangle at (X, Y) of the frame (Y = 0: the bottom row),
+//                                                  with the full frame's bytes; the PPM is W x H
+//                                                  (rt_render_accum_window / rt_render_converge_window)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -108,6 +112,8 @@ struct Options {
     bool converge = false;                   // --tolerance E: rt_render_converge with the budget --passes (needs it)
     double tolerance = 0.0;
     long long min_passes = 0;                // --min-passes M (needs --tolerance; default 4)
+    bool window = false;                     // --window X,Y,W,H: that rectangle of the frame alone (needs --passes)
+    rt_window win{};
     std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -287,11 +293,28 @@ int main(int argc, char** argv) {
         else if (a == "--jitter") { o.jitter = std::atoi(next().c_str()); if (o.jitter == 0) o.jitter = -1; }
         else if (a == "--passes") { o.passes = std::atoi(next().c_str()); if (o.passes == 0) o.passes = -1; }
         else if (a == "--tolerance") { o.converge = true; o.tolerance = number_arg(a, next()); }
+        else if (a == "--window") {
+            const std::string v = next();
+            long long q[4];
+            char tail = 0;
+            if (std::sscanf(v.c_str(), "%lld,%lld,%lld,%lld%c", &q[0], &q[1], &q[2], &q[3], &tail) != 4 ||
+                v.find_first_not_of("0123456789,-") != std::string::npos) {
+                std::fprintf(stderr, "rt_render: --window takes X,Y,W,H (four integers)\n");
+                return 2;
+            }
+            for (long long t : q)
+                if (t < INT32_MIN || t > INT32_MAX) {
+                    std::fprintf(stderr, "rt_render: --window takes X,Y,W,H (four integers)\n");
+                    return 2;
+                }
+            o.window = true;
+            o.win = rt_window{(int32_t)q[0], (int32_t)q[1], (int32_t)q[2], (int32_t)q[3], (int32_t)q[2]};
+        }
         else if (a == "--min-passes") { o.min_passes = std::atoll(next().c_str()); if (o.min_passes == 0) o.min_passes = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K [--tolerance E [--min-passes M]]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K [--tolerance E [--min-passes M]] [--window X,Y,W,H]]] "
                                     "[--eye-move DX,DY,DZ] [--look-move DX,DY,DZ]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
@@ -373,6 +396,10 @@ int main(int argc, char** argv) {
     }
     if (o.min_passes != 0 && (o.min_passes < 2 || o.min_passes > (1ll << 31))) {
         std::fprintf(stderr, "rt_render: --min-passes must lie in 2 .. 2147483648\n");
+        return 2;
+    }
+    if (o.window && o.passes == 0) {
+        std::fprintf(stderr, "rt_render: --window needs --passes\n");
         return 2;
     }
     if ((o.coarse != 0) != o.refine) {
@@ -492,6 +519,14 @@ int main(int argc, char** argv) {
         for (int q = 0; q < 3; ++q) displacement[3 * (size_t)o.move_k[m] + q] = o.move_d[3 * m + q];
     }
 
+    if (o.window && (o.win.x0 < 0 || o.win.y0 < 0 || o.win.width < 1 || o.win.height < 1 ||
+                     (long long)o.win.x0 + o.win.width > W || (long long)o.win.y0 + o.win.height > H)) {
+        std::fprintf(stderr, "rt_render: --window %d,%d,%d,%d is empty or leaves the %d x %d frame\n", o.win.x0, o.win.y0,
+                     o.win.width, o.win.height, W, H);
+        return 2;
+    }
+    // the buffers of a window are dense: OW x OH is the image written
+    const int OW = o.window ? o.win.width : W, OH = o.window ? o.win.height : H;
     rt_camera cam;
     check(rt_camera_init_reference(&cam, W, H, pitch), "rt_camera_init_reference");
     if (o.focus) check(rt_camera_focus(&cam, o.focus_ratio, &cam), "rt_camera_focus");
@@ -529,6 +564,18 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
+        else if (o.converge && o.window) {
+            std::fill(count.begin(), count.end(), 0u);      // every repeat is a new sum
+            check(rt_render_converge_window(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                            o.camera_motion ? &o.camera_move : nullptr, W, H, &o.win, depth, o.samples,
+                                            o.jitter, (uint32_t)o.seed, o.passes, min_passes, o.tolerance, o.aperture,
+                                            o.light_size, o.shutter, accum.data(), accum2.data(), count.data(), nullptr,
+                                            rgba8.data(), nullptr, &st, &n_active), "rt_render_converge_window");
+        } else if (o.window)
+            check(rt_render_accum_window(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                         o.camera_motion ? &o.camera_move : nullptr, W, H, &o.win, depth, o.samples,
+                                         o.jitter, (uint32_t)o.seed, 0u, o.passes, o.aperture, o.light_size, o.shutter,
+                                         accum.data(), nullptr, rgba8.data(), nullptr, &st), "rt_render_accum_window");
         else if (o.converge) {
             std::fill(count.begin(), count.end(), 0u);      // every repeat is a new sum
             check(rt_render_converge(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
@@ -569,7 +616,9 @@ int main(int argc, char** argv) {
     }
     const double per_call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() /
                                o.repeat;
-    check(rt_write_ppm(o.out.c_str(), rgba8.data(), W, H, 4), "rt_write_ppm");
+    check(rt_write_ppm(o.out.c_str(), rgba8.data(), OW, OH, 4), "rt_write_ppm");
+    if (o.window)
+        std::printf("rt_render: window %d,%d,%d,%d of the %d x %d frame\n", o.win.x0, o.win.y0, OW, OH, W, H);
     const uint64_t rays = st.primary_rays + st.reflect_rays + st.shadow_rays;
     std::printf("rt_render: %dx%d depth %d -> %s | rays %llu (primary %llu, reflect %llu, shadow %llu) | kernel %.3f ms"
                 " | %.1f Mray/s\n",
@@ -578,11 +627,11 @@ int main(int argc, char** argv) {
                 rays / (st.kernel_ms * 1e3));
     if (o.converge) {
         unsigned long long traced = 0;
-        for (uint32_t n : count) traced += n;
+        for (size_t k = 0; k < (size_t)OW * OH; ++k) traced += count[k];
         std::printf("rt_render: converged, a budget of %d passes from seed %u, tolerance %g, at least %u passes: %llu of "
                     "%llu pixels still active, %llu of %llu pixel-passes traced, %llu primary rays\n", o.passes, o.seed,
-                    o.tolerance, min_passes, (unsigned long long)n_active, (unsigned long long)W * H, traced,
-                    (unsigned long long)W * H * (unsigned long long)o.passes, (unsigned long long)st.primary_rays);
+                    o.tolerance, min_passes, (unsigned long long)n_active, (unsigned long long)OW * OH, traced,
+                    (unsigned long long)OW * OH * (unsigned long long)o.passes, (unsigned long long)st.primary_rays);
     } else if (o.passes != 0)
         std::printf("rt_render: accumulated, %d passes with the seeds %u .. %u: the mean of %d x %d x %d samples per "
                     "pixel, %llu primary rays\n", o.passes, o.seed, (unsigned)(o.seed + (unsigned)o.passes - 1u), o.passes,

@@ -7,8 +7,9 @@
 //   rt_plain.hip    the plain render path, render_dev_impl and its eight steps, and the view cache it owns: the
 //                   dispatch-table kernels (rt_order / rowsum / iota / disp / run_plan / run_disp), rt_prepare_kernel
 //   rt_diag.hip     the view diagnostics of include/rt_diag.h
-//   rt_sampled.hip  adaptive supersampling (rt_classify_kernel), the lens family's device entry points and the
-//                   adaptive lens render's
+//   rt_sampled.hip  adaptive supersampling (rt_classify_kernel), the lens family's device entry points, the
+//                   adaptive lens render's, and the accumulating and converging renders' with their windowed forms
+//                   (kernels: rt_accum.hip, rt_converge.hip, rt_accum_window.hip, rt_converge_window.hip)
 //   rt_frames.hip   every call that renders into host memory: the context's device buffers, the ray sums, the packed
 //                   and asynchronous frames, the pinned-memory registry, the copy kernel and the SDMA path
 //   rt_rays.hip     the ray-list entry points (rt_intersect_kernel, rt_probe_math_kernel)
@@ -334,14 +335,17 @@ constexpr int kAccumCallPasses = 65536;
 int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                      int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
                      double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                     uint32_t* raycount2, void* stream);
+                     uint32_t* raycount2, void* stream, const rt_window* win = nullptr);
 // The checks on the converging render's own arguments and its device render, as `who` (rt_frames.hip's host entry point too).
 int converge_arg_checks(const char* who, int passes, uint32_t min_passes, double tolerance);
 int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                         int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
                         double tolerance, double aperture, double light_size, double shutter, double* accum,
                         double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                        uint32_t* raycount2, uint32_t* active, void* stream);
+                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win = nullptr);
+// `win` of the two above: nullptr runs the frame's kernels; a window (checked by window_arg_checks against the W x H
+// frame) runs the windowed ones on buffers whose pointers point at window pixel (0, 0) (rt_render_accum_window_dev).
+int window_arg_checks(const char* who, const rt_window* win, int W, int H);
 
 // rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after
 // the context's streams have drained).

@@ -476,6 +476,144 @@ extern "C" int rt_render_converge(rt_ctx* c, const rt_scene* scene, const double
         });
 }
 
+// ---- windows of the accumulating and converging renders into host memory (include/rt_api.h) -------------------------
+// One per-pixel host array of a windowed host render: context buffer k, `elem` bytes per pixel, addressed on the host
+// with the window's stride; dev: its dense width x height device copy, filled in by host_render_window.
+struct WinBuf {
+    int k;
+    size_t elem;
+    void* host;
+    void* dev;
+};
+
+// Rows of a window between a strided host array and its dense device copy: only the window's own elements move.
+static int window_copy(const rt_window& w, const WinBuf& b, bool to_device, hipStream_t st) {
+    const size_t row = (size_t)w.width * b.elem, pitch = (size_t)w.stride * b.elem;
+    if (to_device) RT_HIP(hipMemcpy2DAsync(b.dev, row, b.host, pitch, row, (size_t)w.height, hipMemcpyHostToDevice, st));
+    else RT_HIP(hipMemcpy2DAsync(b.host, pitch, b.dev, row, row, (size_t)w.height, hipMemcpyDeviceToHost, st));
+    return RT_OK;
+}
+
+// host_render for a window: dense device buffers of the window's pixels (b[0..2]: RGBA32F, RGBA8, RGB64F as the caller
+// gave them; then n_extra more), render(dense window, counters) between the timing events, the ray sums, the rows back
+// with the stride, one synchronisation of the render stream, then the statistics from primary(&n).
+template <class Render, class Primary>
+static int host_render_window(rt_ctx* c, const rt_window& w, WinBuf* b, int n_extra, rt_stats* stats, Render&& render,
+                              Primary&& primary) {
+    RT_HIP(hipSetDevice(c->device));
+    int rc;
+    const size_t npx = (size_t)w.width * (size_t)w.height;
+    for (int k = 0; k < 3 + n_extra; ++k)
+        if ((b[k].host || k >= 3) && (rc = ctx_buffer(c, b[k].k, npx * b[k].elem, &b[k].dev)) != RT_OK) return rc;
+    void *d_rc = nullptr, *d_sums = nullptr;
+    if (stats && ((rc = ctx_buffer(c, 3, npx * 8, &d_rc)) || (rc = ctx_buffer(c, 4, 2 * sizeof(unsigned long long), &d_sums))))
+        return rc;
+    const rt_window dense{w.x0, w.y0, w.width, w.height, w.width};
+    RT_HIP(hipEventRecord(c->frames.ev0, c->frames.rs));
+    if ((rc = render(dense, (uint32_t*)d_rc)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->frames.ev1, c->frames.rs));
+    if (stats && (rc = queue_raysum(c, npx, 2, (uint32_t*)d_rc, (unsigned long long*)d_sums))) return rc;
+    for (int k = 0; k < 3 + n_extra; ++k)
+        if (b[k].host && (rc = window_copy(w, b[k], false, c->frames.rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->frames.rs));
+    uint64_t prim = 0;
+    if ((rc = primary(&prim)) != RT_OK || !stats) return rc;
+    if ((rc = read_stats(c, npx, (const unsigned long long*)d_sums, stats)) != RT_OK) return rc;
+    stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+    stats->primary_rays = prim;
+    return RT_OK;
+}
+
+// rt_render_accum for a window: the checks first, then only the window's rows of `accum` go up (first_pass > 0) and only
+// the window's rows of every array come back.
+extern "C" int rt_render_accum_window(rt_ctx* c, const rt_scene* scene, const double* displacement,
+                                      const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                      const rt_window* win, int depth, int samples, int jitter, uint32_t seed,
+                                      uint32_t first_pass, int passes, double aperture, double light_size,
+                                      double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                      rt_stats* stats) {
+    const char* who = "rt_render_accum_window";
+    int rc = window_arg_checks(who, win, W, H);             // first: no context is needed to reject a window
+    if (rc || (rc = sampled_host_checks(who, c, W, H, samples))) return rc;
+    if ((rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (passes < 1 || passes > kAccumCallPasses)
+        return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
+    if ((uint64_t)first_pass + (uint64_t)passes > (1ull << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": first_pass + passes must not exceed 2^31");
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    WinBuf b[4] = {{0, 16, rgba32f, nullptr}, {1, 4, rgba8, nullptr}, {2, 24, rgb64f, nullptr},
+                   {rt_ctx::Frames::kBufAccum, 24, accum, nullptr}};
+    return host_render_window(
+        c, *win, b, 1, stats,
+        [&](const rt_window& dense, uint32_t* d_rc) {
+            int r;
+            if (first_pass > 0 && (r = window_copy(*win, b[3], true, c->frames.rs))) return r;
+            return accum_render_dev("rt_render_accum_window_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                                    first_pass, passes, aperture, light_size, shutter, (double*)b[3].dev,
+                                    (float*)b[0].dev, (uint8_t*)b[1].dev, (double*)b[2].dev, d_rc, c->frames.rs, &dense);
+        },
+        [&](uint64_t* prim) {
+            *prim = (uint64_t)win->width * (uint64_t)win->height * (uint64_t)samples * (uint64_t)samples * (uint64_t)passes;
+            return RT_OK;
+        });
+}
+
+// rt_render_converge for a window: the window's rows of the three state arrays go up and come back; *n_active and the
+// primary rays behind *stats are the window's.
+extern "C" int rt_render_converge_window(rt_ctx* c, const rt_scene* scene, const double* displacement,
+                                         const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                         const rt_window* win, int depth, int samples, int jitter, uint32_t seed,
+                                         int passes, uint32_t min_passes, double tolerance, double aperture,
+                                         double light_size, double shutter, double* accum, double* accum2,
+                                         uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                         rt_stats* stats, uint64_t* n_active) {
+    const char* who = "rt_render_converge_window";
+    int rc = window_arg_checks(who, win, W, H);             // first: no context is needed to reject a window
+    if (rc || (rc = sampled_host_checks(who, c, W, H, samples))) return rc;
+    if ((rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
+    if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
+    if ((rc = converge_arg_checks(who, passes, min_passes, tolerance))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const auto passes_held = [&]() {                        // the pixel-passes the window's state holds
+        uint64_t n = 0;
+        for (int j = 0; j < win->height; ++j)
+            for (int i = 0; i < win->width; ++i) n += count[(size_t)j * (size_t)win->stride + (size_t)i];
+        return n;
+    };
+    const uint64_t before = passes_held();
+    WinBuf b[6] = {{0, 16, rgba32f, nullptr}, {1, 4, rgba8, nullptr}, {2, 24, rgb64f, nullptr},
+                   {rt_ctx::Frames::kBufAccum, 24, accum, nullptr}, {rt_ctx::Frames::kBufAccum2, 24, accum2, nullptr},
+                   {rt_ctx::Frames::kBufCount, 4, count, nullptr}};
+    void* d_active = nullptr;
+    if ((rc = ctx_buffer(c, rt_ctx::Frames::kBufActive, 4, &d_active))) return rc;
+    return host_render_window(
+        c, *win, b, 3, stats,
+        [&](const rt_window& dense, uint32_t* d_rc) {
+            int r;
+            for (int k = 3; k < 6; ++k)
+                if ((r = window_copy(*win, b[k], true, c->frames.rs))) return r;
+            return converge_render_dev("rt_render_converge_window_dev", c, cam, motion, W, H, depth, samples, jitter,
+                                       seed, passes, min_passes, tolerance, aperture, light_size, shutter,
+                                       (double*)b[3].dev, (double*)b[4].dev, (uint32_t*)b[5].dev, (float*)b[0].dev,
+                                       (uint8_t*)b[1].dev, (double*)b[2].dev, d_rc, (uint32_t*)d_active, c->frames.rs,
+                                       &dense);
+        },
+        [&](uint64_t* prim) {
+            uint32_t n = 0;
+            RT_HIP(hipMemcpy(&n, d_active, sizeof(n), hipMemcpyDeviceToHost));
+            if (n_active) *n_active = n;
+            *prim = (passes_held() - before) * (uint64_t)samples * (uint64_t)samples;
+            return RT_OK;
+        });
+}
+
 // rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
 // rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
 // back.

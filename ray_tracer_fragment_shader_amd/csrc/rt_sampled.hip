@@ -363,6 +363,40 @@ extern "C" int rt_render_shutter_dev(rt_ctx* c, const rt_camera* cam, const rt_c
                               light_size, shutter, rgba32f, rgba8, rgb64f, raycount2, stream);
 }
 
+// ---- windows of the accumulating and converging renders (include/rt_api.h) -------------------------------------------
+// The checks on a window of the W x H frame (W, H are checked by the render's own front).
+int window_arg_checks(const char* who, const rt_window* win, int W, int H) {
+    if (!win) return rt_fail(RT_EINVAL, std::string(who) + ": null window");
+    if (win->x0 < 0 || win->y0 < 0) return rt_fail(RT_EINVAL, std::string(who) + ": negative window origin (window)");
+    if (win->width < 1 || win->height < 1)
+        return rt_fail(RT_EINVAL, std::string(who) + ": window width and height must be at least 1 (window)");
+    if ((long long)win->x0 + win->width > W || (long long)win->y0 + win->height > H)
+        return rt_fail(RT_EINVAL, std::string(who) + ": the window leaves the frame (window)");
+    if (win->stride < win->width)
+        return rt_fail(RT_EINVAL, std::string(who) + ": the window's stride is below its width (window)");
+    return RT_OK;
+}
+
+// What the windowed kernels take (rt_sampled.hpp WindowParams): the window's corners in sample units and every buffer
+// pointer of the launch record moved back by y0 * stride + x0 of its own elements, to where frame pixel (0, 0) would lie.
+// The moved pointers are only ever indexed with the elements of the window's pixels (integer arithmetic: no pointer
+// outside its buffer is formed in C++).
+static void window_fold(const rt_window& w, int samples, SampledLaunch* L) {
+    L->window = WindowParams{samples * w.x0, samples * w.y0, samples * (w.x0 + w.width), samples * (w.y0 + w.height),
+                             w.stride};
+    const uintptr_t off = (uintptr_t)w.y0 * (uintptr_t)w.stride + (uintptr_t)w.x0;
+    const auto back = [&](auto* p, size_t bytes) {
+        return p ? reinterpret_cast<decltype(p)>((uintptr_t)p - off * bytes) : p;
+    };
+    L->accum = back(L->accum, 24);
+    L->accum2 = back(L->accum2, 24);
+    L->npasses = back(L->npasses, 4);
+    L->o32 = back(L->o32, 16);
+    L->o8 = back(L->o8, 4);
+    L->o64 = back(L->o64, 24);
+    L->orc2 = back(L->orc2, 8);
+}
+
 // ---- progressive accumulation (include/rt_api.h) -----------------------------------------------------------------------
 // Passes first_pass .. first_pass + passes - 1 of the shutter render (seed + p each) added to `accum` in the contract's
 // order by rt_accum_kernel: the shutter render's checks and launch record, the call's own checks, then launches of at most
@@ -375,11 +409,11 @@ extern "C" int rt_render_shutter_dev(rt_ctx* c, const rt_camera* cam, const rt_c
 int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                      int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
                      double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                     uint32_t* raycount2, void* stream) {
+                     uint32_t* raycount2, void* stream, const rt_window* win) {
     SampledLaunch L{};
-    const int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
-                                  rgba32f, rgba8, rgb64f, raycount2, stream, &L);
-    if (rc) return rc;
+    int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
+                            rgba32f, rgba8, rgb64f, raycount2, stream, &L);
+    if (rc || (win && (rc = window_arg_checks(who, win, W, H)))) return rc;
     if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
     if (passes < 1 || passes > kAccumCallPasses)
         return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
@@ -388,6 +422,12 @@ int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_
     RT_HIP(hipSetDevice(c->device));
     L.accum = accum;
     L.call_first = first_pass;
+    if (win) {
+        window_fold(*win, samples, &L);
+        rgba32f = (float*)L.o32;
+        rgba8 = (uint8_t*)L.o8;
+        rgb64f = L.o64;
+    }
     const uint32_t end = first_pass + (uint32_t)passes, step = (uint32_t)c->knobs.accum_max_passes;
     for (uint32_t p = first_pass; p < end; p += step) {
         L.first_pass = p;
@@ -396,8 +436,11 @@ int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_
         L.o32 = last ? rgba32f : nullptr;
         L.o8 = last ? rgba8 : nullptr;
         L.o64 = last ? rgb64f : nullptr;
-        const hipError_t e = with_depth(depth, [&](auto B) { return launch_accum<decltype(B)::value>(L); });
-        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_accum_kernel: ") + hipGetErrorString(e));
+        const hipError_t e = with_depth(depth, [&](auto B) {
+            return win ? launch_accum_window<decltype(B)::value>(L) : launch_accum<decltype(B)::value>(L);
+        });
+        if (e != hipSuccess)
+            return rt_fail(RT_EHIP, std::string(win ? "rt_accum_window_kernel: " : "rt_accum_kernel: ") + hipGetErrorString(e));
     }
     return RT_OK;
 }
@@ -433,11 +476,11 @@ int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const 
                         int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
                         double tolerance, double aperture, double light_size, double shutter, double* accum,
                         double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                        uint32_t* raycount2, uint32_t* active, void* stream) {
+                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win) {
     SampledLaunch L{};
     int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
                             rgba32f, rgba8, rgb64f, raycount2, stream, &L);
-    if (rc) return rc;
+    if (rc || (win && (rc = window_arg_checks(who, win, W, H)))) return rc;
     if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
     if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
     if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
@@ -449,6 +492,12 @@ int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const 
     L.npasses = count;
     L.min_passes = min_passes;
     L.tolerance = tolerance;
+    if (win) {
+        window_fold(*win, samples, &L);
+        rgba32f = (float*)L.o32;
+        rgba8 = (uint8_t*)L.o8;
+        rgb64f = L.o64;
+    }
     const uint32_t end = (uint32_t)passes, step = (uint32_t)c->knobs.accum_max_passes;
     for (uint32_t p = 0; p < end; p += step) {
         L.passes = std::min(step, end - p);
@@ -458,8 +507,12 @@ int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const 
         L.o8 = L.last ? rgba8 : nullptr;
         L.o64 = L.last ? rgb64f : nullptr;
         L.active = L.last ? active : nullptr;
-        const hipError_t e = with_depth(depth, [&](auto B) { return launch_converge<decltype(B)::value>(L); });
-        if (e != hipSuccess) return rt_fail(RT_EHIP, std::string("rt_converge_kernel: ") + hipGetErrorString(e));
+        const hipError_t e = with_depth(depth, [&](auto B) {
+            return win ? launch_converge_window<decltype(B)::value>(L) : launch_converge<decltype(B)::value>(L);
+        });
+        if (e != hipSuccess)
+            return rt_fail(RT_EHIP, std::string(win ? "rt_converge_window_kernel: " : "rt_converge_kernel: ") +
+                                        hipGetErrorString(e));
     }
     return RT_OK;
 }
@@ -473,6 +526,31 @@ extern "C" int rt_render_converge_dev(rt_ctx* c, const rt_camera* cam, const rt_
     return converge_render_dev("rt_render_converge_dev", c, cam, motion, W, H, depth, samples, jitter, seed, passes,
                                min_passes, tolerance, aperture, light_size, shutter, accum, accum2, count, rgba32f, rgba8,
                                rgb64f, raycount2, active, stream);
+}
+
+// The windowed entry points: the same host code with the window's checks, folding and kernels.
+extern "C" int rt_render_accum_window_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                          const rt_window* win, int depth, int samples, int jitter, uint32_t seed,
+                                          uint32_t first_pass, int passes, double aperture, double light_size,
+                                          double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                          uint32_t* raycount2, void* stream) {
+    const char* who = "rt_render_accum_window_dev";
+    if (const int rc = window_arg_checks(who, win, W, H)) return rc;    // first: no context is needed to reject a window
+    return accum_render_dev(who, c, cam, motion, W, H, depth, samples, jitter, seed, first_pass, passes, aperture,
+                            light_size, shutter, accum, rgba32f, rgba8, rgb64f, raycount2, stream, win);
+}
+
+extern "C" int rt_render_converge_window_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W,
+                                             int H, const rt_window* win, int depth, int samples, int jitter,
+                                             uint32_t seed, int passes, uint32_t min_passes, double tolerance,
+                                             double aperture, double light_size, double shutter, double* accum,
+                                             double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8,
+                                             double* rgb64f, uint32_t* raycount2, uint32_t* active, void* stream) {
+    const char* who = "rt_render_converge_window_dev";
+    if (const int rc = window_arg_checks(who, win, W, H)) return rc;    // first: no context is needed to reject a window
+    return converge_render_dev(who, c, cam, motion, W, H, depth, samples, jitter, seed, passes, min_passes, tolerance,
+                               aperture, light_size, shutter, accum, accum2, count, rgba32f, rgba8, rgb64f, raycount2,
+                               active, stream, win);
 }
 
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------

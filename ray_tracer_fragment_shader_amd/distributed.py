@@ -57,6 +57,24 @@ class BandPlan:
         return scenes.rows(self.band_height, self.world, rank, self.frames if frames is None else frames)
 
 
+def window_plan(width: int, height: int, parts: int) -> List[tuple]:
+    """The frame as `parts` windows (x0, y0, w, h) for Tracer.render_accum_window_into / render_converge_window_into:
+    horizontal strips of whole rows, bottom to top, whose heights differ by at most one (the taller ones first) — the
+    contiguous split a rank per GPU, or a tile loop over a frame whose state does not fit at once, would use.  The
+    strips partition the frame exactly; a window's bytes do not depend on the split.  More parts than rows give one
+    strip per row (never an empty window).  A pure function: moving the strips between processes is the caller's."""
+    if width < 1 or height < 1 or parts < 1:
+        raise ValueError("width, height and parts must be at least 1")
+    n = min(parts, height)
+    base, extra = divmod(height, n)
+    plan, y = [], 0
+    for k in range(n):
+        h = base + (1 if k < extra else 0)
+        plan.append((0, y, width, h))
+        y += h
+    return plan
+
+
 def _host_staged(group=None) -> bool:
     """gloo over device tensors: the rehearsal of the RCCL path on one GPU (bench.py --backend gloo) stages
     the exchange through host memory; RCCL moves device memory directly."""

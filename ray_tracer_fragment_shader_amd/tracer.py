@@ -341,6 +341,121 @@ class Tracer:
                                   tolerance, aperture, light_size, shutter, state, bufs, active, stream)
         return bufs, state, active
 
+    # ------------------------------------------------- windows of the accumulating and converging renders
+    _WINDOW_BUFS = {"accum": (torch.float64, 3), "accum2": (torch.float64, 3), "count": (torch.int32, 1),
+                    "rgba32f": (torch.float32, 4), "rgba8": (torch.uint8, 4), "rgb64f": (torch.float64, 3),
+                    "raycount": (torch.int32, 2)}
+
+    def _window(self, width: int, height: int, window, tensors: dict):
+        """-> (rt_window, {name: pointer}).  Each tensor is a full-frame one, (height, width[, C]), in which the window
+        lies in place, or one of the window's own (h, w[, C]) pixels — dense, or a view of wider rows; all must give
+        the same row stride."""
+        try:
+            x0, y0, w, h = (int(v) for v in window)
+        except (TypeError, ValueError):
+            raise ValueError("window must be (x0, y0, width, height)") from None
+        if x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > width or y0 + h > height:
+            raise ValueError(f"window {(x0, y0, w, h)} is empty or leaves the {width} x {height} frame")
+        stride, ptrs = None, {}
+        for name, t in tensors.items():
+            if t is None:
+                ptrs[name] = None
+                continue
+            dtype, c = self._WINDOW_BUFS[name]
+            if not t.is_cuda or t.dtype != dtype:
+                raise ValueError(f"{name} must be a HIP tensor of {dtype}")
+            if t.dim() == 2 and c == 1:
+                t = t.unsqueeze(-1)
+            if t.dim() != 3 or t.shape[2] != c:
+                raise ValueError(f"{name} must have {c} element(s) per pixel in its last dimension")
+            if tuple(t.shape[:2]) == (height, width):
+                t = t[y0:y0 + h, x0:x0 + w]
+            elif tuple(t.shape[:2]) != (h, w):
+                raise ValueError(f"{name} must hold the {height} x {width} frame or the {h} x {w} window, not "
+                                 f"{tuple(t.shape[:2])}")
+            if (c > 1 and t.stride(2) != 1) or t.stride(1) != c or t.stride(0) % c or t.stride(0) < w * c:
+                raise ValueError(f"{name}: pixels must be contiguous within a row and rows a whole number of pixels apart")
+            if stride is not None and t.stride(0) // c != stride:
+                raise ValueError(f"{name}: every buffer of a window must have the same row stride in pixels")
+            stride = t.stride(0) // c
+            ptrs[name] = ctypes.c_void_p(t.data_ptr())
+        return abi.rt_window(x0, y0, w, h, stride if stride is not None else w), ptrs
+
+    def render_accum_window_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int,
+                                 height: int, window, depth: int, samples: int, jitter: int, seed: int, first_pass: int,
+                                 passes: int, aperture: float, light_size: float, shutter: float, accum: torch.Tensor,
+                                 bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_accum_window_dev: render_accum_into() for the pixels of window = (x0, y0, w, h) of the width x
+        height frame alone, with the full frame's bytes.  `accum` and every buffer of `bufs` is either a full-frame
+        tensor, in which the window is rendered in place and nothing else is touched, or a tensor of the window's own
+        h x w pixels.  Asynchronous on `stream` (default: torch's current stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if accum is None:
+            raise ValueError("accum is required")
+        win, p = self._window(width, height, window, {"accum": accum, **{k: bufs.get(k) for k in
+                                                                         ("rgba32f", "rgba8", "rgb64f", "raycount")}})
+        abi.check(abi.lib().rt_render_accum_window_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height,
+            ctypes.byref(win), depth, samples, jitter, int(seed) & 0xFFFFFFFF, int(first_pass), int(passes),
+            float(aperture), float(light_size), float(shutter), p["accum"], p["rgba32f"], p["rgba8"], p["rgb64f"],
+            p["raycount"], ctypes.c_void_p(st.cuda_stream)), "rt_render_accum_window_dev")
+        return bufs
+
+    def render_accum_window(self, cam, motion, width, height, window, depth, samples, jitter, seed, first_pass, passes,
+                            aperture, light_size, shutter, accum=None, rgba32f=True, rgba8=False, rgb64f=False,
+                            raycount=False, stream=None):
+        """-> (dense buffers of the window's h x w pixels as alloc_ss() lays them out, the accumulator): `accum`
+        continued (full-frame or dense), or a new dense one when it is None (then first_pass must be 0)."""
+        _, _, w, h = window
+        if accum is None:
+            if first_pass != 0:
+                raise ValueError("first_pass > 0 continues a sum: pass its accum")
+            accum = self.alloc_accum(w, h)
+        bufs = self.alloc_ss(w, h, None, rgba32f, rgba8, rgb64f, raycount)
+        self.render_accum_window_into(cam, motion, width, height, window, depth, samples, jitter, seed, first_pass,
+                                      passes, aperture, light_size, shutter, accum, bufs, stream)
+        return bufs, accum
+
+    def render_converge_window_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int,
+                                    height: int, window, depth: int, samples: int, jitter: int, seed: int, passes: int,
+                                    min_passes: int, tolerance: float, aperture: float, light_size: float,
+                                    shutter: float, state, bufs: dict, active: Optional[torch.Tensor] = None,
+                                    stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_converge_window_dev: render_converge_into() for the pixels of window = (x0, y0, w, h) alone, with
+        the full frame's bytes; `active` counts the window's pixels.  The three tensors of `state` and every buffer of
+        `bufs` are full-frame tensors (the window in place) or tensors of the window's h x w pixels."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        accum, accum2, count = state
+        if accum is None or accum2 is None or count is None:
+            raise ValueError("state must be (accum, accum2, count)")
+        if active is not None and (active.dtype != torch.int32 or active.numel() != 1):
+            raise ValueError("active must be a one-element int32 tensor")
+        win, p = self._window(width, height, window, {"accum": accum, "accum2": accum2, "count": count,
+                                                      **{k: bufs.get(k) for k in
+                                                         ("rgba32f", "rgba8", "rgb64f", "raycount")}})
+        abi.check(abi.lib().rt_render_converge_window_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height,
+            ctypes.byref(win), depth, samples, jitter, int(seed) & 0xFFFFFFFF, int(passes),
+            int(min_passes) & 0xFFFFFFFF, float(tolerance), float(aperture), float(light_size), float(shutter),
+            p["accum"], p["accum2"], p["count"], p["rgba32f"], p["rgba8"], p["rgb64f"], p["raycount"], _ptr(active),
+            ctypes.c_void_p(st.cuda_stream)), "rt_render_converge_window_dev")
+        return bufs
+
+    def render_converge_window(self, cam, motion, width, height, window, depth, samples, jitter, seed, passes,
+                               min_passes, tolerance, aperture, light_size, shutter, state=None, rgba32f=True,
+                               rgba8=False, rgb64f=False, raycount=False, stream=None):
+        """-> (dense buffers of the window's pixels, the state, the window's active count as a one-element device
+        tensor): `state` continued (full-frame or dense), or a new dense one when it is None."""
+        _, _, w, h = window
+        if state is None:
+            state = self.alloc_converge(w, h)
+        bufs = self.alloc_ss(w, h, None, rgba32f, rgba8, rgb64f, raycount)
+        active = torch.zeros((1,), dtype=torch.int32, device=torch.device("cuda", self.device))
+        self.render_converge_window_into(cam, motion, width, height, window, depth, samples, jitter, seed, passes,
+                                         min_passes, tolerance, aperture, light_size, shutter, state, bufs, active,
+                                         stream)
+        return bufs, state, active
+
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
     def alloc_lens_adaptive(self, width: int, height: int, rgba32f=True, rgba8=False, rgb64f=False, raycount=False,
                             refined=True):
