@@ -799,8 +799,8 @@ typedef struct rt_window {      /* a rectangle of the width x height output fram
  *     height below 1, a window that leaves the frame, stride < win.width, and every check of the un-windowed call.
  *  8. Asynchronous on `stream`, no allocation and no host synchronisation; capturable in a hipGraph, the reset of
  *     `active` a memset node of the call.  No per-view state.
- *  9. Not offered: windows of rt_render_lens_adaptive_dev; rt_rows; the packed and group paths; a list of windows in
- *     one launch.
+ *  9. Not offered: windows of rt_render_lens_adaptive_dev; rt_rows; the packed and group paths.  A list of windows in
+ *     one launch is rt_render_accum_windows_dev and rt_render_converge_windows_dev (below).
  * The kernels are rt_accum_kernel and rt_converge_kernel with the lane's sample formed from the window's sample origin;
  * the host folds the window into five words and moves the pointers, and every instance keeps its parent's waves per
  * SIMD (profiles/window/resource_usage.txt).
@@ -837,6 +837,94 @@ int rt_render_converge_window(rt_ctx* ctx, const rt_scene* scene, const double* 
                               double aperture, double light_size, double shutter, double* accum, double* accum2,
                               uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats,
                               uint64_t* n_active);
+
+/* ---- lists of windows of the accumulating and converging renders (ABI 10: new symbols only) ------------------------ */
+/* A window call is one launch per rectangle and per launch group, and each launch pays its ramp and drain: a rank that
+ * owns dozens of disjoint bands, a tile loop or a viewer refining several regions pays it per rectangle.  The list calls
+ * render any set of DISJOINT windows of one frame with one launch per launch group, every pixel with the bytes of the
+ * un-windowed frame.  The list lives in the context (rt_set_windows, as the motion does: rt_set_motion); the render calls
+ * take exactly the un-windowed calls' arguments. */
+#define RT_MAX_WINDOWS      4096
+#define RT_WINDOWS_IN_PLACE 0   /* every window inside full-frame buffers: stride = frame width               */
+#define RT_WINDOWS_PACKED   1   /* every window dense (stride = its width), one after the other in list order */
+/* rt_window_list_plan: a pure host function (no context, no GPU) that validates a list and gives the numbers everything
+ * else uses.  wins[k].stride is ignored on input: the layout decides it.
+ *   offset[k]      the element index of window k's pixel (0, 0) in every per-pixel buffer (an element: rt_window above).
+ *                  IN_PLACE: y0 width + x0, the stride is `width`.  PACKED: the sum of the areas of windows 0 .. k - 1,
+ *                  the stride is wins[k].width.
+ *   *elements      the per-pixel elements the buffers must hold.  IN_PLACE: width height.  PACKED: the sum of the areas.
+ *   first_tile[k]  the number of 8 x 8-sample tiles of windows 0 .. k - 1 at `samples` = S: window k has
+ *                  ceil(S w / 8) ceil(S h / 8) of them; first_tile[n] is the launch's tile count.
+ * Any output pointer may be null.  RT_EINVAL (rt_last_error names the argument), with nothing written, for n < 1 or
+ * n > RT_MAX_WINDOWS (`n`), an unknown `layout`, `samples` not 1, 2, 4 or 8, a bad frame size (`width`, `height`), a
+ * null `wins`, a window that fails the single-window checks of rule 7 of the window calls (`window`, with its index) and
+ * two windows that share a frame pixel (`window`, with both indices).  Windows that touch along an edge are disjoint.
+ * Disjoint windows make both layouts' footprints disjoint: that is the whole aliasing rule. */
+int rt_window_list_plan(int width, int height, int samples, const rt_window* wins, int n, int layout,
+                        uint32_t* first_tile /* n + 1 */, int64_t* offset /* n */, uint64_t* elements);
+/* rt_set_windows: validates the list with rt_window_list_plan, copies it into the context and uploads one device table
+ * (per window: its rectangle, stride and element base, and its tile prefix for each of S = 1, 2, 4, 8, so the table does
+ * not depend on S).  Synchronous: work in flight on the device is waited for first, and this is the only allocation of
+ * the list calls.  n = 0 with wins = NULL clears the list.  rt_set_scene and rt_set_motion do not touch the list.  A
+ * failed call leaves the previous list in force. */
+int rt_set_windows(rt_ctx* ctx, int width, int height, const rt_window* wins, int n, int layout);
+/* The list renders: rt_render_accum_dev's and rt_render_converge_dev's arguments, unchanged.
+ *  1. Value.  For every pixel of every window of the list, rule 1 of the window calls: the bytes of the un-windowed call
+ *     for that frame pixel, under the full frame's sample key.  The buffers hold `elements` elements laid out as the plan
+ *     says: window k's pixel (i, j) is element offset[k] + j stride_k + i of every per-pixel buffer.
+ *  2. Nothing else is touched: elements that belong to no window are neither read nor written.
+ *  3. `active` (converge) is the count over all windows of the list.
+ *  4. The order of the list changes nothing but the PACKED offsets.  The list {0, 0, width, height} gives the bytes of
+ *     the single-window call on the whole frame and of the un-windowed call.
+ *  5. As per window today: (0, a) then (a, b) equals (0, a + b); the host's launch split (RT_ACCUM_MAX_PASSES) is
+ *     invisible; a loosely stopped list resumes under a smaller E; a state written by the un-windowed or the
+ *     single-window calls is continued by a list call (IN_PLACE, or PACKED after moving the rows) and the other way round.
+ *  6. One launch per launch group of at most RT_ACCUM_MAX_PASSES passes, whatever n is.  The grid is one-dimensional over
+ *     first_tile[n] tiles (folded into grid.y above 2^20 tiles); a wave finds its window by a wave-uniform binary search
+ *     of the prefix column (at most 12 steps), loads that entry once and from there runs the single-window kernel's body.
+ *  7. RT_EINVAL (rt_last_error names `window`), with no byte written, when no list is set or `width`, `height` are not
+ *     the list's frame; and for every check of the un-windowed call.
+ *  8. Asynchronous on `stream`, no allocation and no host synchronisation; capturable in a hipGraph, the reset of
+ *     `active` a memset node of the call.  A captured graph holds the table's address and the tile count of the list in
+ *     force at capture: after rt_set_windows, re-capture.
+ *  9. Not offered: a list produced on the device (the table's layout does not preclude it: prefixes and entries are plain
+ *     device arrays); overlapping windows; lists for rt_render_lens_adaptive_dev; rt_rows; the packed and group paths.
+ * Every instance keeps its parent's waves per SIMD and adds no scratch (profiles/window_list/resource_usage.txt).
+ * Measured (MI355X, the window calls' c2 frames and arguments, accum (0, 16) and converge K = 64, M = 4, E = 1 / 255 at
+ * S = 1 and S = 2, tools/bench_window_list.py, profiles/window_list/bench_window_list.json, every leg's bytes checked
+ * equal first): one list call against one window call per rectangle takes 0.43 x / 0.36 x / 0.75 x / 0.62 x for 4 x 4 tiles
+ * (accum S = 1, converge S = 1, accum S = 2, converge S = 2), 0.62 x / 0.60 x / 0.85 x / 0.79 x for 8 strips and
+ * 0.125 x / 0.128 x / 0.28 x / 0.25 x for rank 0's 17 bands of 8 rows at 8 ranks, above the spreads in every cell.  Against
+ * the un-windowed call the 4 x 4 tiles cost 1.108 x / 1.100 x / 1.056 x / 1.055 x and the 8 strips 1.061 x / 1.054 x /
+ * 1.063 x / 1.056 x.  The list of the one whole-frame window costs 1.041 x / 1.036 x / 1.041 x / 1.040 x the window call on it:
+ * not within the spreads; 1.6 % of it is in the kernel's own traced time (profiles/window_list/kernel_trace_accum_s1.csv),
+ * the rest was not separated.  4096 windows of
+ * 8 x 8 pixels cost 1.035 x / 1.025 x / 1.025 x / 1.025 x the one window of their region.  profiles/window_list/README.md
+ * has the records.  Other scenes, depths and motions: not measured. */
+int rt_render_accum_windows_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width, int height,
+                                int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes,
+                                double aperture, double light_size, double shutter, double* accum, float* rgba32f,
+                                uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, void* stream);
+int rt_render_converge_windows_dev(rt_ctx* ctx, const rt_camera* cam, const rt_camera_motion* motion, int width,
+                                   int height, int depth, int samples, int jitter, uint32_t seed, int passes,
+                                   uint32_t min_passes, double tolerance, double aperture, double light_size,
+                                   double shutter, double* accum, double* accum2, uint32_t* count, float* rgba32f,
+                                   uint8_t* rgba8, double* rgb64f, uint32_t* raycount2, uint32_t* active, void* stream);
+/* Synchronous host-buffer conveniences, as rt_render_accum and rt_render_converge with the list after their arguments:
+ * rt_set_scene, rt_set_motion and rt_set_windows(width, height, wins, n, layout), then the render.  The host arrays are
+ * laid out as the plan says, as the context's device buffers are, and only the windows' rows move (the state up,
+ * everything back).  *n_active and *stats are the list's.  The list stays set in the context. */
+int rt_render_accum_windows(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                            const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
+                            uint32_t seed, uint32_t first_pass, int passes, double aperture, double light_size,
+                            double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                            rt_stats* stats, const rt_window* wins, int n, int layout);
+int rt_render_converge_windows(rt_ctx* ctx, const rt_scene* scene, const double* displacement, const rt_camera* cam,
+                               const rt_camera_motion* motion, int width, int height, int depth, int samples, int jitter,
+                               uint32_t seed, int passes, uint32_t min_passes, double tolerance, double aperture,
+                               double light_size, double shutter, double* accum, double* accum2, uint32_t* count,
+                               float* rgba32f, uint8_t* rgba8, double* rgb64f, rt_stats* stats, uint64_t* n_active,
+                               const rt_window* wins, int n, int layout);
 
 /* ---- packed pixel formats (ABI 5)--------------------------------------------------------------- */
 /* What a frame's bytes look like in a buffer.  Rows are dense (W * bytes per pixel), j = 0 at the bottom.

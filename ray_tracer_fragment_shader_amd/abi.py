@@ -33,6 +33,8 @@ RT_OUT_RGBA32F, RT_OUT_RGBA8 = 1, 2
 RT_PIXEL_RGBA32F, RT_PIXEL_GRAY32F, RT_PIXEL_RGBA8, RT_PIXEL_RGB8, RT_PIXEL_GRAY8 = 0, 1, 2, 3, 4
 PIXEL_BYTES = {RT_PIXEL_RGBA32F: 16, RT_PIXEL_GRAY32F: 4, RT_PIXEL_RGBA8: 4, RT_PIXEL_RGB8: 3, RT_PIXEL_GRAY8: 1}
 RT_COMM_ID_BYTES = 128
+RT_MAX_WINDOWS = 4096
+RT_WINDOWS_IN_PLACE, RT_WINDOWS_PACKED = 0, 1
 
 D3 = c_double * 3
 
@@ -256,6 +258,25 @@ SIGNATURES = {
                                           c_int, c_int, _P(rt_window), c_int, c_int, c_int, ctypes.c_uint32, c_int,
                                           ctypes.c_uint32, c_double, c_double, c_double, c_double, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, _P(rt_stats), _P(c_uint64)]),
+    "rt_window_list_plan": (c_int, [c_int, c_int, c_int, _P(rt_window), c_int, c_int, _P(ctypes.c_uint32),
+                                    _P(ctypes.c_int64), _P(c_uint64)]),
+    "rt_set_windows": (c_int, [c_void_p, c_int, c_int, _P(rt_window), c_int, c_int]),
+    "rt_render_accum_windows_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int, c_int, c_int,
+                                            c_int, ctypes.c_uint32, ctypes.c_uint32, c_int, c_double, c_double,
+                                            c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_render_converge_windows_dev": (c_int, [c_void_p, _P(rt_camera), _P(rt_camera_motion), c_int, c_int, c_int,
+                                               c_int, c_int, ctypes.c_uint32, c_int, ctypes.c_uint32, c_double,
+                                               c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rt_render_accum_windows": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion),
+                                        c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, ctypes.c_uint32, c_int,
+                                        c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        _P(rt_stats), _P(rt_window), c_int, c_int]),
+    "rt_render_converge_windows": (c_int, [c_void_p, _P(rt_scene), _P(c_double), _P(rt_camera), _P(rt_camera_motion),
+                                           c_int, c_int, c_int, c_int, c_int, ctypes.c_uint32, c_int, ctypes.c_uint32,
+                                           c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, _P(rt_stats), _P(c_uint64), _P(rt_window),
+                                           c_int, c_int]),
     # include/rt_diag.h
     "rt_group_agree_due": (c_int, [c_uint64, c_int, c_uint64]),
     "rt_group_agree_vote": (None, [c_uint64, c_int, _P(c_uint64)]),

@@ -64,6 +64,10 @@
 //                                                  only the W x H rectangle at (X, Y) of the frame (Y = 0: the bottom row),
 //                                                  with the full frame's bytes; the PPM is W x H
 //                                                  (rt_render_accum_window / rt_render_converge_window)
+//   ... --passes 64 [--tolerance 0.004] --windows X,Y,W,H:X,Y,W,H:...
+//                                                  the listed disjoint rectangles of the frame in one launch per launch
+//                                                  group, in place; the PPM is the full frame, black outside the windows
+//                                                  (rt_render_accum_windows / rt_render_converge_windows)
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -114,6 +118,7 @@ struct Options {
     long long min_passes = 0;                // --min-passes M (needs --tolerance; default 4)
     bool window = false;                     // --window X,Y,W,H: that rectangle of the frame alone (needs --passes)
     rt_window win{};
+    std::vector<rt_window> windows;         // --windows X,Y,W,H:...: those rectangles in one launch (needs --passes)
     std::vector<int> move_k;                // --move K:DX,DY,DZ (repeatable): sphere K's displacement
     std::vector<double> move_d;
 };
@@ -310,11 +315,29 @@ int main(int argc, char** argv) {
             o.window = true;
             o.win = rt_window{(int32_t)q[0], (int32_t)q[1], (int32_t)q[2], (int32_t)q[3], (int32_t)q[2]};
         }
+        else if (a == "--windows") {
+            const std::string v = next();
+            bool ok = !v.empty() && v.find_first_not_of("0123456789,-:") == std::string::npos;
+            for (size_t at = 0; ok && at <= v.size();) {
+                const size_t end = std::min(v.find(':', at), v.size());
+                const std::string item = v.substr(at, end - at);
+                long long q[4] = {0, 0, 0, 0};
+                char tail = 0;
+                ok = std::sscanf(item.c_str(), "%lld,%lld,%lld,%lld%c", &q[0], &q[1], &q[2], &q[3], &tail) == 4;
+                for (long long t : q) ok = ok && t >= INT32_MIN && t <= INT32_MAX;
+                if (ok) o.windows.push_back(rt_window{(int32_t)q[0], (int32_t)q[1], (int32_t)q[2], (int32_t)q[3], 0});
+                at = end + 1;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "rt_render: --windows takes X,Y,W,H:X,Y,W,H:... (four integers per window)\n");
+                return 2;
+            }
+        }
         else if (a == "--min-passes") { o.min_passes = std::atoll(next().c_str()); if (o.min_passes == 0) o.min_passes = -1; }
         else { std::fprintf(stderr, "usage: rt_render [--config c1|c2|c3|c5|demo | --stdin] [--width W --height H "
                                     "--pitch P --depth B] [--device N] [--faithful glibc|msvc [--seed S]] "
                                     "[--gpus N [--band H]] [--samples 1|2|4|8 [--adaptive T | [--light-size R] "
-                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K [--tolerance E [--min-passes M]] [--window X,Y,W,H]]] "
+                                    "[--aperture A [--focus RATIO]] [--shutter F [--move K:DX,DY,DZ]...] [--coarse C --refine T | --jitter J [--seed K] [--passes K [--tolerance E [--min-passes M]] [--window X,Y,W,H | --windows X,Y,W,H:...]]] "
                                     "[--eye-move DX,DY,DZ] [--look-move DX,DY,DZ]]] "
                                     "[--repeat K] [--out file.ppm]\n");
                return 2; }
@@ -400,6 +423,10 @@ int main(int argc, char** argv) {
     }
     if (o.window && o.passes == 0) {
         std::fprintf(stderr, "rt_render: --window needs --passes\n");
+        return 2;
+    }
+    if (!o.windows.empty() && (o.passes == 0 || o.window)) {
+        std::fprintf(stderr, "rt_render: --windows needs --passes and excludes --window\n");
         return 2;
     }
     if ((o.coarse != 0) != o.refine) {
@@ -564,7 +591,26 @@ int main(int argc, char** argv) {
             check(rt_render_lens_adaptive(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam, W, H, depth,
                                           o.coarse, o.samples, o.refine_t, o.aperture, o.light_size, o.shutter, nullptr,
                                           rgba8.data(), nullptr, nullptr, &st, &n_refined), "rt_render_lens_adaptive");
-        else if (o.converge && o.window) {
+        else if (!o.windows.empty()) {
+            // in place: the arrays are the full frame's, zero (black) outside the windows
+            std::fill(count.begin(), count.end(), 0u);      // every repeat is a new sum
+            const int nw = (int)o.windows.size();
+            if (o.converge)
+                check(rt_render_converge_windows(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                                 o.camera_motion ? &o.camera_move : nullptr, W, H, depth, o.samples,
+                                                 o.jitter, (uint32_t)o.seed, o.passes, min_passes, o.tolerance,
+                                                 o.aperture, o.light_size, o.shutter, accum.data(), accum2.data(),
+                                                 count.data(), nullptr, rgba8.data(), nullptr, &st, &n_active,
+                                                 o.windows.data(), nw, RT_WINDOWS_IN_PLACE),
+                      "rt_render_converge_windows");
+            else
+                check(rt_render_accum_windows(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
+                                              o.camera_motion ? &o.camera_move : nullptr, W, H, depth, o.samples,
+                                              o.jitter, (uint32_t)o.seed, 0u, o.passes, o.aperture, o.light_size,
+                                              o.shutter, accum.data(), nullptr, rgba8.data(), nullptr, &st,
+                                              o.windows.data(), nw, RT_WINDOWS_IN_PLACE),
+                      "rt_render_accum_windows");
+        } else if (o.converge && o.window) {
             std::fill(count.begin(), count.end(), 0u);      // every repeat is a new sum
             check(rt_render_converge_window(ctx, &scene, o.motion ? displacement.data() : nullptr, &cam,
                                             o.camera_motion ? &o.camera_move : nullptr, W, H, &o.win, depth, o.samples,
@@ -619,6 +665,11 @@ int main(int argc, char** argv) {
     check(rt_write_ppm(o.out.c_str(), rgba8.data(), OW, OH, 4), "rt_write_ppm");
     if (o.window)
         std::printf("rt_render: window %d,%d,%d,%d of the %d x %d frame\n", o.win.x0, o.win.y0, OW, OH, W, H);
+    unsigned long long list_px = 0;
+    for (const rt_window& w : o.windows) list_px += (unsigned long long)w.width * (unsigned long long)w.height;
+    if (!o.windows.empty())
+        std::printf("rt_render: %zu windows, %llu pixels of the %d x %d frame, in place\n", o.windows.size(), list_px, W, H);
+    const unsigned long long out_px = o.windows.empty() ? (unsigned long long)OW * OH : list_px;
     const uint64_t rays = st.primary_rays + st.reflect_rays + st.shadow_rays;
     std::printf("rt_render: %dx%d depth %d -> %s | rays %llu (primary %llu, reflect %llu, shadow %llu) | kernel %.3f ms"
                 " | %.1f Mray/s\n",
@@ -630,8 +681,8 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < (size_t)OW * OH; ++k) traced += count[k];
         std::printf("rt_render: converged, a budget of %d passes from seed %u, tolerance %g, at least %u passes: %llu of "
                     "%llu pixels still active, %llu of %llu pixel-passes traced, %llu primary rays\n", o.passes, o.seed,
-                    o.tolerance, min_passes, (unsigned long long)n_active, (unsigned long long)OW * OH, traced,
-                    (unsigned long long)OW * OH * (unsigned long long)o.passes, (unsigned long long)st.primary_rays);
+                    o.tolerance, min_passes, (unsigned long long)n_active, out_px, traced,
+                    out_px * (unsigned long long)o.passes, (unsigned long long)st.primary_rays);
     } else if (o.passes != 0)
         std::printf("rt_render: accumulated, %d passes with the seeds %u .. %u: the mean of %d x %d x %d samples per "
                     "pixel, %llu primary rays\n", o.passes, o.seed, (unsigned)(o.seed + (unsigned)o.passes - 1u), o.passes,

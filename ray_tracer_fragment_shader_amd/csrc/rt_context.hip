@@ -61,6 +61,7 @@ extern "C" int rt_ctx_destroy(rt_ctx* c) {
     if (c->frames.cs) (void)hipStreamSynchronize(c->frames.cs);
     if (c->scene.d_scene) (void)hipFree(c->scene.d_scene);
     if (c->scene.d_motion) (void)hipFree(c->scene.d_motion);
+    if (c->windows.d_table) (void)hipFree(c->windows.d_table);
     view_release(c);
     sdma_destroy(c);
     if (c->frames.ev0) (void)hipEventDestroy(c->frames.ev0);
@@ -102,6 +103,7 @@ static void knobs_from_env(rt_ctx::Knobs& k) {
     if (const char* e = getenv("RT_ORDER_POLICY")) k.order_policy = std::min(std::max(atoi(e), 0), 1);
     if (const char* e = getenv("RT_ACHRO_OFF")) k.achro_off = atoi(e) != 0;
     if (const char* e = getenv("RT_ACCUM_MAX_PASSES")) k.accum_max_passes = std::min(std::max(atoi(e), 1), 65536);
+    if (const char* e = getenv("RT_WINDOW_GRID_X")) k.window_grid_x = std::min(std::max(atoi(e), 1), 1 << 20);
 }
 
 extern "C" int rt_ctx_create(int device, rt_ctx** out) {
@@ -242,4 +244,60 @@ extern "C" int rt_set_motion(rt_ctx* c, const double* displacement, int n_sphere
     }
     if (c->scene.d_motion && memcmp(disp.data(), c->scene.disp.data(), disp.size() * sizeof(double)) == 0) return RT_OK;
     return motion_upload(c, std::move(disp));
+}
+
+// ---- the list of windows (include/rt_api.h, ABI 10: new symbols only) ---------------------------------------------
+// The table is built on the host (rt_group_plan.cpp rt_build_window_table, after rt_window_list_plan's checks) and
+// uploaded whole into an allocation of its own; the old table is freed only once the new one holds the list, so a call
+// that fails at any step — the checks, the allocation, the copy — leaves the previous list in force.
+extern "C" int rt_set_windows(rt_ctx* c, int W, int H, const rt_window* wins, int n, int layout) {
+    if (!c) return rt_fail(RT_EINVAL, "rt_set_windows: null context");
+    RT_HIP(hipSetDevice(c->device));
+    if (!wins && n == 0) {                                  // (NULL, 0) clears the list; the table's memory is kept
+        RT_HIP(hipDeviceSynchronize());
+        c->windows.set = false;
+        c->windows.list.clear();
+        c->windows.offset.clear();
+        return RT_OK;
+    }
+    // The list in force again (it was valid when it was set) keeps the device copy and costs no check: the host
+    // conveniences call this for every render.  The strides are the layout's, not the caller's.
+    if (c->windows.set && wins && W == c->windows.width && H == c->windows.height && layout == c->windows.layout &&
+        n >= 1 && (size_t)n == c->windows.list.size()) {
+        bool same = true;
+        for (int k = 0; k < n && same; ++k) {
+            const rt_window& o = c->windows.list[k];
+            same = wins[k].x0 == o.x0 && wins[k].y0 == o.y0 && wins[k].width == o.width && wins[k].height == o.height;
+        }
+        if (same) return RT_OK;
+    }
+    std::vector<unsigned char> table;
+    std::vector<rt_window> list;
+    uint32_t tiles[4];
+    uint64_t elements = 0;
+    const int rc = rt_build_window_table(W, H, wins, n, layout, &table, &list, tiles, &elements);
+    if (rc) return rc;
+    // Renders still in flight on any stream of this device read the old table: wait for them before it is freed.
+    RT_HIP(hipDeviceSynchronize());
+    unsigned char* d = nullptr;
+    if (hipMalloc(&d, table.size()) != hipSuccess) return rt_fail(RT_ENOMEM, "rt_set_windows: hipMalloc failed");
+    const hipError_t e_copy = hipMemcpy(d, table.data(), table.size(), hipMemcpyHostToDevice);
+    if (e_copy != hipSuccess) {
+        (void)hipFree(d);
+        return rt_fail(RT_EHIP, std::string("rt_set_windows: ") + hipGetErrorString(e_copy));
+    }
+    if (c->windows.d_table) (void)hipFree(c->windows.d_table);
+    c->windows.d_table = d;
+    c->windows.cap = table.size();
+    c->windows.width = W;
+    c->windows.height = H;
+    c->windows.layout = layout;
+    c->windows.list.swap(list);
+    c->windows.offset.resize((size_t)n);
+    const rt::DevWindow* e = reinterpret_cast<const rt::DevWindow*>(table.data() + rt::window_entries_at(n));
+    for (int k = 0; k < n; ++k) c->windows.offset[k] = e[k].base + ((int64_t)e[k].y0 * e[k].stride + e[k].x0);
+    for (int s = 0; s < 4; ++s) c->windows.tiles[s] = tiles[s];
+    c->windows.elements = elements;
+    c->windows.set = true;
+    return RT_OK;
 }

@@ -94,6 +94,19 @@ struct rt_ctx {
         std::vector<double> disp;              // the displacements in force, 3 per sphere (all 0: no motion)
     } scene;
 
+    // The list of windows in force (rt_set_windows, rt_context.hip; read by rt_sampled.hip's list renders and
+    // rt_frames.hip's host entry points).  rt_set_scene and rt_set_motion do not touch it.
+    struct Windows {
+        bool set = false;
+        int width = 0, height = 0, layout = 0;  // the frame the list is of; RT_WINDOWS_IN_PLACE / RT_WINDOWS_PACKED
+        std::vector<rt_window> list;            // the windows, each with its layout's stride
+        std::vector<int64_t> offset;            // the element of each window's pixel (0, 0) (rt_window_list_plan)
+        uint32_t tiles[4] = {0, 0, 0, 0};       // the launch's tile count at S = 1, 2, 4, 8
+        uint64_t elements = 0;                  // per-pixel elements of a buffer (rt_window_list_plan)
+        unsigned char* d_table = nullptr;       // rt_layout.hpp: four prefix columns, then the DevWindow entries
+        size_t cap = 0;
+    } windows;
+
     // The A/B knobs rt_ctx_create reads from the environment (rt_context.hip knobs_from_env; the measurements behind a
     // default stand where the knob is read).  Only order_mode changes later (rt_diag_tile_order).
     struct Knobs {
@@ -137,6 +150,12 @@ struct rt_ctx {
         // four times the rays, not measured).  A larger value saves little more: per launch the split costs one read
         // and one write of the sums (48 bytes per pixel).  Other scenes, depths and motions: not measured.
         int accum_max_passes = kAccumMaxPasses;
+        // RT_WINDOW_GRID_X: the most tiles one row of the list kernels' grid holds (rt_sampled.hpp window_list_grid: a
+        // list of more tiles folds into grid.y, the last row padded with waves that store nothing).  The images are the
+        // same bytes under every value; the tests set a small one to run the fold on a small frame.  1 .. 2^20; a launch
+        // has at most 65535 rows, so a list of more than 65535 times this many tiles gets longer rows than asked for
+        // (rt_sampled.hip window_list_params).
+        int window_grid_x = 1 << 20;
     } knobs;
 
     // The eye the per-eye records inside d_scene were prepared for (rt_plain.hip; rt_set_scene clears `valid`).
@@ -335,16 +354,19 @@ constexpr int kAccumCallPasses = 65536;
 int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                      int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
                      double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                     uint32_t* raycount2, void* stream, const rt_window* win = nullptr);
+                     uint32_t* raycount2, void* stream, const rt_window* win = nullptr, bool list = false);
 // The checks on the converging render's own arguments and its device render, as `who` (rt_frames.hip's host entry point too).
 int converge_arg_checks(const char* who, int passes, uint32_t min_passes, double tolerance);
 int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                         int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
                         double tolerance, double aperture, double light_size, double shutter, double* accum,
                         double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win = nullptr);
+                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win = nullptr,
+                        bool list = false);
 // `win` of the two above: nullptr runs the frame's kernels; a window (checked by window_arg_checks against the W x H
 // frame) runs the windowed ones on buffers whose pointers point at window pixel (0, 0) (rt_render_accum_window_dev).
+// `list` (with win = nullptr): the context's list of windows (rt_set_windows), which must be of the W x H frame, in one
+// launch of the list kernels per launch group, on buffers laid out as rt_window_list_plan says.
 int window_arg_checks(const char* who, const rt_window* win, int W, int H);
 
 // rt_frames.hip.  Waits for the SDMA copies in flight and destroys the engine path's signals (rt_ctx_destroy, after

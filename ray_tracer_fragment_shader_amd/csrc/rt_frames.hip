@@ -614,6 +614,165 @@ extern "C" int rt_render_converge_window(rt_ctx* c, const rt_scene* scene, const
         });
 }
 
+// ---- lists of windows of the accumulating and converging renders into host memory (include/rt_api.h) ----------------
+// Rows of every window of the context's list between a host array and its device copy, both laid out as the plan says
+// (window k's pixel (0, 0) at element offset[k], rows `stride` elements apart): only the windows' own elements move.  A
+// packed list is one run of elements, moved in one copy.
+static int window_list_copy(const rt_ctx* c, const WinBuf& b, bool to_device, hipStream_t st) {
+    const rt_ctx::Windows& L = c->windows;
+    if (L.layout == RT_WINDOWS_PACKED) {
+        const size_t bytes = (size_t)L.elements * b.elem;
+        if (to_device) RT_HIP(hipMemcpyAsync(b.dev, b.host, bytes, hipMemcpyHostToDevice, st));
+        else RT_HIP(hipMemcpyAsync(b.host, b.dev, bytes, hipMemcpyDeviceToHost, st));
+        return RT_OK;
+    }
+    for (size_t k = 0; k < L.list.size(); ++k) {
+        const rt_window& w = L.list[k];
+        const size_t off = (size_t)L.offset[k] * b.elem;
+        const size_t row = (size_t)w.width * b.elem, pitch = (size_t)w.stride * b.elem;
+        char *h = (char*)b.host + off, *d = (char*)b.dev + off;
+        if (to_device) RT_HIP(hipMemcpy2DAsync(d, pitch, h, pitch, row, (size_t)w.height, hipMemcpyHostToDevice, st));
+        else RT_HIP(hipMemcpy2DAsync(h, pitch, d, pitch, row, (size_t)w.height, hipMemcpyDeviceToHost, st));
+    }
+    return RT_OK;
+}
+
+// The pixels of the context's list.
+static uint64_t window_list_pixels(const rt_ctx* c) {
+    uint64_t n = 0;
+    for (const rt_window& w : c->windows.list) n += (uint64_t)w.width * (uint64_t)w.height;
+    return n;
+}
+
+// host_render_window for the context's list: device buffers of the plan's `elements` elements in the plan's layout.  The
+// counters of elements that belong to no window are zeroed before the render, so the ray sums are the list's.
+template <class Render, class Primary>
+static int host_render_windows(rt_ctx* c, WinBuf* b, int n_extra, rt_stats* stats, Render&& render, Primary&& primary) {
+    RT_HIP(hipSetDevice(c->device));
+    int rc;
+    const size_t nel = (size_t)c->windows.elements;
+    for (int k = 0; k < 3 + n_extra; ++k)
+        if ((b[k].host || k >= 3) && (rc = ctx_buffer(c, b[k].k, nel * b[k].elem, &b[k].dev)) != RT_OK) return rc;
+    void *d_rc = nullptr, *d_sums = nullptr;
+    if (stats && ((rc = ctx_buffer(c, 3, nel * 8, &d_rc)) || (rc = ctx_buffer(c, 4, 2 * sizeof(unsigned long long), &d_sums))))
+        return rc;
+    if (stats) RT_HIP(hipMemsetAsync(d_rc, 0, nel * 8, c->frames.rs));
+    RT_HIP(hipEventRecord(c->frames.ev0, c->frames.rs));
+    if ((rc = render((uint32_t*)d_rc)) != RT_OK) return rc;
+    RT_HIP(hipEventRecord(c->frames.ev1, c->frames.rs));
+    if (stats && (rc = queue_raysum(c, nel, 2, (uint32_t*)d_rc, (unsigned long long*)d_sums))) return rc;
+    for (int k = 0; k < 3 + n_extra; ++k)
+        if (b[k].host && (rc = window_list_copy(c, b[k], false, c->frames.rs))) return rc;
+    RT_HIP(hipStreamSynchronize(c->frames.rs));
+    uint64_t prim = 0;
+    if ((rc = primary(&prim)) != RT_OK || !stats) return rc;
+    if ((rc = read_stats(c, nel, (const unsigned long long*)d_sums, stats)) != RT_OK) return rc;
+    stats->reflect_rays = stats->primary_rays + stats->reflect_rays - prim;
+    stats->primary_rays = prim;
+    return RT_OK;
+}
+
+// rt_render_accum for a list of windows: the checks first, then the list, the scene and the motion are set, only the windows' rows of `accum` go up
+// (first_pass > 0) and only the windows' rows of every array come back.
+extern "C" int rt_render_accum_windows(rt_ctx* c, const rt_scene* scene, const double* displacement,
+                                       const rt_camera* cam, const rt_camera_motion* motion, int W, int H, int depth,
+                                       int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes,
+                                       double aperture, double light_size, double shutter, double* accum, float* rgba32f,
+                                       uint8_t* rgba8, double* rgb64f, rt_stats* stats, const rt_window* wins, int n,
+                                       int layout) {
+    const char* who = "rt_render_accum_windows";
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc) return rc;
+    if ((rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (passes < 1 || passes > kAccumCallPasses)
+        return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
+    if ((uint64_t)first_pass + (uint64_t)passes > (1ull << 31))
+        return rt_fail(RT_EINVAL, std::string(who) + ": first_pass + passes must not exceed 2^31");
+    // the list first: a bad one is rejected before the scene changes; the list in force again costs no check
+    if (!wins) return rt_fail(RT_EINVAL, std::string(who) + ": null wins");
+    if ((rc = rt_set_windows(c, W, H, wins, n, layout))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    WinBuf b[4] = {{0, 16, rgba32f, nullptr}, {1, 4, rgba8, nullptr}, {2, 24, rgb64f, nullptr},
+                   {rt_ctx::Frames::kBufAccum, 24, accum, nullptr}};
+    return host_render_windows(
+        c, b, 1, stats,
+        [&](uint32_t* d_rc) {
+            int r;
+            if (first_pass > 0 && (r = window_list_copy(c, b[3], true, c->frames.rs))) return r;
+            return accum_render_dev("rt_render_accum_windows_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                                    first_pass, passes, aperture, light_size, shutter, (double*)b[3].dev,
+                                    (float*)b[0].dev, (uint8_t*)b[1].dev, (double*)b[2].dev, d_rc, c->frames.rs, nullptr,
+                                    true);
+        },
+        [&](uint64_t* prim) {
+            *prim = window_list_pixels(c) * (uint64_t)samples * (uint64_t)samples * (uint64_t)passes;
+            return RT_OK;
+        });
+}
+
+// rt_render_converge for a list of windows: the windows' rows of the three state arrays go up and come back; *n_active
+// and the primary rays behind *stats are the list's.
+extern "C" int rt_render_converge_windows(rt_ctx* c, const rt_scene* scene, const double* displacement,
+                                          const rt_camera* cam, const rt_camera_motion* motion, int W, int H, int depth,
+                                          int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
+                                          double tolerance, double aperture, double light_size, double shutter,
+                                          double* accum, double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8,
+                                          double* rgb64f, rt_stats* stats, uint64_t* n_active, const rt_window* wins,
+                                          int n, int layout) {
+    const char* who = "rt_render_converge_windows";
+    int rc = sampled_host_checks(who, c, W, H, samples);
+    if (rc) return rc;
+    if ((rc = lens_arg_checks(kLensMotion, who, aperture, light_size, shutter))) return rc;
+    if ((rc = jitter_arg_checks(who, jitter))) return rc;
+    if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
+    if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
+    if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
+    if ((rc = converge_arg_checks(who, passes, min_passes, tolerance))) return rc;
+    // the list first: a bad one is rejected before the scene changes; the list in force again costs no check
+    if (!wins) return rt_fail(RT_EINVAL, std::string(who) + ": null wins");
+    if ((rc = rt_set_windows(c, W, H, wins, n, layout))) return rc;
+    if ((rc = rt_set_scene(c, scene))) return rc;           // no device work when the scene is unchanged
+    if ((rc = rt_set_motion(c, displacement, displacement ? scene->n_spheres : 0))) return rc;   // nor when the motion is
+    const auto passes_held = [&]() {                        // the pixel-passes the list's state holds
+        uint64_t held = 0;
+        for (size_t k = 0; k < c->windows.list.size(); ++k) {
+            const rt_window& w = c->windows.list[k];
+            const uint32_t* p = count + c->windows.offset[k];
+            for (int j = 0; j < w.height; ++j)
+                for (int i = 0; i < w.width; ++i) held += p[(size_t)j * (size_t)w.stride + (size_t)i];
+        }
+        return held;
+    };
+    const uint64_t before = passes_held();
+    WinBuf b[6] = {{0, 16, rgba32f, nullptr}, {1, 4, rgba8, nullptr}, {2, 24, rgb64f, nullptr},
+                   {rt_ctx::Frames::kBufAccum, 24, accum, nullptr}, {rt_ctx::Frames::kBufAccum2, 24, accum2, nullptr},
+                   {rt_ctx::Frames::kBufCount, 4, count, nullptr}};
+    void* d_active = nullptr;
+    if ((rc = ctx_buffer(c, rt_ctx::Frames::kBufActive, 4, &d_active))) return rc;
+    return host_render_windows(
+        c, b, 3, stats,
+        [&](uint32_t* d_rc) {
+            int r;
+            for (int k = 3; k < 6; ++k)
+                if ((r = window_list_copy(c, b[k], true, c->frames.rs))) return r;
+            return converge_render_dev("rt_render_converge_windows_dev", c, cam, motion, W, H, depth, samples, jitter,
+                                       seed, passes, min_passes, tolerance, aperture, light_size, shutter,
+                                       (double*)b[3].dev, (double*)b[4].dev, (uint32_t*)b[5].dev, (float*)b[0].dev,
+                                       (uint8_t*)b[1].dev, (double*)b[2].dev, d_rc, (uint32_t*)d_active, c->frames.rs,
+                                       nullptr, true);
+        },
+        [&](uint64_t* prim) {
+            uint32_t live = 0;
+            RT_HIP(hipMemcpy(&live, d_active, sizeof(live), hipMemcpyDeviceToHost));
+            if (n_active) *n_active = live;
+            *prim = (passes_held() - before) * (uint64_t)samples * (uint64_t)samples;
+            return RT_OK;
+        });
+}
+
 // rt_render for an adaptively sampled frame of the lens family: rt_set_scene, rt_set_motion (nullptr: none), then
 // rt_render_lens_adaptive_dev into the context's device buffers (rt_render_adaptive's two among them), then the copies
 // back.

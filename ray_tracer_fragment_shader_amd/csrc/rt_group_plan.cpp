@@ -1,7 +1,8 @@
 // rt_group_plan.cpp — the host-side decisions of rt_render_multi (rt_group.cpp) that involve no device: what each
 // rank of a row-banded frame sends, what rank 0 receives and where it lands, and the scene agreement of a
-// one-process-per-GPU group.  Plain C++ (no HIP), so the CPU tests drive the same code from two gloo processes
-// (tests/test_distributed.py) and the sanitizer leg links it.
+// one-process-per-GPU group; and the plan of a list of windows (rt_window_list_plan, the table of rt_set_windows).
+// Plain C++ (no HIP), so the CPU tests drive the same code from two gloo processes (tests/test_distributed.py) and the
+// sanitizer leg links it (it runs the group plan; the list plan is run by tests/test_window_list_plan.py).
 //
 // The reference renders one frame on one thread (rayTraceScreen, Hw4/MySdlApplication.cpp:1251-1324); the whole
 // multi-GPU split is this build's.  Pixels are independent (rayTraceRay :1184-1249 reads only the
@@ -125,6 +126,94 @@ extern "C" int rt_scene_fingerprint(const rt_scene* scene, uint64_t* out) {
     int rc = rt_build_dev_scene(scene, &blob);
     if (rc) return rc;
     *out = rt_blob_fingerprint(blob);
+    return RT_OK;
+}
+
+// ---- lists of windows (rt_api.h: rt_window_list_plan; the table of rt_set_windows) ----------------------------------
+namespace {
+
+// Tiles of 8 x 8 samples a w x h window has at S = 1 << s.
+uint64_t window_tiles(const rt_window& w, int s) {
+    return (uint64_t)((((int64_t)w.width << s) + 7) >> 3) * (uint64_t)((((int64_t)w.height << s) + 7) >> 3);
+}
+
+// The checks of rt_window_list_plan, as `who`.
+int window_list_checks(const char* who, int W, int H, const rt_window* wins, int n, int layout) {
+    const std::string me = std::string(who) + ": ";
+    if (n < 1 || n > RT_MAX_WINDOWS) return rt_fail(RT_EINVAL, me + "n must lie in 1 .. RT_MAX_WINDOWS");
+    if (layout != RT_WINDOWS_IN_PLACE && layout != RT_WINDOWS_PACKED) return rt_fail(RT_EINVAL, me + "unknown layout");
+    if (W <= 0 || H <= 0 || (long long)W * H > (1LL << 31))
+        return rt_fail(RT_EINVAL, me + "bad image size (width, height)");
+    if (!wins) return rt_fail(RT_EINVAL, me + "null wins");
+    for (int k = 0; k < n; ++k) {
+        const rt_window& w = wins[k];
+        if (w.x0 < 0 || w.y0 < 0 || w.width < 1 || w.height < 1 || (long long)w.x0 + w.width > W ||
+            (long long)w.y0 + w.height > H)
+            return rt_fail(RT_EINVAL, me + "window " + std::to_string(k) + " is empty or leaves the frame (window)");
+    }
+    // (n <= 4096: every pair, 8.4 million integer comparisons at the most)
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b) {
+            const rt_window &p = wins[a], &q = wins[b];
+            if (p.x0 < q.x0 + q.width && q.x0 < p.x0 + p.width && p.y0 < q.y0 + q.height && q.y0 < p.y0 + p.height)
+                return rt_fail(RT_EINVAL, me + "windows " + std::to_string(a) + " and " + std::to_string(b) +
+                                              " share a frame pixel (window)");
+        }
+    return RT_OK;
+}
+
+int64_t window_stride(const rt_window& w, int W, int layout) { return layout == RT_WINDOWS_PACKED ? w.width : W; }
+
+}  // namespace
+
+extern "C" int rt_window_list_plan(int width, int height, int samples, const rt_window* wins, int n, int layout,
+                                   uint32_t* first_tile, int64_t* offset, uint64_t* elements) {
+    const char* who = "rt_window_list_plan";
+    int s = -1;
+    for (int q = 0; q < 4; ++q)
+        if (samples == 1 << q) s = q;
+    if (s < 0) return rt_fail(RT_EINVAL, std::string(who) + ": samples must be 1, 2, 4 or 8");
+    if (const int rc = window_list_checks(who, width, height, wins, n, layout)) return rc;
+    // a tile holds at least one pixel of its window, so the tiles number at most width height <= 2^31
+    uint64_t tiles = 0, area = 0;
+    for (int k = 0; k < n; ++k) {
+        if (first_tile) first_tile[k] = (uint32_t)tiles;
+        if (offset)
+            offset[k] = layout == RT_WINDOWS_PACKED ? (int64_t)area : (int64_t)wins[k].y0 * width + wins[k].x0;
+        tiles += window_tiles(wins[k], s);
+        area += (uint64_t)wins[k].width * (uint64_t)wins[k].height;
+    }
+    if (first_tile) first_tile[n] = (uint32_t)tiles;
+    if (elements) *elements = layout == RT_WINDOWS_PACKED ? area : (uint64_t)width * (uint64_t)height;
+    return RT_OK;
+}
+
+int rt_build_window_table(int width, int height, const rt_window* wins, int n, int layout,
+                          std::vector<unsigned char>* table, std::vector<rt_window>* list, uint32_t tiles[4],
+                          uint64_t* elements) {
+    if (const int rc = window_list_checks("rt_set_windows", width, height, wins, n, layout)) return rc;
+    table->assign(rt::window_table_bytes(n), 0);
+    list->assign(wins, wins + n);
+    uint32_t* prefix = reinterpret_cast<uint32_t*>(table->data());
+    rt::DevWindow* e = reinterpret_cast<rt::DevWindow*>(table->data() + rt::window_entries_at(n));
+    uint64_t area = 0, sum[4] = {0, 0, 0, 0};
+    for (int k = 0; k < n; ++k) {
+        const rt_window& w = wins[k];
+        const int64_t stride = window_stride(w, width, layout);
+        const int64_t off = layout == RT_WINDOWS_PACKED ? (int64_t)area : (int64_t)w.y0 * width + w.x0;
+        (*list)[k].stride = (int32_t)stride;
+        e[k] = rt::DevWindow{w.x0, w.y0, w.width, w.height, (int32_t)stride, 0, off - ((int64_t)w.y0 * stride + w.x0)};
+        for (int s = 0; s < 4; ++s) {
+            prefix[(size_t)s * (n + 1) + k] = (uint32_t)sum[s];
+            sum[s] += window_tiles(w, s);
+        }
+        area += (uint64_t)w.width * (uint64_t)w.height;
+    }
+    for (int s = 0; s < 4; ++s) {
+        prefix[(size_t)s * (n + 1) + n] = (uint32_t)sum[s];
+        tiles[s] = (uint32_t)sum[s];
+    }
+    *elements = layout == RT_WINDOWS_PACKED ? area : (uint64_t)width * (uint64_t)height;
     return RT_OK;
 }
 

@@ -25,6 +25,13 @@ int rt_build_dev_scene(const rt_scene* scene, std::vector<unsigned char>* blob);
 int rt_build_motion(const std::vector<unsigned char>& blob, const double* cl, const double* disp, int n,
                     std::vector<unsigned char>* out);
 
+// The window table (rt_layout.hpp DevWindow) of the list wins[n] of the width x height frame under `layout`, after
+// rt_window_list_plan's checks as rt_set_windows (rt_group_plan.cpp): *list is the list with the layout's strides,
+// tiles[s] the launch's tile count at S = 1 << s, *elements the plan's.
+int rt_build_window_table(int width, int height, const rt_window* wins, int n, int layout,
+                          std::vector<unsigned char>* table, std::vector<rt_window>* list, uint32_t tiles[4],
+                          uint64_t* elements);
+
 // rayTraceScreen basis (MySdlApplication.cpp:1270-1277): right = normalize(LD x up),
 // up' = normalize(right x LD), LD = look_at - eye.
 void rt_camera_basis(const rt_camera* cam, double right[3], double upp[3]);

@@ -264,6 +264,21 @@ inline constexpr size_t motion_bytes_for(int ns) {
     return sizeof(DevMotion) + (sizeof(DevMotionSphere) + sizeof(DevSphereF)) * (size_t)ns;
 }
 
+// The window table of a context (rt_set_windows; an allocation of its own), read by rt_accum_windows_kernel and
+// rt_converge_windows_kernel: four prefix columns of n + 1 words each, column s holding rt_window_list_plan's first_tile
+// at S = 1 << s (what a wave searches for its flat tile number), then — 16-byte aligned — one DevWindow per window
+// (what the wave loads once it has found its window).  Nothing in it depends on S but the choice of the column, which
+// the host makes; prefixes and entries are plain arrays, so a later change may write them on the device.
+struct DevWindow {
+    int32_t x0, y0, width, height;     // the window, in output pixels of the frame
+    int32_t stride;                    // the row stride of the layout, in elements
+    int32_t pad;
+    int64_t base;                      // offset[k] - (y0 stride + x0): the element frame pixel (0, 0) would have, so
+                                       // that frame pixel (X, Y) of the window is element base + Y stride + X
+};
+inline constexpr size_t window_entries_at(int n) { return (4 * ((size_t)n + 1) * sizeof(uint32_t) + 15) / 16 * 16; }
+inline constexpr size_t window_table_bytes(int n) { return window_entries_at(n) + (size_t)n * sizeof(DevWindow); }
+
 }  // namespace rt
 
 // rt_render_screen's chunk (rt_screen.cpp), read by the screen mode of rt_trace_rays_kernel: one pixel's screen point

@@ -397,6 +397,22 @@ static void window_fold(const rt_window& w, int samples, SampledLaunch* L) {
     L->orc2 = back(L->orc2, 8);
 }
 
+// The context's list of windows as the list kernels take it (rt_sampled.hpp WindowListParams), after the checks of the
+// list renders: a list must be set and must be of the W x H frame.
+static int window_list_params(const char* who, const rt_ctx* c, int W, int H, int s, WindowListParams* out) {
+    if (!c->windows.set) return rt_fail(RT_EINVAL, std::string(who) + ": no list of windows set (window)");
+    if (W != c->windows.width || H != c->windows.height)
+        return rt_fail(RT_EINVAL, std::string(who) + ": width, height are not the frame of the list of windows (window)");
+    const int n = (int)c->windows.list.size();
+    out->prefix = reinterpret_cast<const uint32_t*>(c->windows.d_table) + (size_t)s * (size_t)(n + 1);
+    out->entries = reinterpret_cast<const rt::DevWindow*>(c->windows.d_table + rt::window_entries_at(n));
+    out->n = (uint32_t)n;
+    out->tiles = c->windows.tiles[s];
+    // the grid's row length: the knob's, raised where the list's tiles would otherwise need more than 65535 rows
+    out->grid_x = std::max((uint32_t)c->knobs.window_grid_x, (out->tiles + 65534u) / 65535u);
+    return RT_OK;
+}
+
 // ---- progressive accumulation (include/rt_api.h) -----------------------------------------------------------------------
 // Passes first_pass .. first_pass + passes - 1 of the shutter render (seed + p each) added to `accum` in the contract's
 // order by rt_accum_kernel: the shutter render's checks and launch record, the call's own checks, then launches of at most
@@ -409,11 +425,12 @@ static void window_fold(const rt_window& w, int samples, SampledLaunch* L) {
 int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
                      int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass, int passes, double aperture,
                      double light_size, double shutter, double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                     uint32_t* raycount2, void* stream, const rt_window* win) {
+                     uint32_t* raycount2, void* stream, const rt_window* win, bool list) {
     SampledLaunch L{};
     int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
                             rgba32f, rgba8, rgb64f, raycount2, stream, &L);
     if (rc || (win && (rc = window_arg_checks(who, win, W, H)))) return rc;
+    if (list && (rc = window_list_params(who, c, W, H, L.P.ss_log2, &L.windows))) return rc;
     if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
     if (passes < 1 || passes > kAccumCallPasses)
         return rt_fail(RT_EINVAL, std::string(who) + ": passes must lie in 1 .. 65536");
@@ -437,10 +454,14 @@ int accum_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const rt_
         L.o8 = last ? rgba8 : nullptr;
         L.o64 = last ? rgb64f : nullptr;
         const hipError_t e = with_depth(depth, [&](auto B) {
-            return win ? launch_accum_window<decltype(B)::value>(L) : launch_accum<decltype(B)::value>(L);
+            return list  ? launch_accum_windows<decltype(B)::value>(L)
+                   : win ? launch_accum_window<decltype(B)::value>(L)
+                         : launch_accum<decltype(B)::value>(L);
         });
         if (e != hipSuccess)
-            return rt_fail(RT_EHIP, std::string(win ? "rt_accum_window_kernel: " : "rt_accum_kernel: ") + hipGetErrorString(e));
+            return rt_fail(RT_EHIP, std::string(list  ? "rt_accum_windows_kernel: "
+                                                : win ? "rt_accum_window_kernel: "
+                                                      : "rt_accum_kernel: ") + hipGetErrorString(e));
     }
     return RT_OK;
 }
@@ -476,11 +497,12 @@ int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const 
                         int depth, int samples, int jitter, uint32_t seed, int passes, uint32_t min_passes,
                         double tolerance, double aperture, double light_size, double shutter, double* accum,
                         double* accum2, uint32_t* count, float* rgba32f, uint8_t* rgba8, double* rgb64f,
-                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win) {
+                        uint32_t* raycount2, uint32_t* active, void* stream, const rt_window* win, bool list) {
     SampledLaunch L{};
     int rc = shutter_launch(who, c, cam, motion, W, H, depth, samples, jitter, seed, aperture, light_size, shutter,
                             rgba32f, rgba8, rgb64f, raycount2, stream, &L);
     if (rc || (win && (rc = window_arg_checks(who, win, W, H)))) return rc;
+    if (list && (rc = window_list_params(who, c, W, H, L.P.ss_log2, &L.windows))) return rc;
     if (!accum) return rt_fail(RT_EINVAL, std::string(who) + ": null accum");
     if (!accum2) return rt_fail(RT_EINVAL, std::string(who) + ": null accum2");
     if (!count) return rt_fail(RT_EINVAL, std::string(who) + ": null count");
@@ -508,11 +530,14 @@ int converge_render_dev(const char* who, rt_ctx* c, const rt_camera* cam, const 
         L.o64 = L.last ? rgb64f : nullptr;
         L.active = L.last ? active : nullptr;
         const hipError_t e = with_depth(depth, [&](auto B) {
-            return win ? launch_converge_window<decltype(B)::value>(L) : launch_converge<decltype(B)::value>(L);
+            return list  ? launch_converge_windows<decltype(B)::value>(L)
+                   : win ? launch_converge_window<decltype(B)::value>(L)
+                         : launch_converge<decltype(B)::value>(L);
         });
         if (e != hipSuccess)
-            return rt_fail(RT_EHIP, std::string(win ? "rt_converge_window_kernel: " : "rt_converge_kernel: ") +
-                                        hipGetErrorString(e));
+            return rt_fail(RT_EHIP, std::string(list  ? "rt_converge_windows_kernel: "
+                                                : win ? "rt_converge_window_kernel: "
+                                                      : "rt_converge_kernel: ") + hipGetErrorString(e));
     }
     return RT_OK;
 }
@@ -551,6 +576,28 @@ extern "C" int rt_render_converge_window_dev(rt_ctx* c, const rt_camera* cam, co
     return converge_render_dev(who, c, cam, motion, W, H, depth, samples, jitter, seed, passes, min_passes, tolerance,
                                aperture, light_size, shutter, accum, accum2, count, rgba32f, rgba8, rgb64f, raycount2,
                                active, stream, win);
+}
+
+// The list entry points: the same host code with the context's list of windows and the list kernels.
+extern "C" int rt_render_accum_windows_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W, int H,
+                                           int depth, int samples, int jitter, uint32_t seed, uint32_t first_pass,
+                                           int passes, double aperture, double light_size, double shutter,
+                                           double* accum, float* rgba32f, uint8_t* rgba8, double* rgb64f,
+                                           uint32_t* raycount2, void* stream) {
+    return accum_render_dev("rt_render_accum_windows_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                            first_pass, passes, aperture, light_size, shutter, accum, rgba32f, rgba8, rgb64f, raycount2,
+                            stream, nullptr, true);
+}
+
+extern "C" int rt_render_converge_windows_dev(rt_ctx* c, const rt_camera* cam, const rt_camera_motion* motion, int W,
+                                              int H, int depth, int samples, int jitter, uint32_t seed, int passes,
+                                              uint32_t min_passes, double tolerance, double aperture, double light_size,
+                                              double shutter, double* accum, double* accum2, uint32_t* count,
+                                              float* rgba32f, uint8_t* rgba8, double* rgb64f, uint32_t* raycount2,
+                                              uint32_t* active, void* stream) {
+    return converge_render_dev("rt_render_converge_windows_dev", c, cam, motion, W, H, depth, samples, jitter, seed,
+                               passes, min_passes, tolerance, aperture, light_size, shutter, accum, accum2, count,
+                               rgba32f, rgba8, rgb64f, raycount2, active, stream, nullptr, true);
 }
 
 // ---- the adaptive lens render (include/rt_api.h) --------------------------------------------------------------------

@@ -957,6 +957,297 @@ __global__ __launch_bounds__(64) void rt_converge_window_kernel(const DevScene* 
     }
 }
 
+// ---- Lists of windows (rt_render_accum_windows_dev, rt_render_converge_windows_dev, include/rt_api.h): the pixels of any
+// set of disjoint windows of the frame in one launch, byte for byte what the un-windowed kernels give them. ----
+
+// What a list kernel gets beside its parent's arguments: the prefix column of the launch's S (n + 1 words: the tiles
+// before each window, then the launch's tile count), the entries (rt_layout.hpp DevWindow), the number of windows, the
+// launch's tile count and the grid's row length (window_list_grid).
+struct WindowListParams {
+    const uint32_t* __restrict__ prefix;
+    const rt::DevWindow* __restrict__ entries;
+    uint32_t n, tiles, grid_x;
+};
+
+// What a wave of a list kernel keeps of its window: rt_accum_window_kernel's W.sx0 + 8 tx and W.sy0 + 8 ty already summed
+// (the wave's sample origin in the frame), the window's far corner in samples, its stride, and the element number frame
+// pixel (0, 0) would have (signed: a packed window far up the frame lies early in the buffers).
+struct WindowTile {
+    int32_t ox, oy;
+    int32_t sx1, sy1;
+    int32_t stride;
+    int64_t base;
+    bool pad;                                  // a wave past the launch's tile count (the fold's last row): stores nothing
+};
+
+// The wave's window and its tile within it, from its flat tile number: a binary search of the prefix column (prefix[k]
+// <= flat < prefix[k + 1]: no window is empty, so the column rises strictly; at most 12 steps for 4096 windows), one load
+// of that entry, one division by the window's tiles per row.  Everything here is formed from the block's number and
+// kernel arguments alone, so it is wave-uniform: the loads are scalar loads and the results scalar registers
+// (readfirstlane where a division went through the vector unit).  It runs once, before the first trace.
+__device__ __forceinline__ WindowTile window_tile_of(const WindowListParams& T, int s) {
+    uint32_t flat = blockIdx.y * T.grid_x + blockIdx.x;
+    WindowTile r;
+    r.pad = flat >= T.tiles;
+    if (r.pad) flat = T.tiles - 1;                          // a valid tile to trace; nothing of it is stored
+    uint32_t lo = 0, hi = T.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (T.prefix[mid] <= flat) lo = mid;
+        else hi = mid;
+    }
+    const rt::DevWindow e = T.entries[lo];
+    const uint32_t t = flat - T.prefix[lo];
+    const uint32_t tiles_x = (uint32_t)(((e.width << s) + 7) >> 3);
+    const uint32_t ty = (uint32_t)__builtin_amdgcn_readfirstlane((int)(t / tiles_x));
+    const uint32_t tx = t - ty * tiles_x;
+    r.ox = (e.x0 << s) + (int32_t)(tx * 8u);
+    r.oy = (e.y0 << s) + (int32_t)(ty * 8u);
+    r.sx1 = (e.x0 + e.width) << s;
+    r.sy1 = (e.y0 + e.height) << s;
+    r.stride = e.stride;
+    r.base = e.base;
+    return r;
+}
+
+// rt_accum_window_kernel statement for statement, but for where the wave's tile comes from: window_tile_of in place of
+// (W, blockIdx), and the element number k = base + (lr >> s) stride + (i >> s) with the list's signed base.  The waves
+// of one window tile it from its own origin exactly as the single-window kernel's do, so a lane holds the same sample
+// either way.  A kernel of its own, as rt_accum_window_kernel is.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_accum_windows_kernel(const DevScene* __restrict__ S,
+                                                              const DevMotion* __restrict__ M, RenderParams P,
+                                                              JitterParams Q, ShutterParams C, AccumParams N,
+                                                              WindowListParams T, double aperture, double light_size,
+                                                              double shutter, double* accum, void* o32, void* o8,
+                                                              double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl, sj = s + jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const WindowTile W = window_tile_of(T, s);
+    // (rt_accum_kernel: the lane's coordinates are formed again wherever they are read)
+    struct Lane { int i, lr, a, b, q; bool owner; size_t k; };
+    const auto lane_of = [&]() {
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        const int x = l & 7, y = l >> 3;
+        Lane r;
+        r.i = W.ox + x;
+        r.lr = W.oy + y;
+        r.a = x & S1;
+        r.b = y & S1;
+        r.q = ((y >> s) << (3 - s)) + (x >> s);          // the pixel's number in the tile
+        r.owner = r.a == 0 && r.b == 0 && r.i < W.sx1 && r.lr < W.sy1 && !W.pad;
+        r.k = (size_t)(W.base + (int64_t)(r.lr >> s) * (int64_t)W.stride + (int64_t)(r.i >> s));   // read under `owner` only
+        return r;
+    };
+    const int npix = 64 >> (2 * s);
+    double* park_rgb = reinterpret_cast<double*>(smem + (TREE ? 0 : slot_bytes(B, TRANSP, 64)));
+    uint32_t* park_rc = reinterpret_cast<uint32_t*>(park_rgb + 3 * npix);
+    {
+        const Lane ln = lane_of();
+        if (ln.owner) {
+            d3 acc = mk(0.0, 0.0, 0.0);
+            uint32_t seg_sum = 0, sh_sum = 0;
+            if (N.first > 0) acc = mk(accum[3 * ln.k], accum[3 * ln.k + 1], accum[3 * ln.k + 2]);
+            if (N.first > N.call_first && orc2) { seg_sum = orc2[2 * ln.k]; sh_sum = orc2[2 * ln.k + 1]; }
+            park_rgb[ln.q] = acc.x; park_rgb[npix + ln.q] = acc.y; park_rgb[2 * npix + ln.q] = acc.z;
+            park_rc[ln.q] = seg_sum; park_rc[npix + ln.q] = sh_sum;
+        }
+    }
+    for (uint32_t t = 0; t < N.count; ++t) {
+        const uint32_t p = N.first + t;
+        const Lane ln = lane_of();
+        const int i = ln.i, lr = ln.lr, a = ln.a, b = ln.b;
+        const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+        const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed + p);
+        const int n = a + (b << s);                         // time index a + S b
+        const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                        ldexp(1.0, -(s + sj)));
+        // the camera of the lane's time
+        const d3 eye = add(ld3(P.eye), scl(sigma, ld3(C.eye_move)));
+        const d3 look = add(ld3(P.look), scl(sigma, ld3(C.look_move)));
+        const d3 ld = sub(look, eye);
+        const d3 right = cam_normalize(cross(ld, ld3(C.up)));
+        const d3 upp = cam_normalize(cross(right, ld));
+        // screen_point of the fine camera at that time
+        const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+        const d3 sp = add(add(look, scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                          scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+        const double inv_sj = ldexp(1.0, -sj);
+        const auto t_of = [&](int c, int kd) { return (double)(2 * ((c << jl) + kd) + 1 - (1 << sj)) * inv_sj; };
+        const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+        const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+        const d3 e = add(add(eye, scl(aperture * ta, right)), scl(aperture * tb, upp));
+        const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+        V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+        const Motion mo{sigma, M};
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                                LightShift{light_size * ga, light_size * gb}, &mo);
+        reduce_samples(s, 8, col, seg, sh);
+        const Lane after = lane_of();
+        if (after.owner) {
+            const int q = after.q;
+            const d3 acc = p == 0 ? col : add(mk(park_rgb[q], park_rgb[npix + q], park_rgb[2 * npix + q]), col);
+            park_rgb[q] = acc.x; park_rgb[npix + q] = acc.y; park_rgb[2 * npix + q] = acc.z;
+            park_rc[q] += seg;
+            park_rc[npix + q] += sh;
+        }
+    }
+    const Lane ln = lane_of();
+    if (ln.owner) {
+        const size_t k = ln.k;
+        const int q = ln.q;
+        const d3 acc = mk(park_rgb[q], park_rgb[npix + q], park_rgb[2 * npix + q]);
+        const uint32_t seg_sum = park_rc[q], sh_sum = park_rc[npix + q];
+        accum[3 * k] = acc.x; accum[3 * k + 1] = acc.y; accum[3 * k + 2] = acc.z;
+        if (o32 || o8 || o64 || orc2) {
+            const double cnt = (double)(N.first + N.count);
+            store_sampled(P, k, mk(acc.x / cnt, acc.y / cnt, acc.z / cnt), seg_sum, sh_sum, o32, o8, o64, orc2);
+        }
+    }
+}
+
+// rt_converge_window_kernel statement for statement with rt_accum_windows_kernel's tile lookup and element number.
+// *active is added to by every wave of every window, so it counts the list's pixels.
+template <int B, bool TRANSP, bool TREE>
+__global__ __launch_bounds__(64) void rt_converge_windows_kernel(const DevScene* __restrict__ S,
+                                                                 const DevMotion* __restrict__ M, RenderParams P,
+                                                                 JitterParams Q, ShutterParams C, ConvergeParams N,
+                                                                 WindowListParams T, double aperture, double light_size,
+                                                                 double shutter, double* accum, double* accum2,
+                                                                 uint32_t* count, uint32_t* active, void* o32, void* o8,
+                                                                 double* o64, uint32_t* orc2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int s = P.ss_log2, S1 = (1 << s) - 1, jl = Q.jl, sj = s + jl;
+    SceneView V = view_of(S, S, S->n_padded, S->n_stride, S->n_lights);
+    const WindowTile W = window_tile_of(T, s);
+    // (rt_accum_kernel: the lane's coordinates are formed again wherever they are read)
+    struct Lane { int i, lr, a, b, q; bool first, owner; size_t k; };
+    const auto lane_of = [&]() {
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        const int x = l & 7, y = l >> 3;
+        Lane r;
+        r.i = W.ox + x;
+        r.lr = W.oy + y;
+        r.a = x & S1;
+        r.b = y & S1;
+        r.q = ((y >> s) << (3 - s)) + (x >> s);          // the pixel's number in the tile
+        r.first = r.a == 0 && r.b == 0;
+        r.owner = r.first && r.i < W.sx1 && r.lr < W.sy1 && !W.pad;
+        r.k = (size_t)(W.base + (int64_t)(r.lr >> s) * (int64_t)W.stride + (int64_t)(r.i >> s));   // read under `owner` only
+        return r;
+    };
+    const int npix = 64 >> (2 * s);
+    double* park_rgb = reinterpret_cast<double*>(smem + (TREE ? 0 : slot_bytes(B, TRANSP, 64)));
+    double* park_sq = park_rgb + 3 * npix;
+    uint32_t* park_rc = reinterpret_cast<uint32_t*>(park_sq + 3 * npix);
+    uint32_t* park_n = park_rc + 2 * npix;
+    const auto parked = [&](const double* p, int q) { return mk(p[q], p[npix + q], p[2 * npix + q]); };
+    const auto park = [&](double* p, int q, d3 v) { p[q] = v.x; p[npix + q] = v.y; p[2 * npix + q] = v.z; };
+    {
+        // every pixel slot of the tile is filled: a slot outside the window holds n = 0 and is never live
+        const Lane ln = lane_of();
+        if (ln.first) {
+            d3 acc = mk(0.0, 0.0, 0.0), sq = mk(0.0, 0.0, 0.0);
+            uint32_t n = 0, seg_sum = 0, sh_sum = 0;
+            if (ln.owner) {
+                n = count[ln.k];
+                if (n > 0) {                                // n = 0: accum and accum2 are not read
+                    acc = mk(accum[3 * ln.k], accum[3 * ln.k + 1], accum[3 * ln.k + 2]);
+                    sq = mk(accum2[3 * ln.k], accum2[3 * ln.k + 1], accum2[3 * ln.k + 2]);
+                }
+                if (N.later && orc2) { seg_sum = orc2[2 * ln.k]; sh_sum = orc2[2 * ln.k + 1]; }
+            }
+            park(park_rgb, ln.q, acc);
+            park(park_sq, ln.q, sq);
+            park_rc[ln.q] = seg_sum; park_rc[npix + ln.q] = sh_sum;
+            park_n[ln.q] = n;
+        }
+    }
+    bool ran = false;
+    for (uint32_t t = 0; t < N.count; ++t) {
+        // what the wave's first lanes parked, before the loop or in the pass before, is read by every lane below
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const Lane ln = lane_of();
+        const uint32_t n_px = park_n[ln.q];
+        const bool go = ln.owner && !converge_stopped(parked(park_rgb, ln.q), parked(park_sq, ln.q), n_px, N.min_passes,
+                                                      N.tolerance);
+        const uint64_t live = __ballot(go);
+        if (live == 0) break;
+        ran = true;
+        const int i = ln.i, lr = ln.lr, a = ln.a, b = ln.b;
+        const int ic = i < P.width ? i : P.width - 1, j = lr < P.height ? lr : P.height - 1;
+        const uint32_t w = rtj::jitter_word((uint32_t)lr * (uint32_t)P.width + (uint32_t)i, Q.seed + n_px);
+        const int n = a + (b << s);                         // time index a + S b
+        const double sigma = shutter * ((double)(2 * ((n << jl) + rtj::jitter_level(w, 6, jl)) + 1 - (1 << (s + sj))) *
+                                        ldexp(1.0, -(s + sj)));
+        // the camera of the lane's time
+        const d3 eye = add(ld3(P.eye), scl(sigma, ld3(C.eye_move)));
+        const d3 look = add(ld3(P.look), scl(sigma, ld3(C.look_move)));
+        const d3 ld = sub(look, eye);
+        const d3 right = cam_normalize(cross(ld, ld3(C.up)));
+        const d3 upp = cam_normalize(cross(right, ld));
+        // screen_point of the fine camera at that time
+        const int fi = (ic << jl) + rtj::jitter_level(w, 0, jl), fj = (j << jl) + rtj::jitter_level(w, 1, jl);
+        const d3 sp = add(add(look, scl(Q.pitch_f * (double)(fi + Q.bottom_fx), right)),
+                          scl(Q.pitch_f * (double)(fj + Q.bottom_fy), upp));
+        const double inv_sj = ldexp(1.0, -sj);
+        const auto t_of = [&](int c, int kd) { return (double)(2 * ((c << jl) + kd) + 1 - (1 << sj)) * inv_sj; };
+        const double ta = t_of(a, rtj::jitter_level(w, 2, jl)), tb = t_of(b, rtj::jitter_level(w, 3, jl));
+        const double ga = t_of(a, rtj::jitter_level(w, 4, jl)), gb = t_of(b, rtj::jitter_level(w, 5, jl));
+        const d3 e = add(add(eye, scl(aperture * ta, right)), scl(aperture * tb, upp));
+        const double ex = e.x - S->bc[0], ey = e.y - S->bc[1], ez = e.z - S->bc[2];   // hits_ok_from, the swept proof
+        V.hits_ok = (M->hits_inside != 0) & (ex * ex + ey * ey + ez * ez <= M->hits_lim2);
+        const Motion mo{sigma, M};
+        uint32_t seg = 0, sh = 0;
+        d3 col = trace_generic<B, TRANSP, TREE, 64, true, true>(V, e, sp, smem, &seg, &sh,
+                                                                LightShift{light_size * ga, light_size * gb}, &mo);
+        reduce_samples(s, 8, col, seg, sh);
+        const Lane after = lane_of();
+        int l = threadIdx.x;
+        asm volatile("" : "+v"(l));
+        if (after.owner && ((live >> l) & 1ull)) {          // nothing of a stopped pixel's ray reaches the state
+            const int q = after.q;
+            const uint32_t np = park_n[q];
+            const d3 v2 = mk(col.x * col.x, col.y * col.y, col.z * col.z);
+            const d3 acc = np == 0 ? col : add(parked(park_rgb, q), col);
+            const d3 sq = np == 0 ? v2 : add(parked(park_sq, q), v2);
+            park(park_rgb, q, acc);
+            park(park_sq, q, sq);
+            park_rc[q] += seg;
+            park_rc[npix + q] += sh;
+            park_n[q] = np + 1u;
+        }
+    }
+    const Lane ln = lane_of();
+    bool open = false;                                      // the pixel is not stopped on its final state
+    if (ln.owner) {
+        const size_t k = ln.k;
+        const int q = ln.q;
+        const d3 acc = parked(park_rgb, q), sq = parked(park_sq, q);
+        const uint32_t n = park_n[q], seg_sum = park_rc[q], sh_sum = park_rc[npix + q];
+        if (ran) {
+            accum[3 * k] = acc.x; accum[3 * k + 1] = acc.y; accum[3 * k + 2] = acc.z;
+            accum2[3 * k] = sq.x; accum2[3 * k + 1] = sq.y; accum2[3 * k + 2] = sq.z;
+            count[k] = n;
+        }
+        if (N.last) {
+            const double cnt = (double)n;
+            store_sampled(P, k, mk(acc.x / cnt, acc.y / cnt, acc.z / cnt), seg_sum, sh_sum, o32, o8, o64, orc2);
+            open = !converge_stopped(acc, sq, n, N.min_passes, N.tolerance);
+        } else if (orc2) {
+            orc2[2 * k] = seg_sum; orc2[2 * k + 1] = sh_sum;
+        }
+    }
+    if (N.last && active) {
+        const uint64_t still = __ballot(open);
+        if (still != 0 && threadIdx.x == 0) atomicAdd(active, (uint32_t)__popcll(still));
+    }
+}
+
 // A launch of one of the kernels.
 struct SampledLaunch {
     int variant;                               // trace_variant()
@@ -993,13 +1284,18 @@ struct SampledLaunch {
     // rt_accum_window_kernel, rt_converge_window_kernel: the window as the kernels take it; accum, accum2, npasses and
     // the four outputs then hold the pointers moved back to frame pixel (0, 0)
     WindowParams window;
+    // rt_accum_windows_kernel, rt_converge_windows_kernel: the context's window table as the kernels take it (the
+    // buffer pointers are the caller's, unmoved)
+    WindowListParams windows;
 };
 
 // Defined once per depth B in rt_adaptive_b<B>.o (rt_adaptive.hip), per kind in rt_lens_k<kind>_b<B>.o (rt_lens.hip)
 // the adaptive lens render's two in rt_lens_adaptive_b<B>.o (rt_lens_adaptive.hip), the jittered render's in
 // rt_jitter_b<B>.o (rt_jitter.hip), the shutter render's in rt_shutter_b<B>.o (rt_shutter.hip) and the accumulating
 // render's in rt_accum_b<B>.o (rt_accum.hip); the converging render's in rt_converge_b<B>.o (rt_converge.hip); their
-// windowed forms in rt_accum_window_b<B>.o (rt_accum_window.hip) and rt_converge_window_b<B>.o (rt_converge_window.hip).
+// windowed forms in rt_accum_window_b<B>.o (rt_accum_window.hip) and rt_converge_window_b<B>.o (rt_converge_window.hip);
+// the list forms in rt_accum_windows_b<B>.o (rt_accum_windows.hip) and rt_converge_windows_b<B>.o
+// (rt_converge_windows.hip).
 template <int B>
 hipError_t launch_refine(const SampledLaunch& L);
 template <int B>
@@ -1018,6 +1314,10 @@ template <int B>
 hipError_t launch_accum_window(const SampledLaunch& L);
 template <int B>
 hipError_t launch_converge_window(const SampledLaunch& L);
+template <int B>
+hipError_t launch_accum_windows(const SampledLaunch& L);
+template <int B>
+hipError_t launch_converge_windows(const SampledLaunch& L);
 template <int B, bool AREA, bool MOTION>
 hipError_t launch_lens(const SampledLaunch& L);
 #define RT_DECLARE_SAMPLED(B)                                         \
@@ -1039,6 +1339,10 @@ hipError_t launch_lens(const SampledLaunch& L);
     hipError_t launch_accum_window<B>(const SampledLaunch& L);        \
     template <>                                                       \
     hipError_t launch_converge_window<B>(const SampledLaunch& L);     \
+    template <>                                                       \
+    hipError_t launch_accum_windows<B>(const SampledLaunch& L);       \
+    template <>                                                       \
+    hipError_t launch_converge_windows<B>(const SampledLaunch& L);    \
     template <>                                                       \
     hipError_t launch_lens<B, false, false>(const SampledLaunch& L);  \
     template <>                                                       \
@@ -1195,6 +1499,35 @@ hipError_t launch_converge_window_impl(const SampledLaunch& L) {
                            lds + converge_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera,
                            n, L.window, L.aperture, L.light_size, L.shutter, tile_rows, L.accum, L.accum2, L.npasses,
                            L.active, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+// The grid of the list kernels: one wave per tile of the list, `grid_x` (WindowListParams) of them per row of the grid;
+// a last row that is not full is padded with waves that store nothing, as lens_grid's last slice is.
+inline dim3 window_list_grid(const WindowListParams& t) {
+    return dim3(std::min(t.tiles, t.grid_x), (t.tiles + t.grid_x - 1) / t.grid_x, 1u);
+}
+
+template <int B>
+hipError_t launch_accum_windows_impl(const SampledLaunch& L) {
+    const dim3 g = window_list_grid(L.windows);
+    const AccumParams n{L.first_pass, L.passes, L.call_first};
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_accum_windows_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64),
+                           lds + accum_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera, n,
+                           L.windows, L.aperture, L.light_size, L.shutter, L.accum, L.o32, L.o8, L.o64, L.orc2);
+    });
+}
+
+template <int B>
+hipError_t launch_converge_windows_impl(const SampledLaunch& L) {
+    const dim3 g = window_list_grid(L.windows);
+    const ConvergeParams n{L.tolerance, L.passes, L.min_passes, L.later ? 1u : 0u, L.last ? 1u : 0u};
+    return launch_sampled<B>(L.variant, [&](auto transp, auto tree, size_t lds) {
+        hipLaunchKernelGGL((rt_converge_windows_kernel<B, decltype(transp)::value, decltype(tree)::value>), g, dim3(64),
+                           lds + converge_park_bytes(L.P.ss_log2), L.stream, L.scene, L.motion, L.P, L.jitter, L.camera,
+                           n, L.windows, L.aperture, L.light_size, L.shutter, L.accum, L.accum2, L.npasses, L.active,
+                           L.o32, L.o8, L.o64, L.orc2);
     });
 }
 

@@ -75,6 +75,27 @@ def window_plan(width: int, height: int, parts: int) -> List[tuple]:
     return plan
 
 
+def band_windows(width: int, height: int, n_ranks: int, rank: int, band_height: int) -> List[tuple]:
+    """The windows (0, y, width, h) of `rank` in a round-robin band split, in ascending y, for Tracer.set_windows: the
+    frame is cut into bands of `band_height` rows, bottom to top (the last one may be shorter), and band b goes to rank
+    b mod n_ranks — the split that balances where contiguous strips (window_plan) do not, and which one list call
+    renders in one launch per launch group.  A rank with no band gets an empty list (set no list of it).  The ranks'
+    lists partition the frame.
+
+    This is the row ownership of the plain render's multi-GPU path: with rt_rows {band_height, n_ranks, rank}
+    rt_global_row maps a rank's local row lr to image row ((lr // hb) * n_ranks + rank) * hb + lr % hb, i.e. to the
+    rows of exactly these windows, in this order.  rt_band_plan (csrc/rt_host.cpp; rt_group_plan.cpp's rt_group_plan_frame
+    calls it) chooses that path's band height — 8, the tile height, when asked for 0 — and the rows of the largest
+    slab; it leaves what it is given above 0 unchanged, so band_windows(..., band_height=hb) with the hb it returns is
+    the same split.  band_windows has no default height and calls nothing: a pure function."""
+    if width < 1 or height < 1 or n_ranks < 1 or band_height < 1:
+        raise ValueError("width, height, n_ranks and band_height must be at least 1")
+    if rank < 0 or rank >= n_ranks:
+        raise ValueError("rank must lie in 0 .. n_ranks - 1")
+    return [(0, y, width, min(band_height, height - y))
+            for y in range(rank * band_height, height, n_ranks * band_height)]
+
+
 def _host_staged(group=None) -> bool:
     """gloo over device tensors: the rehearsal of the RCCL path on one GPU (bench.py --backend gloo) stages
     the exchange through host memory; RCCL moves device memory directly."""

@@ -29,6 +29,7 @@ class Tracer:
         self._ctx = ctypes.c_void_p()
         abi.check(abi.lib().rt_ctx_create(device, ctypes.byref(self._ctx)), "rt_ctx_create")
         self._scene = None
+        self._windows = None                   # set_windows: (width, height, layout, elements) of the list in force
 
     def close(self):
         if self._ctx:
@@ -454,6 +455,153 @@ class Tracer:
         self.render_converge_window_into(cam, motion, width, height, window, depth, samples, jitter, seed, passes,
                                          min_passes, tolerance, aperture, light_size, shutter, state, bufs, active,
                                          stream)
+        return bufs, state, active
+
+    # --------------------------------------- lists of windows of the accumulating and converging renders
+    _LAYOUTS = {"inplace": abi.RT_WINDOWS_IN_PLACE, "packed": abi.RT_WINDOWS_PACKED}
+
+    def set_windows(self, width: int, height: int, windows, layout: str = "inplace"):
+        """rt_set_windows: the list of disjoint windows (x0, y0, w, h) of the width x height frame the list renders
+        below draw, and how their buffers are laid out: "inplace" (full-frame buffers) or "packed" (every window dense,
+        one after the other in list order, in flat buffers).  windows = None clears the list.  Synchronous.  -> the
+        number of per-pixel elements a buffer must hold (0 for a cleared list).  The Tracer remembers the list's
+        frame, layout and elements for its buffer checks: a list set on the same context behind its back (the C host
+        conveniences rt_render_*_windows) is not seen by them — set lists through this method."""
+        if windows is None:
+            abi.check(abi.lib().rt_set_windows(self._ctx, 0, 0, None, 0, 0), "rt_set_windows")
+            self._windows = None
+            return 0
+        if layout not in self._LAYOUTS:
+            raise ValueError('layout must be "inplace" or "packed"')
+        try:
+            wins = [tuple(int(v) for v in w) for w in windows]
+            arr = (abi.rt_window * max(len(wins), 1))(*[abi.rt_window(x0, y0, w, h, 0) for x0, y0, w, h in wins])
+        except (TypeError, ValueError):
+            raise ValueError("windows must be a sequence of (x0, y0, width, height)") from None
+        # (rt_set_windows validates the list itself: no rt_window_list_plan call, whose disjointness check it repeats)
+        abi.check(abi.lib().rt_set_windows(self._ctx, width, height, arr, len(wins), self._LAYOUTS[layout]),
+                  "rt_set_windows")
+        elements = sum(w * h for _, _, w, h in wins) if layout == "packed" else width * height
+        self._windows = (width, height, layout, elements)
+        return elements
+
+    def _windows_shape(self, c: int):
+        """The shape of a C-channel buffer of the list in force: the full frame's in place, (elements[, C]) packed."""
+        if self._windows is None:
+            raise ValueError("no list of windows set (set_windows)")
+        width, height, layout, elements = self._windows
+        lead = (elements,) if layout == "packed" else (height, width)
+        return lead + ((c,) if c > 1 else ())
+
+    def alloc_windows(self, rgba32f=True, rgba8=False, rgb64f=False, raycount=False):
+        """The output buffers of a list render, as alloc_ss() gives them for a frame, laid out for the list in force:
+        full-frame tensors in place, flat (elements, C) tensors packed.  Uninitialised."""
+        dev = torch.device("cuda", self.device)
+        bufs = {}
+        for name, want in (("rgba32f", rgba32f), ("rgba8", rgba8), ("rgb64f", rgb64f), ("raycount", raycount)):
+            if want:
+                dtype, c = self._WINDOW_BUFS[name]
+                bufs[name] = torch.empty(self._windows_shape(c), dtype=dtype, device=dev)
+        return bufs
+
+    def alloc_windows_accum(self):
+        """The running sums of render_accum_windows_into() for the list in force, uninitialised."""
+        return torch.empty(self._windows_shape(3), dtype=torch.float64, device=torch.device("cuda", self.device))
+
+    def alloc_windows_converge(self):
+        """The state (accum, accum2, count) of render_converge_windows_into() for the list in force; count zeroed."""
+        dev = torch.device("cuda", self.device)
+        return (torch.empty(self._windows_shape(3), dtype=torch.float64, device=dev),
+                torch.empty(self._windows_shape(3), dtype=torch.float64, device=dev),
+                torch.zeros(self._windows_shape(1), dtype=torch.int32, device=dev))
+
+    def _windows_ptrs(self, width: int, height: int, tensors: dict):
+        """{name: pointer} of the buffers of a list render, each checked to be a contiguous HIP tensor of its type with
+        at least the elements the list in force needs."""
+        if self._windows is None:
+            raise ValueError("no list of windows set (set_windows)")
+        if (width, height) != self._windows[:2]:
+            raise ValueError(f"the list of windows is of the {self._windows[0]} x {self._windows[1]} frame")
+        ptrs = {}
+        for name, t in tensors.items():
+            if t is None:
+                ptrs[name] = None
+                continue
+            dtype, c = self._WINDOW_BUFS[name]
+            if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < self._windows[3] * c:
+                raise ValueError(f"{name} must be a contiguous HIP tensor of {dtype} holding {self._windows[3]} "
+                                 f"elements of {c} (alloc_windows)")
+            ptrs[name] = ctypes.c_void_p(t.data_ptr())
+        return ptrs
+
+    def render_accum_windows_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int,
+                                  height: int, depth: int, samples: int, jitter: int, seed: int, first_pass: int,
+                                  passes: int, aperture: float, light_size: float, shutter: float, accum: torch.Tensor,
+                                  bufs: dict, stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_accum_windows_dev: render_accum_into() for the pixels of every window of the list in force
+        (set_windows) in one launch per launch group, with the full frame's bytes; nothing else of the buffers
+        (alloc_windows_accum(), alloc_windows()) is touched.  Asynchronous on `stream` (default: torch's current
+        stream)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if accum is None:
+            raise ValueError("accum is required")
+        p = self._windows_ptrs(width, height, {"accum": accum, **{k: bufs.get(k) for k in
+                                                                  ("rgba32f", "rgba8", "rgb64f", "raycount")}})
+        abi.check(abi.lib().rt_render_accum_windows_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height, depth,
+            samples, jitter, int(seed) & 0xFFFFFFFF, int(first_pass), int(passes), float(aperture), float(light_size),
+            float(shutter), p["accum"], p["rgba32f"], p["rgba8"], p["rgb64f"], p["raycount"],
+            ctypes.c_void_p(st.cuda_stream)), "rt_render_accum_windows_dev")
+        return bufs
+
+    def render_accum_windows(self, cam, motion, width, height, depth, samples, jitter, seed, first_pass, passes,
+                             aperture, light_size, shutter, accum=None, rgba32f=True, rgba8=False, rgb64f=False,
+                             raycount=False, stream=None):
+        """-> (the buffers of alloc_windows(), the accumulator): `accum` continued, or a new one when it is None (then
+        first_pass must be 0)."""
+        if accum is None:
+            if first_pass != 0:
+                raise ValueError("first_pass > 0 continues a sum: pass its accum")
+            accum = self.alloc_windows_accum()
+        bufs = self.alloc_windows(rgba32f, rgba8, rgb64f, raycount)
+        self.render_accum_windows_into(cam, motion, width, height, depth, samples, jitter, seed, first_pass, passes,
+                                       aperture, light_size, shutter, accum, bufs, stream)
+        return bufs, accum
+
+    def render_converge_windows_into(self, cam: abi.rt_camera, motion: Optional[abi.rt_camera_motion], width: int,
+                                     height: int, depth: int, samples: int, jitter: int, seed: int, passes: int,
+                                     min_passes: int, tolerance: float, aperture: float, light_size: float,
+                                     shutter: float, state, bufs: dict, active: Optional[torch.Tensor] = None,
+                                     stream: Optional[torch.cuda.Stream] = None):
+        """rt_render_converge_windows_dev: render_converge_into() for the pixels of every window of the list in force in
+        one launch per launch group, with the full frame's bytes; `active` counts the list's pixels."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        accum, accum2, count = state
+        if accum is None or accum2 is None or count is None:
+            raise ValueError("state must be (accum, accum2, count)")
+        if active is not None and (active.dtype != torch.int32 or active.numel() != 1):
+            raise ValueError("active must be a one-element int32 tensor")
+        p = self._windows_ptrs(width, height, {"accum": accum, "accum2": accum2, "count": count,
+                                               **{k: bufs.get(k) for k in ("rgba32f", "rgba8", "rgb64f", "raycount")}})
+        abi.check(abi.lib().rt_render_converge_windows_dev(
+            self._ctx, ctypes.byref(cam), ctypes.byref(motion) if motion is not None else None, width, height, depth,
+            samples, jitter, int(seed) & 0xFFFFFFFF, int(passes), int(min_passes) & 0xFFFFFFFF, float(tolerance),
+            float(aperture), float(light_size), float(shutter), p["accum"], p["accum2"], p["count"], p["rgba32f"],
+            p["rgba8"], p["rgb64f"], p["raycount"], _ptr(active), ctypes.c_void_p(st.cuda_stream)),
+            "rt_render_converge_windows_dev")
+        return bufs
+
+    def render_converge_windows(self, cam, motion, width, height, depth, samples, jitter, seed, passes, min_passes,
+                                tolerance, aperture, light_size, shutter, state=None, rgba32f=True, rgba8=False,
+                                rgb64f=False, raycount=False, stream=None):
+        """-> (the buffers of alloc_windows(), the state, the list's active count as a one-element device tensor):
+        `state` continued, or a new one when it is None."""
+        if state is None:
+            state = self.alloc_windows_converge()
+        bufs = self.alloc_windows(rgba32f, rgba8, rgb64f, raycount)
+        active = torch.zeros((1,), dtype=torch.int32, device=torch.device("cuda", self.device))
+        self.render_converge_windows_into(cam, motion, width, height, depth, samples, jitter, seed, passes, min_passes,
+                                          tolerance, aperture, light_size, shutter, state, bufs, active, stream)
         return bufs, state, active
 
     # ------------------------------------------------------------ adaptive sampling of the lens family's renders
